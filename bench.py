@@ -19,6 +19,12 @@ return over RCCL: by default (`--gather per_chunk`) the whole [T, n, 4] observat
 all-gathered in chunks of `--chunk` steps on a dedicated stream under the following launches; the collective's
 inbound volume and rate are reported beside the HBM roofline.  `--gather final` exchanges only the last
 observation of a pass, `--gather per_step` one [n, 4] block per env-step (one emei_step launch each).
+
+A plain run does what the headline needs: set up, settle the clocks, warm up, time K passes, print the line (`roofline` from
+the timed passes' own HIP events at N = 1).  `--full` adds the measurements that take runs of their own: the CPU baseline
+(N = 1), and at N > 1 the kernel-only timing (`roofline`, `compute_only`), the other gather / exchange forms of the same job and
+RCCL's report of itself.  `--dump-outputs DIR` writes what the last timed pass returned (dump_outputs); a pass starts from the
+same synthetic inputs in every run with the same arguments.
 """
 import argparse
 import json
@@ -38,6 +44,7 @@ XGMI_PEAK_GBS = XGMI_LINKS * XGMI_LINK_GBS_BIDIR / 2
 SIMDS, CLOCK_GHZ = 1024, 2.4  # 256 CUs x 4 SIMDs, max shader clock (MI355X_MICROARCH.md, chip-level parameters)
 MEASURED_NS_PER_F64_INST = 2.0  # tools/op_cost.hip at 4 waves per SIMD, every SIMD busy (profiles/r03_op_cost.txt)
 MULTI_GPU_SHARD = 131072  # BASELINE configs[4]: 1 048 576 envs / 8 GPUs
+DUMP_BYTES = 60 * 10**6  # --dump-outputs: the sample's size, so that the files stay under 64 MB with their headers
 
 WORKLOADS = {
     # name: (env, envs_per_gpu, freq_rate, dt, horizon, act bytes, obs_dim, act_dim)
@@ -61,6 +68,29 @@ WORKLOADS = {
 def algorithmic_bytes_per_env_step(obs_dim, act_bytes):
     """Fused rollout, state in registers: read action, write obs f32 + reward f32 + done u8."""
     return act_bytes + 4 * obs_dim + 4 + 1
+
+
+def dump_outputs(sr, path):
+    """--dump-outputs: what the last timed pass returned to its caller (this rank's obs [T, n, obs_dim], reward [T, n] and done
+    [T, n] of every chunk) as float32 DIR/obs.npy, reward.npy, done.npy (done's bits as the values 0-3).  A full pass is larger
+    than DUMP_BYTES at the bench shapes: the files hold a fixed sample of envs, k sorted indices of
+    np.random.default_rng(0).choice(n, k, replace=False) with k as large as DUMP_BYTES allows (every env when they fit), over
+    every step (over s sorted steps of a second draw of the same generator when one env's steps alone do not fit)."""
+    import numpy as np
+    import torch
+
+    obs, rew, done = sr.out
+    T, n = rew.shape
+    cell = 4 * (sr.obs_dim + 2)  # float32 bytes of one (step, env): observation, reward, done
+    rng = np.random.default_rng(0)
+    k = min(n, max(1, DUMP_BYTES // (cell * T)))
+    envs = np.arange(n) if k == n else np.sort(rng.choice(n, k, replace=False))
+    s = min(T, DUMP_BYTES // (cell * k))
+    steps = np.arange(T) if s == T else np.sort(rng.choice(T, s, replace=False))
+    ei, si = torch.as_tensor(envs, device=rew.device), torch.as_tensor(steps, device=rew.device)
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("obs", obs), ("reward", rew), ("done", done)):
+        np.save(os.path.join(path, name + ".npy"), t.index_select(0, si).index_select(1, ei).float().cpu().numpy())
 
 
 def host_cpu_share():
@@ -330,7 +360,12 @@ def main():
                     help="body rollouts as (64 envs) x (k steps) work items: 0 = automatic (the default), -1 = one-piece launches, "
                          "k > 0 = k steps per item (emei_config.rollout_chunk_steps); results do not depend on it")
     ap.add_argument("--settle-ms", type=float, default=60.0, help="untimed clock-settle phase before the warm-up passes")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline (N = 1); at N > 1 the kernel-only timing "
+                         "(roofline, compute_only), the final-gather job, the other exchange form and RCCL's report")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed pass returned (a fixed sample of envs, float32 .npy; rank 0's shard) to DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--allow-profiler-env", action="store_true", help="self-launch N > 1 ranks even though a profiler preload is detected")
     ap.add_argument("--extras-timeout", type=float, default=300.0,
                     help="N > 1: seconds the additional measurements after the timed region (compute_only, value_final_gather, the other exchange form) may take "
@@ -338,6 +373,8 @@ def main():
     ap.add_argument("--no-rccl-info", action="store_true", help="do not switch on NCCL_DEBUG=INFO (N > 1, RCCL: the line reports what RCCL chose)")
     ap.add_argument("--per-step-api", action="store_true", help="also time one launch per env-step (emei_step)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a.gpus)  # does not return
@@ -364,7 +401,7 @@ def main():
 
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         backend = os.environ.get("EMEI_BENCH_BACKEND", "nccl")  # "nccl" is RCCL on ROCm
-        if backend == "nccl" and not a.no_rccl_info and "NCCL_DEBUG" not in os.environ:
+        if backend == "nccl" and a.full and not a.no_rccl_info and "NCCL_DEBUG" not in os.environ:
             # what RCCL chose (ranks, channels, algorithm / protocol of the all-gather) goes into the line: its INFO log, per rank, to a file
             rccl_log = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"emei_bench_rccl_{os.getpid()}_r{rank}.log")
             os.environ.update(NCCL_DEBUG="INFO", NCCL_DEBUG_SUBSYS="INIT,ENV,TUNING", NCCL_DEBUG_FILE=rccl_log)
@@ -380,7 +417,7 @@ def main():
             dist.barrier()
 
     from emei_amd.engine import Engine
-    from emei_amd.sharding import ShardedRollout
+    from emei_amd.sharding import ShardedRollout, synthetic_init_state
 
     w = dict(WORKLOADS[a.workload])
     sharded_cartpole = world > 1 and a.workload.startswith("cartpole")
@@ -398,10 +435,14 @@ def main():
         desc = (f"CartPoleSwingUp-v0, {world * N} parallel envs sharded {world}xMI355X ({N} per GPU) with RCCL all-gather of obs"
                 + (" (BASELINE configs[4])" if world == 8 else " (BASELINE configs[4]'s shard size)"))
     sr.make_synthetic_inputs()
+    s0 = synthetic_init_state(env, world * N, sr.lo, sr.hi, sr.seed)
+    s0 = None if s0 is None else torch.as_tensor(s0, dtype=torch.float64, device=sr.device)
 
     # Untimed settle phase before the W warm-up passes: after idling, the first ~10-30 ms of back-to-back
     # launches run ~15 % slower (clocks ramp up; measured: K = 10 gives 0.35 ms per pass after 2 warm-up
-    # passes, 0.295 ms after 100), whatever W the caller chose.
+    # passes, 0.295 ms after 100), whatever W the caller chose.  It runs a time-dependent number of passes, so
+    # the envs go back to the synthetic start after it (state, step and episode counters; device-side, no idle
+    # gap): the W + K passes that follow, and what they return, are the same in every run with the same arguments.
     if a.settle_ms > 0:
         sr.run_pass()
         torch.cuda.synchronize()
@@ -416,6 +457,10 @@ def main():
         for _ in range(min(2000, int(a.settle_ms * 1e-3 / max(t_one, 1e-6)) + 1)):
             sr.run_pass()
         torch.cuda.synchronize()
+        if s0 is None:
+            sr.engine.reset(sr.seed)
+        else:
+            sr.engine.set_state(s0)
     for _ in range(a.warmup):
         sr.run_pass()
     torch.cuda.synchronize()
@@ -438,17 +483,19 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(sr, a.dump_outputs)  # before anything else runs a pass of `sr`
 
     # average launch duration of the dominant kernel over the timed region: at one GPU a pass is
     # exactly one rollout launch, so the event pair around the K passes / K is the kernel's duration
-    # (plus the ~1.5 us dependent-launch gap); with several ranks the all-gather sits between launches
+    # (plus the ~1.5 us dependent-launch gap); with several ranks the all-gather sits between launches,
+    # and the kernel alone takes K more passes of its own (--full)
     single_launch = world == 1 and sr.n_chunks == 1
-    kernel_ms = ev0.elapsed_time(ev1) / a.steps if single_launch else sr.timed_launches_ms(a.steps)
+    kernel_ms = ev0.elapsed_time(ev1) / a.steps if single_launch else (sr.timed_launches_ms(a.steps) if a.full else None)
     total_env_steps = world * N * T * a.steps
     value = total_env_steps / el
     bpes = algorithmic_bytes_per_env_step(sr.obs_dim, sr.action_bytes)
     T_launch = sr.chunk  # env-steps per env of ONE launch (= the horizon unless the pass is chunked)
-    achieved = bpes * N * T_launch / (kernel_ms * 1e-3) / 1e9
     # HBM bytes per launch from the rocprofv3 PMC passes (profiles/traffic.json, written from
     # tools/collect_profiles.sh output with the gfx950 FETCH_SIZE correction); only valid for the
     # default shape it was collected on
@@ -464,7 +511,7 @@ def main():
     # the copied counters describe the kernel the profile was taken on: flag the line when this run's kernel no longer
     # runs as long as that one did (> 10 %: a kernel changed without tools/profile_all.sh, or a very different box)
     prof_us = prof.get("rocprof_kernel_avg_us")
-    profile_stale = bool(prof_us) and abs(kernel_ms * 1e3 - prof_us) > 0.10 * prof_us
+    profile_stale = bool(prof_us) and kernel_ms is not None and abs(kernel_ms * 1e3 - prof_us) > 0.10 * prof_us
 
     out = {
         "metric": "env-steps/s", "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": a.steps,
@@ -480,15 +527,17 @@ def main():
                                       "per_step": "the [n,obs_dim] observation of every env-step, one all-gather per step"}[gather]
                                      + (" over RCCL, on a dedicated stream under the following launches" if a.exchange != "peer_write" else
                                         " — here WITHOUT a collective: written by the rollout kernel into every rank's hipIpc-mapped buffer, one host barrier per chunk")) if world > 1 else "n/a (1 GPU)"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "traffic_source": (f"{prof.get('profile', 'profiles/')} via profiles/traffic.json: rocprofv3 FETCH_SIZE x2 + WRITE_SIZE "
-                                        "passes of this command, collected separately, NOT measured in this run") if traffic else None,
-                     "profile_stale": profile_stale, "profile_kernel_avg_us": prof_us,
-                     "kernel": sr.kernel_name, "kernel_ms": kernel_ms, "algorithmic_bytes_per_env_step": bpes,
-                     "algorithmic_bytes_per_launch": bpes * N * T_launch},
     }
-    if valu:
+    if kernel_ms is not None:
+        achieved = bpes * N * T_launch / (kernel_ms * 1e-3) / 1e9
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                           "traffic_source": (f"{prof.get('profile', 'profiles/')} via profiles/traffic.json: rocprofv3 FETCH_SIZE x2 + WRITE_SIZE "
+                                              "passes of this command, collected separately, NOT measured in this run") if traffic else None,
+                           "profile_stale": profile_stale, "profile_kernel_avg_us": prof_us,
+                           "kernel": sr.kernel_name, "kernel_ms": kernel_ms, "algorithmic_bytes_per_env_step": bpes,
+                           "algorithmic_bytes_per_launch": bpes * N * T_launch}
+    if valu and kernel_ms is not None:
         # second roofline for the VALU-bound bodies: executed vector instructions per launch (SQ_INSTS_VALU, counted per
         # wave) x 4 cycles of issue each (MI355X_MICROARCH.md: one wave issues a VALU instruction per >= 4 cycles; f64 FMA
         # and f32 alike) / (SIMDs x max clock x kernel time) = the fraction of the chip's vector-issue slots in use
@@ -525,7 +574,7 @@ def main():
                                + ("; with --gather per_chunk / per_step every rank receives the whole observation return of its peers, "
                                   "so N > 1 is bound by xGMI by design, not by the rollout kernel" if gather != "final" else "")}
     guard = None
-    if world > 1:
+    if world > 1 and a.full:
         # everything below runs collectives of its own AFTER the timed region: under a deadline, so that a hang costs the extras, not the line
         guard = ExtrasGuard(out, rank, a.extras_timeout).start()
         try:
@@ -604,7 +653,7 @@ def main():
             out["extras_error"] = repr(e)[:500]
     if a.per_step_api and rank == 0:
         out["per_step_api"] = sr.time_per_step_api()
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(env, N, w["freq_rate"], w["dt"], a.integrator or w.get("integrator", "euler"), a.solver)
     if guard is not None and not guard.finish():
         time.sleep(30)  # the deadline fired: its thread prints rank 0's line and ends the process

@@ -134,3 +134,48 @@ def test_extras_guard_prints_the_line_and_leaves_when_the_deadline_passes(tmp_pa
     assert r1.returncode == 0 and r1.stdout.strip() == ""
     ok = subprocess.run([sys.executable, str(prog), "0", "fine"], capture_output=True, text=True, timeout=60)
     assert ok.returncode == 0 and "extras_timed_out" not in ok.stdout and ok.stdout.count("{") == 1
+
+
+def test_dump_outputs_writes_a_bounded_seeded_sample(tmp_path):
+    """bench.dump_outputs: every env and step when they fit; otherwise a sorted default_rng(0) sample of envs over every step
+    (and of steps when one env's alone do not fit), float32, within 64 MB, the same files on every call."""
+    torch = pytest.importorskip("torch")
+    import types
+
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def fake(T, n, obs_dim):
+        g = torch.Generator().manual_seed(3)
+        return types.SimpleNamespace(obs_dim=obs_dim, out=(torch.randn(T, n, obs_dim, generator=g), torch.randn(T, n, generator=g),
+                                                           torch.randint(0, 4, (T, n), generator=g, dtype=torch.uint8)))
+
+    def load(d):
+        return [np.load(tmp_path / d / f"{k}.npy") for k in ("obs", "reward", "done")]
+
+    small = fake(7, 5, 4)
+    bench.dump_outputs(small, str(tmp_path / "small"))
+    for got, want in zip(load("small"), small.out):
+        assert got.dtype == np.float32 and np.array_equal(got, want.float().numpy())
+
+    for name, (T, n, obs_dim) in (("envs", (1000, 8192, 4)), ("steps", (6 * 10**6, 1, 1))):
+        sr = fake(T, n, obs_dim)
+        bench.dump_outputs(sr, str(tmp_path / name))
+        bench.dump_outputs(sr, str(tmp_path / (name + "2")))
+        files = load(name)
+        assert sum(os.path.getsize(tmp_path / name / f"{k}.npy") for k in ("obs", "reward", "done")) <= 64 * 10**6
+        rng = np.random.default_rng(0)
+        k = min(n, max(1, bench.DUMP_BYTES // (4 * (obs_dim + 2) * T)))
+        envs = np.arange(n) if k == n else np.sort(rng.choice(n, k, replace=False))
+        s = min(T, bench.DUMP_BYTES // (4 * (obs_dim + 2) * k))
+        steps = np.arange(T) if s == T else np.sort(rng.choice(T, s, replace=False))
+        assert (len(envs) < n) == (name == "envs") and (len(steps) < T) == (name == "steps")
+        for got, again, full in zip(files, load(name + "2"), sr.out):
+            assert np.array_equal(got, again) and np.array_equal(got, full.numpy()[steps][:, envs].astype(np.float32))
+
+
+def test_steps_must_be_positive():
+    p = subprocess.run([sys.executable, "bench.py", "--steps", "0"], cwd=ROOT, capture_output=True, text=True, timeout=60)
+    assert p.returncode == 2 and "--steps" in p.stderr and not p.stdout.strip()

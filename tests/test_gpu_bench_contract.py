@@ -28,10 +28,10 @@ def _line(cmd, env=None, timeout=300):
     return json.loads(lines[0])
 
 
-def _check_common(j, n_gpus, steps, warmup):
+def _check_common(j, n_gpus, steps, warmup, full=True):
     for k, t in REQUIRED.items():
-        if k == "cpu_baseline" and n_gpus > 1:
-            continue  # timed on rank 0 at N = 1 only
+        if k == "cpu_baseline" and (n_gpus > 1 or not full):
+            continue  # timed on rank 0 at N = 1 only, with --full
         assert k in j, k
         assert isinstance(j[k], t) or (t is float and isinstance(j[k], int)), (k, type(j[k]))
     assert "vs_baseline" in j and j["vs_baseline"] is None  # BASELINE.md holds no published number for this metric
@@ -54,7 +54,7 @@ def _check_common(j, n_gpus, steps, warmup):
 
 def test_default_single_gpu_line():
     steps, warmup = 5, 2
-    j = _line([sys.executable, "bench.py", "--steps", str(steps), "--warmup", str(warmup)])
+    j = _line([sys.executable, "bench.py", "--steps", str(steps), "--warmup", str(warmup), "--full"])
     _check_common(j, 1, steps, warmup)
     assert "65 536" in j["config"]["workload"] and "configs[1]" in j["config"]["workload"]
     # the whole timed region is K launches: a pass cannot be faster than its kernel
@@ -72,12 +72,44 @@ def test_default_single_gpu_line():
     assert j["value"] > 1e7  # north_star's floor
 
 
+def test_plain_line_and_its_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline and the roofline of its own timed passes, and no CPU baseline.
+    --dump-outputs writes what the last timed pass returned: the same files whatever the (time-dependent) settle phase ran, and
+    the same as W + K passes of the engine from the synthetic inputs."""
+    import numpy as np
+
+    from emei_amd.sharding import ShardedRollout
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    steps, warmup = 3, 1
+    for d, settle in (("a", []), ("b", ["--settle-ms", "0"])):
+        j = _line([sys.executable, "bench.py", "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path / d)] + settle)
+        _check_common(j, 1, steps, warmup, full=False)
+        assert "cpu_baseline" not in j and j["roofline"]["kernel_ms"] > 0
+    sr = ShardedRollout("CartPoleSwingUp", 65536, 1000, seed=0)
+    sr.make_synthetic_inputs()
+    for _ in range(warmup + steps):
+        sr.run_pass()
+    torch.cuda.synchronize()
+    bench.dump_outputs(sr, str(tmp_path / "c"))
+    sr.close()
+    size = 0
+    for name in ("obs", "reward", "done"):
+        a, b, c = (np.load(tmp_path / d / f"{name}.npy") for d in "abc")
+        assert a.dtype == np.float32 and a.shape[:2] == (1000, (60 * 10**6) // (1000 * 24)), (name, a.dtype, a.shape)
+        assert np.array_equal(a, b) and np.array_equal(a, c), name
+        size += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+    assert size <= 64 * 10**6
+
+
 @pytest.mark.parametrize("how", ["direct", "under_launcher"])
 def test_two_rank_line_over_gloo_sharing_the_gpu(how):
     """`python bench.py --gpus 2` exactly as the driver types it (bench.py starts its own ranks), and the same line when a
     launcher already did (torch.distributed.run)."""
     steps, warmup = 3, 1
-    args = ["bench.py", "--gpus", "2", "--steps", str(steps), "--warmup", str(warmup)]
+    args = ["bench.py", "--gpus", "2", "--steps", str(steps), "--warmup", str(warmup), "--full"]
     if how == "direct":
         cmd = [sys.executable] + args
     else:
@@ -123,7 +155,7 @@ def test_collective_is_the_other_exchange_when_direct_is_the_runs_own():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         e.pop(k, None)
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", str(steps), "--warmup", str(warmup), "--exchange", "direct",
-                        "--envs-per-gpu", "16384"], cwd=ROOT, env=e, capture_output=True, text=True, timeout=600)
+                        "--envs-per-gpu", "16384", "--full"], cwd=ROOT, env=e, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert j["config"]["exchange"] == "direct" and j["value_collective_exchange"]["exchange"] == "collective"
@@ -137,7 +169,7 @@ def test_peer_write_exchange_as_the_runs_own_form():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         e.pop(k, None)
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--exchange", "peer_write",
-                        "--envs-per-gpu", "16384"], cwd=ROOT, env=e, capture_output=True, text=True, timeout=600)
+                        "--envs-per-gpu", "16384", "--full"], cwd=ROOT, env=e, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert j["config"]["exchange"] == "peer_write" and "WITHOUT a collective" in j["config"]["obs_allgather"]
@@ -152,8 +184,8 @@ def test_a_hang_or_an_error_after_the_timed_region_does_not_cost_the_line(how):
     e = dict(os.environ, EMEI_BENCH_SHARE_GPU="1", EMEI_BENCH_BACKEND="gloo", EMEI_BENCH_TEST_EXTRAS=how)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         e.pop(k, None)
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--envs-per-gpu", "16384", "--extras-timeout", "5"],
-                       cwd=ROOT, env=e, capture_output=True, text=True, timeout=600)
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--envs-per-gpu", "16384", "--extras-timeout", "5",
+                        "--full"], cwd=ROOT, env=e, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -175,7 +207,7 @@ def test_a_failing_rank_fails_the_self_launched_bench():
 def test_other_workloads_carry_their_own_cpu_baseline():
     """configs[2] / configs[3]: the CPU oracle of the SAME env kind is timed beside the GPU number (bounded sample)."""
     for wl, frac in (("invpend", "InvertedPendulum"), ("cheetah", "HalfCheetahRunning")):
-        j = _line([sys.executable, "bench.py", "--workload", wl, "--steps", "3", "--warmup", "1"], timeout=600)
+        j = _line([sys.executable, "bench.py", "--workload", wl, "--steps", "3", "--warmup", "1", "--full"], timeout=600)
         c = j["cpu_baseline"]
         assert c["kind"] == "port" and c["value"] > 0 and frac in c["sample"] and c["cores"] >= 1
         assert c["one_core"]["cores"] == 1 and 0 < c["one_core"]["value"] <= c["value"] * 1.05
