@@ -703,6 +703,41 @@ extern "C" EMEI_API int emei_step(emei_env* h, const void* actions, int action_d
     return emei_rollout(h, 1, actions, action_dtype, obs_out, reward_out, done_out, flags, stream);
 }
 
+extern "C" EMEI_API int emei_evaluate_sequences(emei_env* h, int32_t horizon, int32_t n_candidates, const void* actions, int action_dtype,
+                                                double discount, const double* start_state, double* return_out, int32_t* length_out,
+                                                float* final_obs_out, void* stream) {
+    // the scalar arguments first: they are refused without a handle and before any HIP call
+    if (horizon < 1) return fail(EMEI_ERR_INVALID, "emei_evaluate_sequences: horizon=%d < 1", horizon);
+    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "emei_evaluate_sequences: n_candidates=%d < 1", n_candidates);
+    if (!(discount > 0.0 && discount <= 1.0))
+        return fail(EMEI_ERR_INVALID, "emei_evaluate_sequences: discount=%g is outside (0, 1]", discount);
+    if (!h) return fail(EMEI_ERR_INVALID, "emei_evaluate_sequences: null handle");
+    if (!actions || !return_out || !length_out) return fail(EMEI_ERR_INVALID, "emei_evaluate_sequences: null argument");
+    const int64_t nk = h->cfg.n_envs * (int64_t)n_candidates;
+    if (nk > INT32_MAX)  // one lane per candidate, 32-bit lane indices (as emei_create's bound on n_envs)
+        return fail(EMEI_ERR_INVALID, "emei_evaluate_sequences: n_envs * n_candidates = %lld exceeds 2^31 - 1", (long long)nk);
+    if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
+    EMEI_ON_DEVICE(h, "emei_evaluate_sequences");
+    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "emei_evaluate_sequences: call reset before using the state");
+    int rc;
+    if (!steps_as_body(h->cfg)) {  // the kernel family emei_rollout runs for this handle
+        PendLaunch L = pend_base(h, stream);
+        L.op = PEND_OP_PLAN;
+        L.actions = actions, L.action_dtype = action_dtype, L.n_steps = horizon;
+        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
+        L.return_out = return_out, L.length_out = length_out, L.obs_out = final_obs_out;
+        rc = pend_launch(L);
+    } else {
+        BodyLaunch L = body_base(h, stream);
+        L.op = BODY_OP_PLAN;
+        L.actions = actions, L.n_steps = horizon;
+        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
+        L.return_out = return_out, L.length_out = length_out, L.obs_out = final_obs_out;
+        rc = body_launch(L);
+    }
+    return rc == EMEI_OK ? rc : fail(rc, "emei_evaluate_sequences: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+}
+
 extern "C" EMEI_API int emei_compact_done(emei_env* h, int32_t* idx_out, int32_t* count_out, void* stream) {
     if (!h || !idx_out || !count_out) return fail(EMEI_ERR_INVALID, "emei_compact_done: null argument");
     EMEI_ON_DEVICE(h, "emei_compact_done");

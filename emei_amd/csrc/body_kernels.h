@@ -161,7 +161,8 @@ __device__ __forceinline__ void body_substep(typename Body::real (&s)[Body::NS],
 }
 
 enum BodyOp { BODY_OP_ROLLOUT = 0, BODY_OP_RESET, BODY_OP_GET_OBS, BODY_OP_INIT_OBS, BODY_OP_REWARD, BODY_OP_TERMINAL, BODY_OP_NEXT_OBS,
-              BODY_OP_OCCUPANCY /* host only: *selected = waves of the rollout kernel (of L.integrator) the current device holds at once */ };
+              BODY_OP_OCCUPANCY /* host only: *selected = waves of the rollout kernel (of L.integrator) the current device holds at once */,
+              BODY_OP_PLAN /* emei_evaluate_sequences: body_plan_kernel */ };
 
 // host-side launch descriptor (abi.hip -> body_dispatch.hip -> body_tu.hip)
 struct BodyLaunch {
@@ -198,6 +199,12 @@ struct BodyLaunch {
     int32_t resident_waves = 0;  // waves of the rollout kernel the device holds at once (automatic policy); 0 = unknown
     hipStream_t stream = nullptr;
     int* selected = nullptr;  // out: enum emei_kernel_id of the rollout kernel launched
+    // BODY_OP_PLAN (emei_evaluate_sequences): n_candidates per env, n_steps = the horizon, obs_out = final_obs [n * K, NO] or null
+    const double* start_rows = nullptr;  // [n, NS] float64; null = the handle's state
+    int32_t n_candidates = 1;
+    double discount = 1.0;
+    double* return_out = nullptr;   // [n * K]
+    int32_t* length_out = nullptr;  // [n * K]
 };
 int body_launch(const BodyLaunch& L);  // body_dispatch.hip
 
@@ -674,6 +681,78 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
+// emei_evaluate_sequences (core.py:18-37,190-193: the model a planner queries) for the bodies: lane j scores candidate
+// (i = j / K, k = j % K) of env i — `horizon` env-steps of actions [t, j, :] from env i's start state with the per-step
+// arithmetic of body_rollout_kernel (body_substep x freq_rate, Body::outputs; no observation noise), the state in registers.
+// ret / len / final_obs as pend_plan_kernel.  Lanes map onto waves as the envs of a rollout of n * K envs do, and every lane of
+// a wave keeps stepping until none is live — padding lanes parked as there, lanes past their terminal step without accumulating
+// — so that a wave-mate's state (the cheetah's constraint-slot lending, cheetah_model.h: `donor`) is what that rollout has.
+// A correctness path: actions are read per lane, not staged.
+template <class Body, bool RK4>
+__global__ void __launch_bounds__(kBlock)
+    body_plan_kernel(const typename Body::real* state, const double* start_rows, const float* actions, int64_t n_envs,
+                     int32_t n_cand, int32_t horizon, double discount, int freq_rate, int semi, typename Body::Model m,
+                     const SinCosEntry* trig_tab, unsigned long long* cap_hits, double* ret_out, int32_t* len_out, float* final_obs) {
+    using R = typename Body::real;
+    constexpr int NS = Body::NS, NO = Body::NO, NA = Body::NA;
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table(trig_s, trig_tab);  // every thread reaches the barrier
+    TrigCtx trig;
+    trig.tab = trig_s;
+    __shared__ R scratch_s[(Body::kScratchPerLane > 0 ? Body::kScratchPerLane : 1) * (Body::kScratchPerLane > 0 ? kBlock : 1)];
+    if constexpr (Body::kScratchPerLane > 0) trig.scratch = scratch_s;
+    trig.scratch_stride = kBlock;
+    trig.cap_hits = cap_hits;
+    const int64_t nk = n_envs * n_cand;
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool active = j < nk;
+    // Every lane loads (padding lanes env 0's row) and the padding lanes then take the parked state with a select: no
+    // divergent branch around the loads (the cheetah's RK4 instantiation spilled inside one, at a join tools/isa_scan.py flags)
+    const int64_t i = (active ? j : 0) / n_cand;
+    R s[NS], parked[NS];
+    if (start_rows) {  // wave-uniform; the caller's float64 rows are narrowed as emei_set_state narrows them (util_kernels.hip)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = (R)start_rows[i * NS + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = state[(int64_t)k * n_envs + i];
+    }
+    Body::park(parked);  // as body_rollout_kernel's padding lanes
+#pragma unroll
+    for (int k = 0; k < NS; ++k) s[k] = active ? s[k] : parked[k];
+    double ret = 0.0, g = 1.0;
+    bool live = active;
+    for (int t = 0; t < horizon; ++t) {
+        R ctrl[NA];  // padding lanes: zero, as the rollout's staging gives them
+#pragma unroll
+        for (int k = 0; k < NA; ++k) ctrl[k] = active ? (R)actions[((int64_t)t * nk + j) * NA + k] : R(0);
+        R pre[NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) pre[k] = s[k];
+        typename Body::Warm warm{};
+        for (int k = 0; k < freq_rate; ++k) body_substep<Body, RK4>(s, ctrl, m, semi != 0, trig, warm);
+        float o[NO];
+        R rew;
+        bool term;
+        Body::outputs(s, pre, ctrl, m, freq_rate, o, rew, term, trig);
+        if (live) {
+            ret = ret + g * (double)(float)rew;
+            g = g * discount;
+            // a lane's results leave at its last counted step: no observation is held in registers across the loop
+            if (term || t == horizon - 1) {
+                live = false;
+                ret_out[j] = ret;
+                len_out[j] = t + 1;
+                if (final_obs) {
+#pragma unroll
+                    for (int k = 0; k < NO; ++k) final_obs[j * NO + k] = o[k];
+                }
+            }
+        }
+        if (__ballot(live) == 0ull) break;  // wave-uniform
+    }
+}
+
 // every launch of one Body type (one translation unit instantiates exactly one Body: body_tu.hip)
 template <class Body>
 static int launch_body(const BodyLaunch& L) {
@@ -812,6 +891,21 @@ static int launch_body(const BodyLaunch& L) {
             } else {
                 return EMEI_ERR_UNSUPPORTED;  // e.g. the double pendulum's observation "wrap" is not invertible
             }
+        case BODY_OP_PLAN: {
+            // one lane per candidate; n * n_candidates < 2^31 (checked in abi.hip)
+            const dim3 pgrid((unsigned)((L.n * L.n_candidates + kBlock - 1) / kBlock));
+            const int semi = (int)(L.integrator == EMEI_INTEG_SEMI_IMPLICIT);
+            const SinCosEntry* tt = (const SinCosEntry*)L.trig;
+            if (L.integrator == EMEI_INTEG_RK4)
+                hipLaunchKernelGGL((body_plan_kernel<Body, true>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state, L.start_rows,
+                                   (const float*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, 0, m, tt,
+                                   L.cap_hits, L.return_out, L.length_out, L.obs_out);
+            else
+                hipLaunchKernelGGL((body_plan_kernel<Body, false>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state, L.start_rows,
+                                   (const float*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, semi, m, tt,
+                                   L.cap_hits, L.return_out, L.length_out, L.obs_out);
+            break;
+        }
         default: return EMEI_ERR_INVALID;
     }
     return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;

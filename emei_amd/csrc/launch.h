@@ -7,7 +7,7 @@
 
 namespace emei {
 
-enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS };
+enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN };
 
 // emei_set_obs_peers: the gathered buffers the staged rollout kernel also writes every observation row to
 struct ObsPeers {
@@ -48,6 +48,12 @@ struct PendLaunch {
     uint32_t* host_flag = nullptr;
     uint32_t flag_value = 0;
     ObsPeers peers;  // PEND_OP_ROLLOUT: count > 0 -> the staged peers kernel or EMEI_ERR_UNSUPPORTED
+    // PEND_OP_PLAN (emei_evaluate_sequences): n_candidates per env, n_steps = the horizon, obs_out = final_obs [n * K, 4] or null
+    const double* start_rows = nullptr;  // [n, 4] float64; null = the handle's state
+    int32_t n_candidates = 1;
+    double discount = 1.0;
+    double* return_out = nullptr;   // [n * K]
+    int32_t* length_out = nullptr;  // [n * K]
 };
 
 // pendulum_kernels.hip

@@ -594,6 +594,73 @@ __global__ void __launch_bounds__(kBlock)
     store_row4(next_obs, i, o);
 }
 
+// emei_evaluate_sequences (core.py:18-37,190-193: the model a planner queries): lane j scores candidate (i = j / K, k = j % K)
+// of env i — `horizon` steps of actions [t, j] from env i's start state with the arithmetic of pend_rollout_kernel, the state
+// in registers throughout.  ret = sum_{t < L} discount^t * (double)(float)r_t in step order (the float32 reward the rollout
+// stores), L = the first terminal step + 1 (else horizon); final_obs = the float32 observation of step L - 1.  A lane keeps
+// stepping after its terminal step without accumulating (as a rollout without auto-reset would); the wave leaves the loop
+// once a ballot finds none of its lanes live.  Per candidate the kernel writes 12 B (16 more with final_obs), per step it
+// reads one action.
+template <class Env, typename ActT>
+__global__ void __launch_bounds__(kBlock)
+    pend_plan_kernel(const typename Env::real* state, const double* start_rows, const ActT* actions, int64_t n_envs, int32_t n_cand,
+                     int32_t horizon, double discount, int freq_rate, typename Env::Params p, const SinCosEntry* trig,
+                     double* ret_out, int32_t* len_out, float4* final_obs) {
+    using R = typename Env::real;
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table(trig_s, trig, Env::trig_rot_c(), Env::trig_rot_s());
+    const int64_t nk = n_envs * n_cand;
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= nk) return;
+    const int64_t i = j / n_cand;
+    R s[4];
+    // start state: the handle's SoA, or the caller's float64 rows narrowed as emei_set_state narrows them (util_kernels.hip)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = start_rows ? (R)start_rows[i * 4 + k] : state[k * n_envs + i];
+    typename Env::Carry c;
+    trig_ctx_init(c.trig, trig_s);
+    Env::prime(s, c, p);
+
+    double ret = 0.0, g = 1.0;
+    int32_t len = horizon;
+    bool live = true;
+    float4 fo = make_float4(0.f, 0.f, 0.f, 0.f);
+    // actions a chunk ahead of their use, as in pend_rollout_kernel (steps past the horizon clamped, not branched around)
+    constexpr int kChunk = 8;
+    const int last = horizon - 1;
+    ActT cur[kChunk], nxt[kChunk];
+#pragma unroll
+    for (int u = 0; u < kChunk; ++u) cur[u] = (actions + (int64_t)min(u, last) * nk)[j];
+    bool any_live = true;
+    for (int t0 = 0; t0 < horizon && any_live; t0 += kChunk) {
+#pragma unroll
+        for (int u = 0; u < kChunk; ++u) nxt[u] = (actions + (int64_t)min(t0 + kChunk + u, last) * nk)[j];
+#pragma unroll
+        for (int u = 0; u < kChunk; ++u) {
+            const int t = t0 + u;
+            if (t >= horizon) break;
+            R o[4], rew;
+            bool term;
+            Env::step(s, c, Env::decode_t(cur[u]), p, freq_rate, o, rew, term);
+            if (live) {
+                ret = ret + g * (double)(float)rew;
+                g = g * discount;
+                fo = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
+                if (term) live = false, len = t + 1;
+            }
+            if (__ballot(live) == 0ull) {  // wave-uniform
+                any_live = false;
+                break;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kChunk; ++u) cur[u] = nxt[u];
+    }
+    ret_out[j] = ret;
+    len_out[j] = len;
+    if (final_obs) final_obs[j] = fo;
+}
+
 // ---------------------------------------------------------------------------------------------
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
@@ -748,6 +815,32 @@ static int launch_env(const PendLaunch& L) {
                 hipLaunchKernelGGL((pend_next_obs_kernel<Env, float>), grid, dim3(kBlock), 0, L.stream, (const float*)L.obs_in,
                                    L.actions, L.action_dtype, (float*)L.obs_out, L.n, L.freq_rate, a.p, a.trig);
             break;
+        case PEND_OP_PLAN: {
+            // one lane per candidate; n * n_candidates < 2^31 (checked in abi.hip)
+            const dim3 pgrid((unsigned)((L.n * L.n_candidates + kBlock - 1) / kBlock));
+            const R* st = (const R*)L.state;
+            if constexpr (Env::kDiscrete) {
+                if (L.action_dtype == EMEI_ACT_U8)
+                    hipLaunchKernelGGL((pend_plan_kernel<Env, uint8_t>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
+                                       (const uint8_t*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p,
+                                       a.trig, L.return_out, L.length_out, (float4*)L.obs_out);
+                else if (L.action_dtype == EMEI_ACT_I32)
+                    hipLaunchKernelGGL((pend_plan_kernel<Env, int32_t>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
+                                       (const int32_t*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p,
+                                       a.trig, L.return_out, L.length_out, (float4*)L.obs_out);
+                else if (L.action_dtype == EMEI_ACT_I64)
+                    hipLaunchKernelGGL((pend_plan_kernel<Env, int64_t>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
+                                       (const int64_t*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p,
+                                       a.trig, L.return_out, L.length_out, (float4*)L.obs_out);
+                else return EMEI_ERR_INVALID;
+            } else {
+                if (L.action_dtype != EMEI_ACT_F32) return EMEI_ERR_INVALID;
+                hipLaunchKernelGGL((pend_plan_kernel<Env, float>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
+                                   (const float*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p, a.trig,
+                                   L.return_out, L.length_out, (float4*)L.obs_out);
+            }
+            break;
+        }
         default: return EMEI_ERR_INVALID;
     }
     return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;

@@ -209,13 +209,17 @@ class Engine:
 
     # -- hot path ------------------------------------------------------------------------------
     def _check_actions(self, actions, lead):
+        return self._check_actions_n(actions, lead, self.n_envs)
+
+    def _check_actions_n(self, actions, lead, n):
+        """actions must be lead + [n(, act_dim)], contiguous, on the engine's device -> enum emei_action_dtype"""
         if not isinstance(actions, torch.Tensor) or actions.device != self.device:
             raise ValueError("actions must be a tensor on the engine's device")
         if actions.dtype not in _ACT_DTYPES:
             raise ValueError(f"unsupported action dtype {actions.dtype}")
-        want = lead + ((self.n_envs,) if self.act_dim <= 1 else (self.n_envs, self.act_dim))
+        want = lead + ((n,) if self.act_dim <= 1 else (n, self.act_dim))
         shape = tuple(actions.shape)
-        if shape != want and not (self.act_dim == 1 and shape == lead + (self.n_envs, 1)):
+        if shape != want and not (self.act_dim == 1 and shape == lead + (n, 1)):
             raise ValueError(f"actions shape {shape} != {want}")
         if not actions.is_contiguous():
             raise ValueError("actions must be contiguous")
@@ -293,6 +297,36 @@ class Engine:
         L.check(L.lib().emei_rollout(self._h, T, _ptr(actions), dt, _ptr(obs), _ptr(rew), _ptr(done),
                                      L.FLAG_AUTO_RESET if auto_reset else 0, _stream()))
         return obs, rew, done
+
+    @_on_device
+    def evaluate_sequences(self, actions, discount=1.0, start_state=None, final_obs=False):
+        """Score K candidate action sequences per env from the current state (or `start_state`) in one launch, for planners
+        (emei_evaluate_sequences).  The handle's state, counters and snapshot are left as they are.
+        actions [H, N, K(, act_dim)] on the engine's device; start_state None or [N, state_dim] (float64 rows of set_state).
+        -> (returns float64 [N, K]: sum of discount^t * reward_t up to the first terminal step, included; lengths int32 [N, K]:
+        that step + 1, or H; [final_obs float32 [N, K, obs_dim]: the observation of the last counted step])"""
+        if not isinstance(actions, torch.Tensor) or actions.dim() < 3:
+            raise ValueError("actions must be a tensor [H, N, K(, act_dim)] on the engine's device")
+        H, K = int(actions.shape[0]), int(actions.shape[2])
+        if actions.shape[1] != self.n_envs:
+            raise ValueError(f"actions shape {tuple(actions.shape)}: dimension 1 must be n_envs={self.n_envs}")
+        if not actions.is_contiguous():
+            raise ValueError("actions must be contiguous")
+        # [H, N, K(, act_dim)] is the rollout layout [H, N * K(, act_dim)] of N * K envs
+        flat = actions.view((H, self.n_envs * K) + tuple(actions.shape[3:]))
+        dt = self._check_actions_n(flat, (H,), self.n_envs * K)
+        st = None
+        if start_state is not None:
+            st = torch.as_tensor(start_state, device=self.device)
+            if st.dtype != torch.float64 or tuple(st.shape) != (self.n_envs, self.state_dim) or not st.is_contiguous():
+                raise ValueError(f"start_state must be a contiguous float64 tensor {(self.n_envs, self.state_dim)} on {self.device}; "
+                                 f"got {st.dtype} {tuple(st.shape)}")
+        ret = torch.empty((self.n_envs, K), dtype=torch.float64, device=self.device)
+        length = torch.empty((self.n_envs, K), dtype=torch.int32, device=self.device)
+        fo = torch.empty((self.n_envs, K, self.obs_dim), dtype=torch.float32, device=self.device) if final_obs else None
+        L.check(L.lib().emei_evaluate_sequences(self._h, H, K, _ptr(flat), dt, float(discount), _ptr(st), _ptr(ret), _ptr(length),
+                                                _ptr(fo), _stream()))
+        return (ret, length, fo) if final_obs else (ret, length)
 
     @_on_device
     def capture_step_graph(self, actions, auto_reset=False):

@@ -266,6 +266,33 @@ class HipEnv(EmeiEnv):
     def get_batch_init_state(self, batch_size):
         return self._host_init_state(batch_size)
 
+    def evaluate_action_sequences(self, actions, discount=1.0, start_state=None, final_obs=False):
+        """The query a planner asks of the true dynamics (random shooting, CEM, MPPI; core.py:18-37,190-193 serve model-based
+        callers with freeze() and get_batch_next_obs): K candidate action sequences per env scored from the envs' current
+        states, or from `start_state` rows [num_envs, state_dim] float64, in one launch (Engine.evaluate_sequences).
+        actions [H, num_envs, K(, act_dim)] -> (returns float64 [num_envs, K], lengths int32 [num_envs, K][, final_obs float32
+        [num_envs, K, obs_dim]]): the discounted sum of rewards up to the first terminal step (included), that step + 1 (or H),
+        the observation of that step.  No observation noise, TimeLimit or auto-reset; the env's state is left as it is.
+        NumPy input gives NumPy arrays, tensors give tensors."""
+        import torch
+
+        assert self.state is not None, "Call reset before using step method."  # base_control.py:67
+        eng = self.engine
+        a = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions))
+        a = a.to(eng.device)
+        if eng.act_dim == 0 and a.dtype not in (torch.uint8, torch.int32, torch.int64):
+            a = a.to(torch.int64)
+        if eng.act_dim > 0:
+            a = a.to(torch.float32)
+        st = None
+        if start_state is not None:
+            st = start_state if isinstance(start_state, torch.Tensor) else torch.as_tensor(np.asarray(start_state))
+            st = st.to(device=eng.device, dtype=torch.float64).contiguous()
+        out = eng.evaluate_sequences(a.contiguous(), discount=discount, start_state=st, final_obs=final_obs)
+        if isinstance(actions, torch.Tensor):
+            return out
+        return tuple(t.cpu().numpy() for t in out)
+
 
 def joint_sigmas(params, nq):
     """init_noise_params / obs_noise_params -> (pos sigma [nq], vel sigma [nq]) per (1-dof) joint:

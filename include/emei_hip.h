@@ -33,8 +33,9 @@ extern "C" {
  * 6: emei_config.ode_method (classic control's ODE_approximation(method="rk4"), opt-in) and emei_config.rollout_chunk_steps
  *    (struct_size 408; a 400-byte caller gets euler / automatic), emei_get_rollout_faults, EMEI_NEXT_OBS_ODE_RK4.
  * 7: emei_set_obs_peers + emei_peer_buffer_create / open / close / destroy (multi-GPU observation return by peer writes from the
- *    rollout kernel), EMEI_KERNEL_PEND_STAGED_PEERS_FREQ1 / EMEI_KERNEL_PEND_STAGED_PEERS. */
-#define EMEI_ABI_VERSION 7
+ *    rollout kernel), EMEI_KERNEL_PEND_STAGED_PEERS_FREQ1 / EMEI_KERNEL_PEND_STAGED_PEERS.
+ * 8: emei_evaluate_sequences (K candidate action sequences per env scored from the current or a given state in one launch). */
+#define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
 #define EMEI_API __attribute__((visibility("default")))
@@ -285,6 +286,26 @@ EMEI_API int emei_step_host(emei_env* h, const void* actions_host, int action_dt
  * Results are identical to n_steps calls of emei_step. */
 EMEI_API int emei_rollout(emei_env* h, int32_t n_steps, const void* actions, int action_dtype, float* obs_out,
                  float* reward_out, uint8_t* done_out, uint32_t flags, void* stream);
+
+/* Candidate action sequences scored from the envs' current states, for planners (random shooting, CEM, MPPI, or the true
+ * dynamics as an "oracle model"): the query EmeiEnv serves model-based callers with freeze() "for rollout-test or query" and
+ * get_batch_next_obs (core.py:18-37,190-193), fused — one launch, the state in registers, nothing per step written out.
+ * Candidate (i, k), i < n_envs, k < n_candidates, starts from env i's start state: the handle's current state (start_state NULL)
+ * or row i of start_state [n_envs, state_dim] float64 in emei_set_state's layout.  For t = 0 .. horizon - 1 it applies
+ * actions[t, i, k] — [horizon, n_envs, n_candidates] (discrete) or [horizon, n_envs, n_candidates, act_dim] float32, dtype per
+ * action_dtype as emei_rollout takes it — with exactly the arithmetic emei_rollout runs for this handle.  Outputs, [n_envs,
+ * n_candidates] each:
+ *   return_out    sum over t < L of discount^t * r_t: r_t is the step's reward as the rollout stores it (float32), widened; the
+ *                 sum is accumulated in float64 in step order, discount^t a float64 running product from 1.0
+ *   length_out    L = index of the first step whose terminal bit is set + 1, or horizon (the terminal step's reward counts)
+ *   final_obs_out [n_envs, n_candidates, obs_dim] float32: the observation of step L - 1 as the rollout emits it (NULL: skipped)
+ * No observation noise; TimeLimit counters, truncation and auto-reset are not consulted.  The handle is not touched (state,
+ * counters, reset key, frozen snapshot); freeze() is not required.  horizon >= 1, n_candidates >= 1, 0 < discount <= 1 and
+ * n_envs * n_candidates < 2^31, else EMEI_ERR_INVALID.  Newton solves that end at the iteration cap count into
+ * emei_get_solver_cap_hits.  Neither allocates nor synchronises (capturable). */
+EMEI_API int emei_evaluate_sequences(emei_env* h, int32_t horizon, int32_t n_candidates, const void* actions, int action_dtype,
+                                     double discount, const double* start_state, double* return_out, int32_t* length_out,
+                                     float* final_obs_out, void* stream);
 
 /* Which kernel the LAST emei_step / emei_rollout of this handle launched (enum emei_kernel_id): a debug /
  * test getter, so that a parity test can assert that the path it checked is the path bench.py times. */
