@@ -3,7 +3,9 @@
 The oracle is the composition the call replaces: a handle of N * K envs holding the start states tiled K times runs
 emei_rollout with the same actions, and NumPy recomputes the contract from its float32 rewards, terminal bits and observations
 (ret = sum_{t < L} discount^t * r_t in float64 step order, L = first terminal step + 1 or H, final_obs = the observation of step
-L - 1).  The fused call must give the same bits."""
+L - 1).  The fused call must give the same bits.  The contract itself is held to the CPU oracle in
+tests/test_gpu_plan_oracle.py; the edges of it at the end of this file (action dtypes, terminal steps around the action
+prefetch chunk, configured handles, odd start rows, three-block cheetah lanes) mostly use the composition too."""
 import numpy as np
 import pytest
 
@@ -248,3 +250,167 @@ def test_capture_replays_the_same_result():
     torch.cuda.synchronize()
     for x, y in zip(got, want):
         assert torch.equal(x, y)
+
+
+# ------------------------------------------------------------------------------------------------ contract edges
+import plan_reference as P  # noqa: E402  (host-made inputs shared with the oracle tests)
+
+
+def _plan(eng, acts, gamma, **kw):
+    return tuple(x.cpu().numpy() for x in eng.evaluate_sequences(acts, discount=gamma, final_obs=True, **kw))
+
+
+@pytest.mark.parametrize("H", [7, 8, 9, 17])
+@pytest.mark.parametrize("name", ["CartPoleSwingUp", "CartPoleBalancing"])
+def test_integer_action_dtypes_agree(name, H):
+    """pend_plan_kernel<Env, uint8_t / int32_t / int64_t> are three instantiations whose 8-step action prefetch strides 1, 4 and
+    8 bytes: the same sequences in each dtype, horizons around the prefetch chunk, give the same bits and those of the rollout
+    composition."""
+    N, K, gamma = 37, 7, 0.97
+    s0, a8 = P.cartpole_inputs(name, N, K, H, seed=40 + H, spread=0.12)
+    eng = _engine(name, N)
+    eng.set_state(s0)
+    dev = torch.as_tensor(a8, device=eng.device)
+    outs = {dt: eng.evaluate_sequences(dev.to(dt), discount=gamma, final_obs=True) for dt in (torch.uint8, torch.int32, torch.int64)}
+    for dt in (torch.int32, torch.int64):
+        for x, y in zip(outs[dt], outs[torch.uint8]):
+            assert torch.equal(x, y), dt
+    e_ret, e_L, e_fo = _compose(name, s0, dev, gamma)
+    ret, L, fo = (x.cpu().numpy() for x in outs[torch.int32])
+    assert np.array_equal(L, e_L) and np.array_equal(ret, e_ret) and np.array_equal(fo, e_fo)
+    if name == "CartPoleBalancing" and H == 17:
+        assert (e_L < H).any() and (e_L == H).any()
+
+
+def _edge_lengths(H):
+    return {v for v in (7, 8, 9, H - 1, H) if v <= H}
+
+
+@pytest.mark.parametrize("H", [8, 9, 16, 17])
+@pytest.mark.parametrize("name,spread", [("CartPoleBalancing", 0.12), ("ReboundInvertedDoublePendulumBalancing", 0.04)])
+def test_terminal_steps_at_the_prefetch_chunk_edges(name, spread, H):
+    """Terminal steps on both sides of the 8-step action chunk of pend_plan_kernel and at the end of the horizon, and the same
+    steps in body_plan_kernel (whose lanes store their results at their last counted step): start rows spread so that the
+    EXPECTED lengths — the rollout composition's — include 7, 8, 9, H - 1 and H."""
+    N, K, gamma = 37, 7, 0.95
+    build = P.cartpole_inputs if name.startswith("CartPole") else P.pendulum_inputs
+    s0, acts = build(name, N, K, 17, seed=2, spread=spread)
+    eng = _engine(name, N)
+    eng.set_state(s0)
+    dev = torch.as_tensor(acts[:H], device=eng.device).contiguous()
+    e_ret, e_L, e_fo = _compose(name, s0, dev, gamma)
+    assert _edge_lengths(H) <= set(e_L.ravel().tolist()), sorted(set(e_L.ravel().tolist()))
+    ret, L, fo = _plan(eng, dev, gamma)
+    assert np.array_equal(L, e_L) and np.array_equal(ret, e_ret) and np.array_equal(fo, e_fo)
+    assert eng.solver_cap_hits() == 0
+
+
+@pytest.mark.parametrize("name,kw,noise", [
+    ("HopperRunning", dict(freq_rate=MUJOCO["fr"], real_time_scale=MUJOCO["dt"], integrator="rk4"), True),
+    # an InvertedPendulum with observation noise steps as a body (ipend_model.h), a plain euler one on the staged 4-state kernel,
+    # and those two agree to 1e-6, not bit for bit (test_gpu_integrators.py:71): rk4 keeps both handles on the same kernel
+    ("ReboundInvertedPendulumBalancing", dict(integrator="rk4"), True),
+    ("CartPoleBalancing", dict(), False),  # classic control has no observation noise: TimeLimit and auto-reset only
+])
+def test_configured_handle_equals_plain_handle(name, kw, noise):
+    """emei_hip.h: "No observation noise; TimeLimit counters, truncation and auto-reset are not consulted".  A handle configured
+    with observation noise, reset noise, a TimeLimit shorter than the horizon, whose counters an auto-reset rollout has advanced
+    past several truncations, gives the bits of a plain handle holding the same state."""
+    N, K, H, mes, gamma = 37, 7, 16, 5, 0.95
+    fam = P.FAMILY[name][0]
+    s0, acts = P.BUILDERS[fam](name, N, K, H, seed=23)
+    cfg = dict(kw, max_episode_steps=mes, seed=6)
+    if noise:
+        cfg.update(obs_noise=0.05, init_noise=0.01)
+    a, b = _engine(name, N, **cfg), _engine(name, N, **kw)
+    a.reset(seed=6)
+    _, _, done = a.rollout(torch.as_tensor(acts[:, :, 0], device=a.device).contiguous(), auto_reset=True)
+    assert bool((done & 2).any())  # truncations happened: the TimeLimit is live on this handle
+    a.set_state(s0, reset_counters=False)
+    assert int(a.get_counters()[0].max()) > 0 and int(a.get_counters()[1].max()) > 0
+    b.set_state(s0)
+    dev = torch.as_tensor(acts, device=a.device)
+    got, want = a.evaluate_sequences(dev, gamma, final_obs=True), b.evaluate_sequences(dev, gamma, final_obs=True)
+    for x, y in zip(got, want):
+        assert torch.equal(x, y)
+    assert int(want[1].max()) > mes
+    # ... and from start_state rows, with the handle's own state elsewhere
+    a.reset(seed=7)
+    given = a.evaluate_sequences(dev, gamma, start_state=torch.as_tensor(s0, device=a.device), final_obs=True)
+    for x, y in zip(given, want):
+        assert torch.equal(x, y)
+
+
+def _odd_rows(name, rng, N):
+    """ordinary rows with NaN, +-inf, beyond-threshold and on-threshold rows at scattered places of the first wave(s)"""
+    fam, variant = P.FAMILY[name]
+    s0, _ = P.BUILDERS[fam](name, N, 1, 1, seed=int(rng.integers(1 << 30)))
+    ix, ith = (0, 2) if fam == "cartpole" else (0, 1)  # (x, theta) in the state row
+    # cartpole.py: Balancing ends at |x| >= 2.4 or |theta| >= 12 degrees, SwingUp at |x| >= 5 (its theta rows: large angles);
+    # inverted_pendulum.py: the rail at |x| = 2 and cos(theta) = 0.9
+    x_thr, th_thr = {"balancing": (2.4, 12 * 2 * np.pi / 360), "swingup": (5.0, 4 * np.pi)}[variant] if fam == "cartpole" \
+        else (2.0, float(np.arccos(0.9)))
+    odd = {}
+    for n, (col, val) in enumerate([(ix, np.nan), (ith, np.nan), (3, np.nan), (ix, np.inf), (ix, -np.inf), (ith, np.inf), (3, -np.inf),
+                                    (ix, 1.5 * x_thr), (ix, -1.5 * x_thr), (ith, 2 * th_thr), (ith, -2 * th_thr), (ix, x_thr),
+                                    (ix, -x_thr), (ith, th_thr), (ith, -th_thr)]):
+        odd[2 + 4 * n] = (col, val)  # rows 2, 6, ..., 58: K = 3 candidates each, ordinary rows between them in the same wave
+    rows = s0.copy()
+    for r, (col, val) in odd.items():
+        rows[r, col] = val
+    return s0, rows, np.array(sorted(odd))
+
+
+@pytest.mark.parametrize("name", ["CartPoleBalancing", "CartPoleSwingUp", "BoundaryInvertedPendulumBalancing"])
+def test_odd_start_rows(name):
+    """start_state rows that are NaN, +-inf, already beyond a terminal threshold or exactly on it, mixed with ordinary rows inside
+    one wave: every candidate equals the rollout composition (NaN where it has NaN), and the ordinary rows' candidates have the
+    bits of a launch without the odd neighbours."""
+    N, K, H, gamma = 70, 3, 12, 0.95
+    rng = np.random.default_rng(5)
+    plain, rows, odd = _odd_rows(name, rng, N)
+    eng = _engine(name, N)
+    eng.reset(seed=1)  # the handle's own state is not what is scored
+    acts = _actions(eng, H, N, K, seed=4)
+    ret, L, fo = _plan(eng, acts, gamma, start_state=torch.as_tensor(rows, device=eng.device))
+    with np.errstate(all="ignore"):
+        e_ret, e_L, e_fo = _compose(name, rows, acts, gamma)
+    assert np.array_equal(L, e_L)
+    assert np.array_equal(ret, e_ret, equal_nan=True) and np.array_equal(fo, e_fo, equal_nan=True)
+    assert np.isnan(fo[odd[:3]]).any(axis=(1, 2)).all()  # the NaN rows did reach the kernel
+    ret0, L0, fo0 = _plan(eng, acts, gamma, start_state=torch.as_tensor(plain, device=eng.device))
+    keep = np.setdiff1d(np.arange(N), odd)
+    assert np.array_equal(ret[keep], ret0[keep]) and np.array_equal(L[keep], L0[keep]) and np.array_equal(fo[keep], fo0[keep])
+    assert np.isfinite(ret0).all()
+
+
+def test_three_block_cheetah_lanes_vs_oracle():
+    """Cheetah lanes with exactly three constraint blocks (cheetah_model.h: `donor`) in a plan launch: states drawn as
+    test_gpu_cheetah.py:test_lanes_with_three_row_blocks_vs_oracle draws them, K = 3 candidates each over H = 2 env-steps, against
+    the oracle and the contract with the bounds of test_gpu_plan_oracle.py.  The call returns no float64 state to hold to 1e-9:
+    ret is a float64 sum of float32 rewards."""
+    from oracle import oracle as O
+
+    rng = np.random.default_rng(31)
+    q = rng.normal(0, 0.15, (30000, 9))
+    q[:, 1] = rng.uniform(-0.45, 0.1, len(q))  # low: several points on the floor
+    q[:, 2] = rng.normal(0, 0.4, len(q))
+    q[: len(q) // 4, 3:] = rng.uniform(-1.3, 1.3, (len(q) // 4, 6))
+    pool = np.concatenate([q, rng.normal(0, 1.5, q.shape)], axis=1)
+    nb = np.array([bin(int(m)).count("1") for m in O.planar_row_mask("cheetah", pool)])
+    pick = np.concatenate([np.nonzero(nb == 3)[0][:300], np.nonzero(nb >= 4)[0][:80], np.nonzero(nb <= 2)[0][:263]])
+    assert (nb[pick] == 3).sum() == 300 and (nb[pick] >= 4).sum() == 80
+    s0 = pool[rng.permutation(pick)]
+    N, K, H, gamma = len(s0), 3, 2, 0.97
+    kw = dict(freq_rate=2, real_time_scale=0.002)
+    acts = rng.uniform(-1.2, 1.2, (H, N, K, 6)).astype(np.float32)
+    obs, rew, term = P.oracle_steps("HalfCheetahRunning", kw, np.repeat(s0, K, axis=0), acts.reshape(H, N * K, 6))
+    w_ret, w_L, w_fo = P.contract(obs, rew, term, gamma)
+    eng = _engine("HalfCheetahRunning", N, **kw)
+    eng.set_state(s0)
+    ret, L, fo = _plan(eng, torch.as_tensor(acts, device=eng.device), gamma)
+    assert np.array_equal(L.ravel(), w_L) and (w_L == H).all()
+    ratio = np.abs(ret.ravel() - w_ret) / P.ret_bound(rew, w_L, gamma, P.TOL_R["cheetah"])
+    assert ratio.max() <= 1.0, ratio.max()
+    assert rel_err(fo.reshape(N * K, -1), w_fo) <= P.TOL_OBS
+    assert eng.solver_cap_hits() == 0
