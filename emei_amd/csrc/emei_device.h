@@ -254,7 +254,9 @@ __device__ __forceinline__ void sincos_r(T x, T& s, T& c) {
 // v_trig_preop_f64), so that the SAME table path serves every finite angle.  The device library's sincos() used to
 // repair such arguments after the fact; inlined, its ~160 instructions and 8 polynomial constants (16 VGPRs, hoisted
 // out of the rollout loop) sat in every kernel for a branch that no physical trajectory takes.  This reduction needs
-// five constants and returns an angle in [-4, 4] with an absolute error <= ~1e-15 (NaN for a non-finite argument).
+// five constants and returns an angle in [-4, 4], congruent to x modulo 2 pi within 1e-15 (NaN for a non-finite argument);
+// sin / cos of the table path behind it: <= 1.2e-15 absolute.  Both asserted for every binary exponent up to DBL_MAX by
+// tests/test_gpu_device_math.py.
 __device__ __forceinline__ void two_sum(double a, double b, double& s, double& e) {
     s = a + b;
     const double bb = s - a;
@@ -457,7 +459,7 @@ __device__ __forceinline__ void stage_trig_table(SinCosEntry* lds, const SinCosE
     __syncthreads();
 }
 
-// hardware reciprocal seed + Newton (emei_math.h)
+// hardware reciprocal seed + two Newton steps (emei_math.h): <= 2.3e-16 relative (tests/test_gpu_device_math.py)
 __device__ __forceinline__ double rcp_r(double d) { return refine_rcp(d, __builtin_amdgcn_rcp(d)); }
 __device__ __forceinline__ float rcp_r(float d) { return 1.0f / d; }
 
@@ -468,7 +470,9 @@ __device__ __forceinline__ double rcp1_r(double d) {
     return __builtin_fma(r0, __builtin_fma(-d, r0, 1.0), r0);
 }
 __device__ __forceinline__ float rcp1_r(float d) { return 1.0f / d; }
-// 1 / sqrt(x): hardware seed + two Newton steps (x = 0 -> +inf, as the seed)
+// 1 / sqrt(x): hardware seed + two Newton steps, < 1e-15 relative for normal x > 0.  x = 0: the seed is +inf and the Newton step
+// multiplies it by 0.5 * x = 0, so the float64 overload returns NaN (callers guard the degenerate case: hopper_model.h); the float32
+// overload returns +inf.  Both pinned by tests/test_gpu_device_math.py.
 __device__ __forceinline__ double rsqrt_r(double x) {
     double r = __builtin_amdgcn_rsq(x);
     const double hx = 0.5 * x;
@@ -491,7 +495,7 @@ __device__ __forceinline__ float fmax_r(float a, float b) { return __builtin_fma
 __device__ __forceinline__ double fma_r(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float fma_r(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 // n / d for O(1) denominators
-__device__ __forceinline__ double div_r(double n, double d) { return n * rcp_r(d); }  // <= ~2 ulp
+__device__ __forceinline__ double div_r(double n, double d) { return n * rcp_r(d); }  // <= 4.5e-16 relative
 __device__ __forceinline__ float div_r(float n, float d) { return n / d; }
 
 // Python / NumPy floored modulo a % p for p > 0 (np.remainder), without the library fmod loop:
@@ -510,6 +514,9 @@ __device__ __forceinline__ T pymod_pos(T a, T p, T inv_p) {
 // behind ONE wave-uniform test: w in [0, 2 pi) <=> |w - pi| <= pi, so the result of the usual case is tested itself (|o| >= pi:
 // the fix-up, and o = -pi exactly, which the cold path leaves alone) — 6 vector instructions instead of 9 per env-step of the
 // staged InvertedPendulum kernel, the same bits in every case (the cold path is pymod_pos's own sequence).
+// Domain: |theta| < 1e16 (float64) / 1e8 (float32), where the quotient estimate is at most one period off and the result is NumPy's
+// (theta + pi) % (2 pi) - pi bit for bit, inside [-pi, pi).  Beyond it k can miss by more than one period and the result leaves
+// [-pi, pi) (still equal to pymod_pos's, bit for bit); no physical trajectory gets there.
 template <typename T>
 __device__ __forceinline__ T wrap_pi(T theta, bool& finite) {  // finite: of the result (and so of theta); free in the usual case
     const T pi = T(3.141592653589793), p = T(2) * pi;
@@ -579,7 +586,8 @@ __device__ __forceinline__ float u01(uint32_t r) { return (float)(r >> 8) * 0x1.
 // exact inputs (v_sin_f32 / v_cos_f32 take turns; v_log_f32 is log2) are within 1.3e-7 abs (sin, cos) and 4.9e-7 abs
 // (radius) of the exact values over ALL 2^24 inputs — tools/bm_accuracy.hip; libm's logf / sqrtf / sincosf on the rounded
 // angle measured 4.2e-7 / 6.0e-7 — and cost 6 instructions instead of ~170 (sincosf alone brings its large-argument
-// reduction into every kernel that can reset an env).
+// reduction into every kernel that can reset an env).  tests/test_gpu_device_math.py asserts |z - exact| <= 1.6e-6 (= 4.9e-7 +
+// 5.77 (1.3e-7 + 6e-8), 5.77 the largest radius) over all 2^24 values of either field.
 __device__ __forceinline__ void boxmuller(uint32_t a, uint32_t b, float& z0, float& z1) {
     const float u1 = ((float)(a >> 8) + 1.0f) * 0x1.0p-24f;  // (0,1], exact
     const float t = (float)(b >> 8) * 0x1.0p-24f;            // [0,1) turns, exact

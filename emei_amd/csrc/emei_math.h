@@ -6,8 +6,9 @@
 // arithmetic (hundreds of instructions); the angles of this workload are bounded (a swinging pole,
 // |theta| < 1e6 rad), which allows a 2-constant Cody-Waite reduction with FMA and the classic
 // minimax kernels on [-pi/4, pi/4] (coefficients: Sun fdlibm k_sin.c/k_cos.c, public domain;
-// Cephes sinf/cosf for float).  Absolute error <= ~1.5e-16 (double) / ~6e-8 (float), i.e. the
-// same last-bit uncertainty as between any two libm implementations.
+// Cephes sinf/cosf for float).  Absolute error <= 2.0e-16 (double) / 1.0e-7 (float), i.e. the
+// same last-bit uncertainty as between any two libm implementations (asserted on the host by
+// tests/test_math_accuracy.py and on the device by tests/test_gpu_device_math.py).
 //
 // The header is plain C++ (no HIP types) so tests/host/math_accuracy.cpp can compile the very
 // same functions with g++ and compare them with long-double libm on the CPU.
@@ -100,7 +101,7 @@ EMEI_HD void fast_sincos(double x, double& s, double& c) {
 // (emei_trig_table, abi.hip) and staged in LDS by every kernel.  x = k*2pi/256 + r with |r| <= pi/256,
 // so sin r / cos r need 3 / 4 terms and no quadrant logic:
 //     sin x = S_k cos r + C_k sin r,    cos x = C_k cos r - S_k sin r.
-// 15 float64 operations + 3 integer ones instead of 37; absolute error <= ~2.3e-16.
+// 15 float64 operations + 3 integer ones instead of 37; absolute error <= 2.0e-16.
 struct SinCosEntry {
     double s, c;
 };
@@ -159,7 +160,7 @@ EMEI_HD void fast_sincosf(float x, float& s, float& c) {
     c = bits_to_f32(f32_to_bits(c0) ^ cflip);
 }
 
-// 1/d to ~1 ulp from a hardware seed `r0` (>= 20 good bits) by two Newton steps.
+// 1/d to <= 2.3e-16 relative from a hardware seed `r0` (>= 20 good bits) by two Newton steps.
 EMEI_HD double refine_rcp(double d, double r0) {
     double e = __builtin_fma(-d, r0, 1.0);
     double r = __builtin_fma(r0, e, r0);
@@ -167,7 +168,7 @@ EMEI_HD double refine_rcp(double d, double r0) {
     return __builtin_fma(r, e, r);
 }
 
-// n/d with a final residual correction (error <= ~1 ulp for normal operands, no scaling:
+// n/d with a final residual correction (error <= 2.3e-16 relative for normal operands, no scaling:
 // the denominators of this workload are O(1) by construction).
 EMEI_HD double div_via_rcp(double n, double d, double rcp) {
     double q = n * rcp;

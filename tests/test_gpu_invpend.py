@@ -213,6 +213,13 @@ def test_huge_and_nonfinite_angles():
     for name, variant in (("BoundaryInvertedPendulumSwingUp", "boundary_swingup"), ("ReboundInvertedPendulumSwingUp", "rebound_swingup")):
         eng = _engine(name, n, freq_rate=1, real_time_scale=0.02)
         eng.set_state(s0)
+        # the wrapped observation, inside wrap_pi's domain (emei_device.h: |theta| < 1e16): NumPy's floored modulo bit for bit (on
+        # the wrap point itself either representative, as in test_angle_wrap_at_its_boundaries); beyond it nothing is claimed
+        inside = np.abs(theta) < 1e16
+        assert 12 < inside.sum() < n
+        got, want = eng.get_obs().cpu().numpy()[inside, 1], (theta[inside] + np.pi) % (2 * np.pi) - np.pi
+        at_wrap = (np.abs(np.abs(got) - np.pi) < 1e-6) & (np.abs(np.abs(want) - np.pi) < 1e-6)
+        assert got.dtype == np.float64 and np.all((got == want) | at_wrap) and np.all((got >= -np.pi) & (got < np.pi))
         obs, rew, done = eng.step(torch.as_tensor(act, device=eng.device))
         o_st, o_obs, o_rew, o_term = O.ip_step(variant, s0, act.astype(np.float64), 1, 0.02)
         st = eng.get_state().cpu().numpy()
