@@ -738,6 +738,92 @@ extern "C" EMEI_API int emei_evaluate_sequences(emei_env* h, int32_t horizon, in
     return rc == EMEI_OK ? rc : fail(rc, "emei_evaluate_sequences: launch failed (%s)", hipGetErrorString(hipGetLastError()));
 }
 
+// ---------------------------------------------------------------------------------------------
+// emei_plan_shooting / emei_sample_candidates
+extern "C" EMEI_API int64_t emei_plan_shooting_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
+    if (n_envs < 1 || n_envs > INT32_MAX) return fail(EMEI_ERR_INVALID, "emei_plan_shooting_workspace_bytes: n_envs=%lld", (long long)n_envs);
+    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "emei_plan_shooting_workspace_bytes: n_candidates=%d < 1", n_candidates);
+    const int64_t nk = n_envs * (int64_t)n_candidates;
+    if (nk > INT32_MAX)
+        return fail(EMEI_ERR_INVALID, "emei_plan_shooting_workspace_bytes: n_envs * n_candidates = %lld exceeds 2^31 - 1", (long long)nk);
+    // one PlanPartial per (wave, env) segment of the plan kernel: at most waves + envs of them (emei_device.h:plan_reduce_wave)
+    return (int64_t)sizeof(PlanPartial) * ((nk + kWave - 1) / kWave + n_envs);
+}
+
+// the env's ctrlrange from the kernels' own model constants (the Python classes' action_space bounds)
+static void ctrl_range(int env_id, float& lo, float& hi) {
+    if (is_ip(env_id)) lo = (float)ip_make_model(false).ctrl_lo, hi = (float)ip_make_model(false).ctrl_hi;
+    else if (env_id == EMEI_HALFCHEETAH_RUNNING) lo = (float)cheetah::kCtrlLo, hi = (float)cheetah::kCtrlHi;
+    else if (env_id == EMEI_HOPPER_RUNNING) lo = (float)hopper::kCtrlLo, hi = (float)hopper::kCtrlHi;
+    else if (is_body(env_id)) lo = (float)dpend::kXml.ctrl_lo, hi = (float)dpend::kXml.ctrl_hi;
+    else lo = 0.f, hi = 1.f;  // discrete: unused
+}
+
+// the checks the two entry points share, in emei_evaluate_sequences' order: scalars, the handle, what needs the handle
+static int check_candidates(const char* fn, emei_env* h, int32_t horizon, int32_t n_candidates, const float* nominal, double sigma,
+                            int action_dtype, CandidateSpec& sp) {
+    if (horizon < 1) return fail(EMEI_ERR_INVALID, "%s: horizon=%d < 1", fn, horizon);
+    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "%s: n_candidates=%d < 1", fn, n_candidates);
+    if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
+    if (nominal && h->act_dim > 0 && !(std::isfinite(sigma) && sigma > 0.0))
+        return fail(EMEI_ERR_INVALID, "%s: sigma=%g with a nominal sequence must be finite and > 0", fn, sigma);
+    const int64_t nk = h->cfg.n_envs * (int64_t)n_candidates;
+    if (nk > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs * n_candidates = %lld exceeds 2^31 - 1", fn, (long long)nk);
+    if ((int64_t)horizon * (h->act_dim > 0 ? h->act_dim : 1) > INT32_MAX)  // 32-bit word index of the candidate's stream
+        return fail(EMEI_ERR_INVALID, "%s: horizon * act_dim exceeds 2^31 - 1", fn);
+    if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
+    sp.env_offset = h->cfg.env_index_offset, sp.nominal = nominal, sp.sigma = (float)sigma;
+    ctrl_range(h->cfg.env_id, sp.lo, sp.hi);
+    return EMEI_OK;
+}
+
+extern "C" EMEI_API int emei_sample_candidates(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal,
+                                               double sigma, void* actions_out, int action_dtype, void* stream) {
+    CandidateSpec sp{};
+    sp.seed = seed;
+    if (int rc = check_candidates("emei_sample_candidates", h, horizon, n_candidates, nominal, sigma, action_dtype, sp)) return rc;
+    if (!actions_out) return fail(EMEI_ERR_INVALID, "emei_sample_candidates: null argument");
+    EMEI_ON_DEVICE(h, "emei_sample_candidates");
+    const int rc = launch_sample_candidates(sp, h->cfg.n_envs, n_candidates, horizon, h->act_dim, actions_out, action_dtype, (hipStream_t)stream);
+    return rc == EMEI_OK ? rc : fail(rc, "emei_sample_candidates: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+}
+
+extern "C" EMEI_API int emei_plan_shooting(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal,
+                                           double sigma, double discount, const double* start_state, void* workspace,
+                                           void* best_action_out, int action_dtype, void* best_sequence_out, double* best_return_out,
+                                           int32_t* best_index_out, int32_t* best_length_out, void* stream) {
+    if (horizon < 1) return fail(EMEI_ERR_INVALID, "emei_plan_shooting: horizon=%d < 1", horizon);
+    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "emei_plan_shooting: n_candidates=%d < 1", n_candidates);
+    if (!(discount > 0.0 && discount <= 1.0)) return fail(EMEI_ERR_INVALID, "emei_plan_shooting: discount=%g is outside (0, 1]", discount);
+    CandidateSpec sp{};
+    sp.seed = seed;
+    if (int rc = check_candidates("emei_plan_shooting", h, horizon, n_candidates, nominal, sigma, action_dtype, sp)) return rc;
+    if (!workspace || !best_action_out || !best_return_out || !best_index_out)
+        return fail(EMEI_ERR_INVALID, "emei_plan_shooting: null argument");
+    EMEI_ON_DEVICE(h, "emei_plan_shooting");
+    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "emei_plan_shooting: call reset before using the state");
+    int rc;
+    if (!steps_as_body(h->cfg)) {  // the kernel family emei_rollout runs for this handle
+        PendLaunch L = pend_base(h, stream);
+        L.op = PEND_OP_PLAN;
+        L.action_dtype = action_dtype, L.n_steps = horizon;
+        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
+        L.cand = sp, L.partials = workspace;
+        rc = pend_launch(L);
+    } else {
+        BodyLaunch L = body_base(h, stream);
+        L.op = BODY_OP_PLAN;
+        L.n_steps = horizon;
+        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
+        L.cand = sp, L.partials = workspace;
+        rc = body_launch(L);
+    }
+    if (rc == EMEI_OK)
+        rc = launch_plan_finish(workspace, sp, h->cfg.n_envs, n_candidates, horizon, h->act_dim, best_action_out, action_dtype,
+                                best_sequence_out, best_return_out, best_index_out, best_length_out, (hipStream_t)stream);
+    return rc == EMEI_OK ? rc : fail(rc, "emei_plan_shooting: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+}
+
 extern "C" EMEI_API int emei_compact_done(emei_env* h, int32_t* idx_out, int32_t* count_out, void* stream) {
     if (!h || !idx_out || !count_out) return fail(EMEI_ERR_INVALID, "emei_compact_done: null argument");
     EMEI_ON_DEVICE(h, "emei_compact_done");

@@ -205,6 +205,9 @@ struct BodyLaunch {
     double discount = 1.0;
     double* return_out = nullptr;   // [n * K]
     int32_t* length_out = nullptr;  // [n * K]
+    // emei_plan_shooting (as PendLaunch): partials != null -> candidates drawn in the lanes, one PlanPartial per (wave, env) segment
+    CandidateSpec cand = {};
+    void* partials = nullptr;
 };
 int body_launch(const BodyLaunch& L);  // body_dispatch.hip
 
@@ -688,11 +691,15 @@ __global__ void __launch_bounds__(kBlock)
 // a wave keeps stepping until none is live — padding lanes parked as there, lanes past their terminal step without accumulating
 // — so that a wave-mate's state (the cheetah's constraint-slot lending, cheetah_model.h: `donor`) is what that rollout has.
 // A correctness path: actions are read per lane, not staged.
-template <class Body, bool RK4>
+// DRAWN (emei_plan_shooting): the controls are the lane's own draws (emei_device.h:draw_action; every step starts its word
+// stream afresh, so no generator state is held across a step) and the lane keeps (ret, len) for plan_reduce_wave instead of
+// storing them at its last counted step.  The step is the same code either way.
+template <class Body, bool RK4, bool DRAWN = false>
 __global__ void __launch_bounds__(kBlock)
     body_plan_kernel(const typename Body::real* state, const double* start_rows, const float* actions, int64_t n_envs,
                      int32_t n_cand, int32_t horizon, double discount, int freq_rate, int semi, typename Body::Model m,
-                     const SinCosEntry* trig_tab, unsigned long long* cap_hits, double* ret_out, int32_t* len_out, float* final_obs) {
+                     const SinCosEntry* trig_tab, unsigned long long* cap_hits, double* ret_out, int32_t* len_out, float* final_obs,
+                     CandidateSpec sp, PlanPartial* partials) {
     using R = typename Body::real;
     constexpr int NS = Body::NS, NO = Body::NO, NA = Body::NA;
     __shared__ SinCosEntry trig_s[kTrigTableSize];
@@ -721,11 +728,21 @@ __global__ void __launch_bounds__(kBlock)
 #pragma unroll
     for (int k = 0; k < NS; ++k) s[k] = active ? s[k] : parked[k];
     double ret = 0.0, g = 1.0;
+    int32_t len = 0;  // DRAWN: steps counted so far (ret and len stop changing with the lane's last counted step)
     bool live = active;
     for (int t = 0; t < horizon; ++t) {
         R ctrl[NA];  // padding lanes: zero, as the rollout's staging gives them
+        if constexpr (DRAWN) {
+            CandidateWords cw(sp.seed, sp.env_offset + (uint64_t)i, (uint32_t)((active ? j : 0) - i * n_cand));
 #pragma unroll
-        for (int k = 0; k < NA; ++k) ctrl[k] = active ? (R)actions[((int64_t)t * nk + j) * NA + k] : R(0);
+            for (int k = 0; k < NA; ++k) {
+                const float a = draw_action(cw, sp, n_envs, i, t, k, NA);
+                ctrl[k] = active ? (R)a : R(0);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < NA; ++k) ctrl[k] = active ? (R)actions[((int64_t)t * nk + j) * NA + k] : R(0);
+        }
         R pre[NS];
 #pragma unroll
         for (int k = 0; k < NS; ++k) pre[k] = s[k];
@@ -738,19 +755,23 @@ __global__ void __launch_bounds__(kBlock)
         if (live) {
             ret = ret + g * (double)(float)rew;
             g = g * discount;
+            if constexpr (DRAWN) len = t + 1;
             // a lane's results leave at its last counted step: no observation is held in registers across the loop
             if (term || t == horizon - 1) {
                 live = false;
-                ret_out[j] = ret;
-                len_out[j] = t + 1;
-                if (final_obs) {
+                if constexpr (!DRAWN) {
+                    ret_out[j] = ret;
+                    len_out[j] = t + 1;
+                    if (final_obs) {
 #pragma unroll
-                    for (int k = 0; k < NO; ++k) final_obs[j * NO + k] = o[k];
+                        for (int k = 0; k < NO; ++k) final_obs[j * NO + k] = o[k];
+                    }
                 }
             }
         }
         if (__ballot(live) == 0ull) break;  // wave-uniform
     }
+    if constexpr (DRAWN) plan_reduce_wave(j, nk, i, n_cand, ret, len, partials);
 }
 
 // every launch of one Body type (one translation unit instantiates exactly one Body: body_tu.hip)
@@ -896,14 +917,26 @@ static int launch_body(const BodyLaunch& L) {
             const dim3 pgrid((unsigned)((L.n * L.n_candidates + kBlock - 1) / kBlock));
             const int semi = (int)(L.integrator == EMEI_INTEG_SEMI_IMPLICIT);
             const SinCosEntry* tt = (const SinCosEntry*)L.trig;
+            PlanPartial* pp = (PlanPartial*)L.partials;
+            if (pp) {  // emei_plan_shooting
+                if (L.integrator == EMEI_INTEG_RK4)
+                    hipLaunchKernelGGL((body_plan_kernel<Body, true, true>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state,
+                                       L.start_rows, (const float*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, 0, m,
+                                       tt, L.cap_hits, (double*)nullptr, (int32_t*)nullptr, (float*)nullptr, L.cand, pp);
+                else
+                    hipLaunchKernelGGL((body_plan_kernel<Body, false, true>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state,
+                                       L.start_rows, (const float*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, semi,
+                                       m, tt, L.cap_hits, (double*)nullptr, (int32_t*)nullptr, (float*)nullptr, L.cand, pp);
+                break;
+            }
             if (L.integrator == EMEI_INTEG_RK4)
                 hipLaunchKernelGGL((body_plan_kernel<Body, true>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state, L.start_rows,
                                    (const float*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, 0, m, tt,
-                                   L.cap_hits, L.return_out, L.length_out, L.obs_out);
+                                   L.cap_hits, L.return_out, L.length_out, L.obs_out, L.cand, pp);
             else
                 hipLaunchKernelGGL((body_plan_kernel<Body, false>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state, L.start_rows,
                                    (const float*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, semi, m, tt,
-                                   L.cap_hits, L.return_out, L.length_out, L.obs_out);
+                                   L.cap_hits, L.return_out, L.length_out, L.obs_out, L.cand, pp);
             break;
         }
         default: return EMEI_ERR_INVALID;

@@ -597,6 +597,85 @@ __device__ __forceinline__ void boxmuller(uint32_t a, uint32_t b, float& z0, flo
 }
 
 // ---------------------------------------------------------------------------------------------
+// Candidate action sequences of emei_plan_shooting / emei_sample_candidates (the normative text: include/emei_hip.h).
+// Candidate (g, k) — g the GLOBAL env index, k the candidate — owns the word stream W[m] = philox4x32_10(seed, g, k, m >> 2).v[m & 3]:
+// k sits where the reset generator has the episode, `seed` is the call's own key.
+struct CandidateSpec {  // kernel argument
+    uint64_t seed, env_offset;
+    const float* nominal;  // null: Bernoulli(1/2) / uniform on the ctrlrange; else [horizon, n_envs(, act_dim)] probabilities / means
+    float sigma, lo, hi;   // continuous envs: sigma of the Gaussian mode, the ctrlrange
+};
+// (KEYS_IN_PLACE: as philox4x32_10's — for the 4-state plan kernels, whose float64 InvertedPendulum instantiations have no scalar
+// registers left for twenty precomputed round keys; the seed is a kernel argument there)
+template <bool KEYS_IN_PLACE = false>
+struct CandidateWordsT {  // W[] of one candidate, the last Philox block kept
+    uint64_t seed, g;
+    uint32_t k, blk;
+    u32x4 w;
+    __device__ __forceinline__ CandidateWordsT(uint64_t seed_, uint64_t g_, uint32_t k_) : seed(seed_), g(g_), k(k_), blk(~0u), w{} {}
+    __device__ __forceinline__ uint32_t word(uint32_t m) {
+        const uint32_t b = m >> 2, j = m & 3u;
+        if (b != blk) w = philox4x32_10<KEYS_IN_PLACE>(seed, g, k, b), blk = b;
+        return j == 0u ? w.v[0] : (j == 1u ? w.v[1] : (j == 2u ? w.v[2] : w.v[3]));
+    }
+};
+using CandidateWords = CandidateWordsT<false>;
+// THE draw: component a of step t of the candidate behind `cw`, env i of this shard.  na = the env's act_dim (0: discrete, the
+// value is 0.f or 1.f).  Used by the sampling kernel, by the plan kernels' step loops and by the kernel that rewrites the winner.
+template <class Words>
+__device__ __forceinline__ float draw_action(Words& cw, const CandidateSpec& sp, int64_t n_envs, int64_t i, int32_t t, int a, int na) {
+    if (na == 0) {
+        const float p = sp.nominal ? sp.nominal[(int64_t)t * n_envs + i] : 0.5f;
+        return u01(cw.word((uint32_t)t)) < p ? 1.f : 0.f;
+    }
+    const uint32_t c = (uint32_t)t * (uint32_t)na + (uint32_t)a;
+    if (!sp.nominal) return fmaf(u01(cw.word(c)), sp.hi - sp.lo, sp.lo);
+    const uint32_t q = c >> 1;  // the pair (W[2q], W[2q + 1]) lies inside one Philox block
+    float z0, z1;
+    const uint32_t wa = cw.word(2u * q), wb = cw.word(2u * q + 1u);
+    boxmuller(wa, wb, z0, z1);
+    const float mean = sp.nominal[((int64_t)t * n_envs + i) * na + a];
+    return fminf(fmaxf(fmaf(sp.sigma, (c & 1u) ? z1 : z0, mean), sp.lo), sp.hi);
+}
+__device__ __forceinline__ void store_action(void* p, int dtype, int64_t idx, float v) {
+    switch (dtype) {  // wave-uniform
+        case EMEI_ACT_U8: ((uint8_t*)p)[idx] = (uint8_t)v; break;
+        case EMEI_ACT_I32: ((int32_t*)p)[idx] = (int32_t)v; break;
+        case EMEI_ACT_I64: ((int64_t*)p)[idx] = (int64_t)v; break;
+        default: ((float*)p)[idx] = v;
+    }
+}
+
+// The planner's order (emei_hip.h): x beats y if x > y, or if y is NaN and x is not; between candidates neither of which beats
+// the other the lower k wins.  A strict total order on candidates with distinct k, so any reduction tree gives the same winner.
+struct PlanPartial {  // the best candidate of one (wave, env) segment: emei_plan_shooting's workspace holds n_waves + n_envs of them
+    double ret;
+    int32_t k, len;
+};
+__device__ __forceinline__ bool plan_beats(double x, double y) { return x > y || (y != y && x == x); }
+__device__ __forceinline__ bool plan_replaces(double ra, int32_t ka, double rb, int32_t kb) {  // does (rb, kb) replace (ra, ka)?
+    return plan_beats(rb, ra) || (!plan_beats(ra, rb) && kb < ka);
+}
+// End of a plan kernel: lane l of the wave holds candidate j = wave base + l, k = j % n_cand of env i = j / n_cand (lanes with
+// j >= nk hold nothing and may have left).  Segmented suffix reduction by env over the wave's lanes (log2(64) shuffle steps: at
+// step d lane l takes in lane l + d, which by then covers candidates j + d .. j + 2d - 1 of ITS env), then the first lane of every
+// (wave, env) segment writes slot wave + i: consecutive segments differ by one wave, one env or both, so the slot is unique, and
+// env i's segments are exactly the slots w + i of the waves w its K lanes lie on — nothing to initialise, no atomics.
+__device__ __forceinline__ void plan_reduce_wave(int64_t j, int64_t nk, int64_t i, int32_t n_cand, double ret, int32_t len, PlanPartial* partials) {
+    const int lane = (int)(threadIdx.x & (kWave - 1));
+    const int32_t k0 = (int32_t)(j - i * n_cand);
+    int32_t k = k0;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const double r2 = __shfl_down(ret, d, kWave);
+        const int32_t k2 = __shfl_down(k, d, kWave), l2 = __shfl_down(len, d, kWave);
+        const bool same_env = lane + d < kWave && j + d < nk && (int64_t)k0 + d < n_cand;
+        if (same_env && plan_replaces(ret, k, r2, k2)) ret = r2, k = k2, len = l2;
+    }
+    if (j < nk && (lane == 0 || k0 == 0)) partials[(j >> 6) + i] = PlanPartial{ret, k, len};
+}
+
+// ---------------------------------------------------------------------------------------------
 // action loads: dtype is wave-uniform, so the switch is a scalar branch
 __device__ __forceinline__ int load_discrete_action(const void* p, int dtype, int64_t idx) {
     switch (dtype) {

@@ -54,6 +54,10 @@ struct PendLaunch {
     double discount = 1.0;
     double* return_out = nullptr;   // [n * K]
     int32_t* length_out = nullptr;  // [n * K]
+    // emei_plan_shooting: partials != null -> the candidates are drawn in the lanes under `cand` and the kernel leaves one
+    // PlanPartial per (wave, env) segment instead of return_out / length_out
+    CandidateSpec cand = {};
+    void* partials = nullptr;
 };
 
 // pendulum_kernels.hip
@@ -66,5 +70,11 @@ const void* emei_trig_table(int device);
 int launch_state_unpack(const double* aos, void* soa, int precision, int64_t n, int dim, hipStream_t s);
 int launch_state_pack(const void* soa, double* aos, int precision, int64_t n, int dim, hipStream_t s);
 int launch_compact_done(const unsigned long long* masks, int64_t n, int32_t* idx_out, int32_t* count_out, hipStream_t s);
+// emei_sample_candidates / the second launch of emei_plan_shooting (act_dim 0: a discrete env)
+int launch_sample_candidates(const CandidateSpec& sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim, void* actions_out,
+                             int action_dtype, hipStream_t s);
+int launch_plan_finish(const void* partials, const CandidateSpec& sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim,
+                       void* best_action, int action_dtype, void* best_sequence, double* best_return, int32_t* best_index,
+                       int32_t* best_length, hipStream_t s);
 
 }  // namespace emei

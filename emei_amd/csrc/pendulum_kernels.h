@@ -8,6 +8,8 @@
 // and writes obs + reward + done (22 B/env-step with uint8 actions).
 // There is no dense contraction anywhere on this path, hence no MFMA: the roofline is HBM.
 #pragma once
+#include <type_traits>
+
 #include "pendulum_envs.h"
 #include "launch.h"
 
@@ -601,11 +603,15 @@ __global__ void __launch_bounds__(kBlock)
 // stepping after its terminal step without accumulating (as a rollout without auto-reset would); the wave leaves the loop
 // once a ballot finds none of its lanes live.  Per candidate the kernel writes 12 B (16 more with final_obs), per step it
 // reads one action.
-template <class Env, typename ActT>
+// DRAWN (emei_plan_shooting): the action source is the lane itself — candidate (env_offset + i, k)'s draws under `sp`
+// (emei_device.h:draw_action; ActT is then the drawn value's type, int or float, and `actions` unused), one Philox block per four
+// steps for the discrete envs instead of the prefetch — and instead of 12 B per candidate the wave leaves one PlanPartial per
+// (wave, env) segment (plan_reduce_wave).  The step loop is the same code either way.
+template <class Env, typename ActT, bool DRAWN = false>
 __global__ void __launch_bounds__(kBlock)
     pend_plan_kernel(const typename Env::real* state, const double* start_rows, const ActT* actions, int64_t n_envs, int32_t n_cand,
                      int32_t horizon, double discount, int freq_rate, typename Env::Params p, const SinCosEntry* trig,
-                     double* ret_out, int32_t* len_out, float4* final_obs) {
+                     double* ret_out, int32_t* len_out, float4* final_obs, CandidateSpec sp, PlanPartial* partials) {
     using R = typename Env::real;
     __shared__ SinCosEntry trig_s[kTrigTableSize];
     stage_trig_table(trig_s, trig, Env::trig_rot_c(), Env::trig_rot_s());
@@ -629,18 +635,24 @@ __global__ void __launch_bounds__(kBlock)
     constexpr int kChunk = 8;
     const int last = horizon - 1;
     ActT cur[kChunk], nxt[kChunk];
+    CandidateWordsT<true> cw(sp.seed, sp.env_offset + (uint64_t)i, (uint32_t)(j - i * n_cand));
+    if constexpr (!DRAWN) {
 #pragma unroll
-    for (int u = 0; u < kChunk; ++u) cur[u] = (actions + (int64_t)min(u, last) * nk)[j];
+        for (int u = 0; u < kChunk; ++u) cur[u] = (actions + (int64_t)min(u, last) * nk)[j];
+    }
     bool any_live = true;
     for (int t0 = 0; t0 < horizon && any_live; t0 += kChunk) {
+        if constexpr (!DRAWN) {
 #pragma unroll
-        for (int u = 0; u < kChunk; ++u) nxt[u] = (actions + (int64_t)min(t0 + kChunk + u, last) * nk)[j];
+            for (int u = 0; u < kChunk; ++u) nxt[u] = (actions + (int64_t)min(t0 + kChunk + u, last) * nk)[j];
+        }
 #pragma unroll
         for (int u = 0; u < kChunk; ++u) {
             const int t = t0 + u;
             if (t >= horizon) break;
             R o[4], rew;
             bool term;
+            if constexpr (DRAWN) cur[u] = (ActT)draw_action(cw, sp, n_envs, i, t, 0, Env::kDiscrete ? 0 : Env::kActDim);
             Env::step(s, c, Env::decode_t(cur[u]), p, freq_rate, o, rew, term);
             if (live) {
                 ret = ret + g * (double)(float)rew;
@@ -653,12 +665,18 @@ __global__ void __launch_bounds__(kBlock)
                 break;
             }
         }
+        if constexpr (!DRAWN) {
 #pragma unroll
-        for (int u = 0; u < kChunk; ++u) cur[u] = nxt[u];
+            for (int u = 0; u < kChunk; ++u) cur[u] = nxt[u];
+        }
     }
-    ret_out[j] = ret;
-    len_out[j] = len;
-    if (final_obs) final_obs[j] = fo;
+    if constexpr (DRAWN) {
+        plan_reduce_wave(j, nk, i, n_cand, ret, len, partials);
+    } else {
+        ret_out[j] = ret;
+        len_out[j] = len;
+        if (final_obs) final_obs[j] = fo;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -819,25 +837,33 @@ static int launch_env(const PendLaunch& L) {
             // one lane per candidate; n * n_candidates < 2^31 (checked in abi.hip)
             const dim3 pgrid((unsigned)((L.n * L.n_candidates + kBlock - 1) / kBlock));
             const R* st = (const R*)L.state;
+            if (L.partials) {  // emei_plan_shooting: candidates drawn in the lanes, one partial per (wave, env) segment
+                using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
+                hipLaunchKernelGGL((pend_plan_kernel<Env, DrawT, true>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
+                                   (const DrawT*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p, a.trig,
+                                   (double*)nullptr, (int32_t*)nullptr, (float4*)nullptr, L.cand, (PlanPartial*)L.partials);
+                break;
+            }
+            const CandidateSpec none{};
             if constexpr (Env::kDiscrete) {
                 if (L.action_dtype == EMEI_ACT_U8)
                     hipLaunchKernelGGL((pend_plan_kernel<Env, uint8_t>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
                                        (const uint8_t*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p,
-                                       a.trig, L.return_out, L.length_out, (float4*)L.obs_out);
+                                       a.trig, L.return_out, L.length_out, (float4*)L.obs_out, none, (PlanPartial*)nullptr);
                 else if (L.action_dtype == EMEI_ACT_I32)
                     hipLaunchKernelGGL((pend_plan_kernel<Env, int32_t>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
                                        (const int32_t*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p,
-                                       a.trig, L.return_out, L.length_out, (float4*)L.obs_out);
+                                       a.trig, L.return_out, L.length_out, (float4*)L.obs_out, none, (PlanPartial*)nullptr);
                 else if (L.action_dtype == EMEI_ACT_I64)
                     hipLaunchKernelGGL((pend_plan_kernel<Env, int64_t>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
                                        (const int64_t*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p,
-                                       a.trig, L.return_out, L.length_out, (float4*)L.obs_out);
+                                       a.trig, L.return_out, L.length_out, (float4*)L.obs_out, none, (PlanPartial*)nullptr);
                 else return EMEI_ERR_INVALID;
             } else {
                 if (L.action_dtype != EMEI_ACT_F32) return EMEI_ERR_INVALID;
                 hipLaunchKernelGGL((pend_plan_kernel<Env, float>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
                                    (const float*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p, a.trig,
-                                   L.return_out, L.length_out, (float4*)L.obs_out);
+                                   L.return_out, L.length_out, (float4*)L.obs_out, none, (PlanPartial*)nullptr);
             }
             break;
         }

@@ -98,4 +98,74 @@ int launch_compact_done(const unsigned long long* masks, int64_t n, int32_t* idx
     return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;
 }
 
+// ---------------------------------------------------------------------------------------------
+// emei_sample_candidates: lane j writes the sequence of candidate (i = j / K, k = j % K) — what the plan kernels draw in their
+// lanes (emei_device.h:draw_action) — step by step, the stores of a step contiguous over the lanes.
+__global__ void __launch_bounds__(kBlock)
+    sample_candidates_kernel(CandidateSpec sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim, void* out, int action_dtype) {
+    const int64_t nk = n_envs * n_cand;
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= nk) return;
+    const int64_t i = j / n_cand;
+    const int na = act_dim > 0 ? act_dim : 1;
+    CandidateWords cw(sp.seed, sp.env_offset + (uint64_t)i, (uint32_t)(j - i * n_cand));
+    for (int32_t t = 0; t < horizon; ++t)
+        for (int a = 0; a < na; ++a) store_action(out, action_dtype, ((int64_t)t * nk + j) * na + a, draw_action(cw, sp, n_envs, i, t, a, act_dim));
+}
+
+// Second launch of emei_plan_shooting, one wave per env: the best of the env's partials (slots w + i of the waves w its
+// candidates lay on; the order is total, so the lanes' strided pass and the butterfly give the first maximum), then candidate k*'s
+// sequence drawn again, the lanes striding over the steps.
+__global__ void __launch_bounds__(kBlock)
+    plan_finish_kernel(const PlanPartial* partials, CandidateSpec sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim,
+                       void* best_action, int action_dtype, void* best_sequence, double* best_return, int32_t* best_index,
+                       int32_t* best_length) {
+    const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / kWave;  // wave-uniform
+    const int lane = (int)(threadIdx.x & (kWave - 1));
+    if (i >= n_envs) return;
+    const int64_t w0 = (i * n_cand) / kWave, w1 = ((i + 1) * n_cand - 1) / kWave;
+    // (NaN, INT32_MAX) loses to every partial: k < n_cand <= 2^31 - 1
+    double ret = __builtin_nan("");
+    int32_t k = INT32_MAX, len = 0;
+    for (int64_t w = w0 + lane; w <= w1; w += kWave) {
+        const PlanPartial p = partials[w + i];
+        if (plan_replaces(ret, k, p.ret, p.k)) ret = p.ret, k = p.k, len = p.len;
+    }
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const double r2 = __shfl_xor(ret, d, kWave);
+        const int32_t k2 = __shfl_xor(k, d, kWave), l2 = __shfl_xor(len, d, kWave);
+        if (plan_replaces(ret, k, r2, k2)) ret = r2, k = k2, len = l2;
+    }
+    if (lane == 0) {
+        best_return[i] = ret;
+        best_index[i] = k;
+        if (best_length) best_length[i] = len;
+    }
+    const int na = act_dim > 0 ? act_dim : 1;
+    for (int32_t t = lane; t < horizon; t += kWave) {
+        CandidateWords cw(sp.seed, sp.env_offset + (uint64_t)i, (uint32_t)k);
+        for (int a = 0; a < na; ++a) {
+            const float v = draw_action(cw, sp, n_envs, i, t, a, act_dim);
+            if (best_sequence) store_action(best_sequence, action_dtype, ((int64_t)t * n_envs + i) * na + a, v);
+            if (t == 0) store_action(best_action, action_dtype, i * na + a, v);
+        }
+    }
+}
+
+int launch_sample_candidates(const CandidateSpec& sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim, void* actions_out,
+                             int action_dtype, hipStream_t s) {
+    dim3 grid((unsigned)((n_envs * n_cand + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(sample_candidates_kernel, grid, dim3(kBlock), 0, s, sp, n_envs, n_cand, horizon, act_dim, actions_out, action_dtype);
+    return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;
+}
+int launch_plan_finish(const void* partials, const CandidateSpec& sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim,
+                       void* best_action, int action_dtype, void* best_sequence, double* best_return, int32_t* best_index,
+                       int32_t* best_length, hipStream_t s) {
+    dim3 grid((unsigned)((n_envs + kBlock / kWave - 1) / (kBlock / kWave)));
+    hipLaunchKernelGGL(plan_finish_kernel, grid, dim3(kBlock), 0, s, (const PlanPartial*)partials, sp, n_envs, n_cand, horizon, act_dim,
+                       best_action, action_dtype, best_sequence, best_return, best_index, best_length);
+    return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;
+}
+
 }  // namespace emei

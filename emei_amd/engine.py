@@ -328,6 +328,72 @@ class Engine:
                                                 _ptr(fo), _stream()))
         return (ret, length, fo) if final_obs else (ret, length)
 
+    # -- random-shooting planning: candidates drawn and arg-maxed on the device (emei_plan_shooting) -------------
+    def _candidate_args(self, H, K, nominal, sigma, dtype):
+        """validated (nominal tensor or None, sigma, torch dtype) of sample_candidates / plan_shooting: the ABI takes raw pointers"""
+        H, K = int(H), int(K)
+        if H < 1 or K < 1:
+            raise ValueError(f"horizon={H} and n_candidates={K} must be >= 1")
+        if dtype is None:
+            dtype = torch.int64 if self.act_dim == 0 else torch.float32  # what step() takes by default
+        if dtype not in _ACT_DTYPES or (dtype == torch.float32) != (self.act_dim > 0):
+            raise ValueError(f"action dtype {dtype}: uint8 / int32 / int64 for the discrete envs, float32 for the continuous ones")
+        if nominal is not None:
+            want = (H, self.n_envs) if self.act_dim == 0 else (H, self.n_envs, self.act_dim)
+            if not isinstance(nominal, torch.Tensor) or nominal.device != self.device:
+                raise ValueError("nominal must be a tensor on the engine's device")
+            ok_shape = tuple(nominal.shape) == want or (self.act_dim == 1 and tuple(nominal.shape) == (H, self.n_envs))
+            if nominal.dtype != torch.float32 or not ok_shape or not nominal.is_contiguous():
+                raise ValueError(f"nominal must be a contiguous float32 tensor {want}; got {nominal.dtype} {tuple(nominal.shape)}")
+            if self.act_dim > 0 and sigma is None:
+                raise ValueError("nominal on a continuous env needs sigma")
+        return H, K, nominal, float(0.0 if sigma is None else sigma), dtype
+
+    @_on_device
+    def sample_candidates(self, H, K, seed, nominal=None, sigma=None, dtype=None):
+        """The candidate sequences plan_shooting(H, K, seed, nominal=, sigma=) draws, written out (emei_sample_candidates):
+        [H, N, K(, act_dim)] in evaluate_sequences' layout.  nominal None: fair coin flips / uniform on the ctrlrange; else float32
+        [H, N] Bernoulli probabilities (discrete) or [H, N, act_dim] means of clipped Gaussians with `sigma` (continuous).
+        dtype: uint8 / int32 / int64 (discrete; the default int64) or float32."""
+        H, K, nominal, sigma, dtype = self._candidate_args(H, K, nominal, sigma, dtype)
+        shape = (H, self.n_envs, K) + ((self.act_dim,) if self.act_dim > 1 else ())
+        out = torch.empty(shape, dtype=dtype, device=self.device)
+        L.check(L.lib().emei_sample_candidates(self._h, H, K, int(seed) & (2**64 - 1), _ptr(nominal), sigma, _ptr(out),
+                                               _ACT_DTYPES[dtype], _stream()))
+        return out
+
+    @_on_device
+    def plan_shooting(self, H, K, seed, discount=1.0, nominal=None, sigma=None, start_state=None, sequence=False, length=False,
+                      dtype=None):
+        """Random shooting in two launches (emei_plan_shooting): K candidate sequences of H steps per env are drawn in the lanes
+        that score them from the current state (or `start_state` [N, state_dim] float64) and arg-maxed on the device.
+        -> (best_action [N(, act_dim)], best_return float64 [N], best_index int32 [N][, best_sequence [H, N(, act_dim)]]
+        [, best_length int32 [N]]): the first maximum of evaluate_sequences(sample_candidates(...)) per env, NaN returns below
+        everything.  The handle is left as it is.  Arguments as sample_candidates."""
+        H, K, nominal, sigma, dtype = self._candidate_args(H, K, nominal, sigma, dtype)
+        st = None
+        if start_state is not None:
+            st = torch.as_tensor(start_state, device=self.device)
+            if st.dtype != torch.float64 or tuple(st.shape) != (self.n_envs, self.state_dim) or not st.is_contiguous():
+                raise ValueError(f"start_state must be a contiguous float64 tensor {(self.n_envs, self.state_dim)} on {self.device}; "
+                                 f"got {st.dtype} {tuple(st.shape)}")
+        need = int(L.lib().emei_plan_shooting_workspace_bytes(self.n_envs, K))
+        if need < 0:
+            L.check(need)
+        ws = getattr(self, "_plan_ws", None)
+        if ws is None or ws.numel() * 8 < need:  # grow-only (float64 elements: 8-byte aligned records)
+            ws = self._plan_ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+        tail = (self.act_dim,) if self.act_dim > 1 else ()
+        act = torch.empty((self.n_envs,) + tail, dtype=dtype, device=self.device)
+        seq = torch.empty((H, self.n_envs) + tail, dtype=dtype, device=self.device) if sequence else None
+        ret = torch.empty(self.n_envs, dtype=torch.float64, device=self.device)
+        idx = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+        ln = torch.empty(self.n_envs, dtype=torch.int32, device=self.device) if length else None
+        L.check(L.lib().emei_plan_shooting(self._h, H, K, int(seed) & (2**64 - 1), _ptr(nominal), sigma, float(discount), _ptr(st),
+                                           _ptr(ws), _ptr(act), _ACT_DTYPES[dtype], _ptr(seq), _ptr(ret), _ptr(idx), _ptr(ln),
+                                           _stream()))
+        return (act, ret, idx) + ((seq,) if sequence else ()) + ((ln,) if length else ())
+
     @_on_device
     def capture_step_graph(self, actions, auto_reset=False):
         """Capture one emei_step launch per row of `actions` [K, N(,act_dim)] into a hipGraph.

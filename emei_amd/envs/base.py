@@ -293,6 +293,33 @@ class HipEnv(EmeiEnv):
             return out
         return tuple(t.cpu().numpy() for t in out)
 
+    def plan_random_shooting(self, horizon, n_candidates, seed, discount=1.0, nominal=None, sigma=None, start_state=None,
+                             sequence=False, length=False, dtype=None):
+        """Random-shooting MPC's planning half in two launches (Engine.plan_shooting, ABI emei_plan_shooting): per env,
+        `n_candidates` action sequences of `horizon` steps are drawn on the device as a pure function of (seed, env, candidate),
+        scored as evaluate_action_sequences scores them, and the first best one is returned —
+        (best_action [num_envs(, act_dim)], best_return float64 [num_envs], best_index int32 [num_envs][, best_sequence
+        [horizon, num_envs(, act_dim)]][, best_length int32 [num_envs]]).  nominal: Bernoulli probabilities [horizon, num_envs]
+        (discrete) or means [horizon, num_envs, act_dim] of Gaussians with `sigma`, clipped to the action space (continuous);
+        None: fair coins / uniform on the action space.  best_action has the dtype step() takes (int64 / float32) unless `dtype`
+        says otherwise.  A NumPy `nominal` or `start_state` gives NumPy arrays; otherwise tensors, which step() takes as they are.
+        The env's state is left as it is."""
+        import torch
+
+        assert self.state is not None, "Call reset before using step method."  # base_control.py:67
+        eng = self.engine
+        as_numpy = isinstance(nominal, np.ndarray) or isinstance(start_state, np.ndarray)
+        nom = st = None
+        if nominal is not None:
+            nom = nominal if isinstance(nominal, torch.Tensor) else torch.as_tensor(np.asarray(nominal))
+            nom = nom.to(device=eng.device, dtype=torch.float32).contiguous()
+        if start_state is not None:
+            st = start_state if isinstance(start_state, torch.Tensor) else torch.as_tensor(np.asarray(start_state))
+            st = st.to(device=eng.device, dtype=torch.float64).contiguous()
+        out = eng.plan_shooting(horizon, n_candidates, seed, discount=discount, nominal=nom, sigma=sigma, start_state=st,
+                                sequence=sequence, length=length, dtype=dtype)
+        return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+
 
 def joint_sigmas(params, nq):
     """init_noise_params / obs_noise_params -> (pos sigma [nq], vel sigma [nq]) per (1-dof) joint:

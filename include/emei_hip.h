@@ -34,7 +34,9 @@ extern "C" {
  *    (struct_size 408; a 400-byte caller gets euler / automatic), emei_get_rollout_faults, EMEI_NEXT_OBS_ODE_RK4.
  * 7: emei_set_obs_peers + emei_peer_buffer_create / open / close / destroy (multi-GPU observation return by peer writes from the
  *    rollout kernel), EMEI_KERNEL_PEND_STAGED_PEERS_FREQ1 / EMEI_KERNEL_PEND_STAGED_PEERS.
- * 8: emei_evaluate_sequences (K candidate action sequences per env scored from the current or a given state in one launch). */
+ * 8: emei_evaluate_sequences (K candidate action sequences per env scored from the current or a given state in one launch).
+ *    Additive under 8 (no existing prototype or struct changes): emei_plan_shooting_workspace_bytes, emei_sample_candidates,
+ *    emei_plan_shooting (random-shooting planning with the candidates drawn and arg-maxed on the device). */
 #define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
@@ -306,6 +308,54 @@ EMEI_API int emei_rollout(emei_env* h, int32_t n_steps, const void* actions, int
 EMEI_API int emei_evaluate_sequences(emei_env* h, int32_t horizon, int32_t n_candidates, const void* actions, int action_dtype,
                                      double discount, const double* start_state, double* return_out, int32_t* length_out,
                                      float* final_obs_out, void* stream);
+
+/* Random-shooting planning on the true dynamics, the planner's answer to the query above (core.py:18-37,190-193: freeze() "for
+ * rollout-test or query", get_batch_next_obs): the candidates are drawn in the lanes that score them and arg-maxed on the device,
+ * so neither the [horizon, n_envs, n_candidates] actions nor the [n_envs, n_candidates] returns ever exist in memory.
+ *
+ * The candidates (normative).  Candidate (i, k) owns the 32-bit word stream
+ *     W[m] = philox4x32_10(key = seed, counter = (g lo, g hi, k, m >> 2)).v[m & 3],   g = emei_config.env_index_offset + i
+ * — Philox4x32-10 as the reset generator runs it, k in the counter word that has the episode there — and u(w) = (w >> 8) * 2^-24.
+ * A sequence is a pure function of (seed, g, k): reproducible, independent of sharding, recoverable from k alone.
+ *   discrete envs (act_dim 0): action[t] = u(W[t]) < p ? 1 : 0, p = 0.5 (nominal NULL: 1 - the top bit of W[t]) or
+ *       nominal[t, i], float32 [horizon, n_envs] Bernoulli probabilities; sigma is ignored
+ *   continuous, nominal NULL: action[t, a] = fmaf(u(W[t * act_dim + a]), hi - lo, lo) in float32, [lo, hi] the env's ctrlrange
+ *       (the kernels' model constants: +-3 for the InvertedPendulum family, +-1 otherwise)
+ *   continuous, nominal = float32 [horizon, n_envs, act_dim] means: c = t * act_dim + a, q = c >> 1, (z0, z1) = the reset
+ *       generator's Box-Muller of (W[2q], W[2q + 1]), z = (c & 1) ? z1 : z0, action = min(max(fmaf((float)sigma, z, mean), lo), hi)
+ *
+ * emei_sample_candidates writes them out, actions_out [horizon, n_envs, n_candidates(, act_dim)] in emei_evaluate_sequences'
+ * layout and in action_dtype (U8 / I32 / I64 for the discrete envs, F32 for the continuous ones): for tests and for callers that
+ * want the sequences themselves.  It needs no state.
+ *
+ * emei_plan_shooting scores candidate (i, k) exactly as emei_evaluate_sequences scores those actions — the same start state
+ * rule (start_state NULL: the handle's state), the per-step arithmetic of emei_rollout, ret = sum over t < L of discount^t *
+ * (double)(float)r_t in step order, L = the first terminal step + 1 or horizon; no observation noise, TimeLimit or auto-reset; the
+ * handle is untouched, its reset key included (seed is this call's own key) — and returns per env i
+ *   best_index_out[i]      k*, the best candidate
+ *   best_return_out[i]     ret(i, k*)
+ *   best_length_out[i]     L(i, k*) (NULL: skipped)
+ *   best_action_out[i(, :)]       candidate k*'s action at t = 0, in action_dtype
+ *   best_sequence_out[t, i(, :)]  its whole sequence, [horizon, n_envs(, act_dim)] (NULL: skipped)
+ * Order: candidate a beats b if ret_a > ret_b, or if ret_b is NaN and ret_a is not; otherwise the lower k wins.  k* is the first
+ * index of the maximum, NaN counts as below everything (-inf included), all-NaN gives k* = 0 with a NaN return.  The result does
+ * not depend on how an env's candidates fall onto waves or blocks.
+ * workspace: emei_plan_shooting_workspace_bytes(n_envs, n_candidates) bytes of device memory, 16-byte aligned, contents
+ * irrelevant before and after (one record per (wave, env) segment of the first of the call's two launches).
+ * EMEI_ERR_INVALID before any HIP call, scalars first: horizon < 1, n_candidates < 1, discount outside (0, 1]; then a NULL
+ * handle; nominal with sigma not finite or <= 0 on a continuous env; n_envs * n_candidates > 2^31 - 1 (or horizon * act_dim);
+ * a wrong action_dtype; NULL workspace, best_action_out, best_return_out or best_index_out.  EMEI_ERR_STATE without a state.
+ * Neither allocates nor synchronises (capturable).  Newton solves that end at the iteration cap count into
+ * emei_get_solver_cap_hits. */
+/* bytes of device scratch emei_plan_shooting needs for this shape; host only, no handle, no HIP call.
+ * Negative (EMEI_ERR_INVALID) if n_envs < 1, n_candidates < 1 or n_envs * n_candidates > 2^31 - 1. */
+EMEI_API int64_t emei_plan_shooting_workspace_bytes(int64_t n_envs, int32_t n_candidates);
+EMEI_API int emei_sample_candidates(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal,
+                                    double sigma, void* actions_out, int action_dtype, void* stream);
+EMEI_API int emei_plan_shooting(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal, double sigma,
+                                double discount, const double* start_state, void* workspace, void* best_action_out,
+                                int action_dtype, void* best_sequence_out, double* best_return_out, int32_t* best_index_out,
+                                int32_t* best_length_out, void* stream);
 
 /* Which kernel the LAST emei_step / emei_rollout of this handle launched (enum emei_kernel_id): a debug /
  * test getter, so that a parity test can assert that the path it checked is the path bench.py times. */
