@@ -824,6 +824,61 @@ extern "C" EMEI_API int emei_plan_shooting(emei_env* h, int32_t horizon, int32_t
     return rc == EMEI_OK ? rc : fail(rc, "emei_plan_shooting: launch failed (%s)", hipGetErrorString(hipGetLastError()));
 }
 
+// ---------------------------------------------------------------------------------------------
+// emei_plan_mppi: the plan kernel of emei_plan_shooting with every return kept, then the weighted mean of the redrawn candidates.
+// Workspace: emei_plan_shooting's partials (a multiple of 16 bytes), then n_envs * n_candidates float64 returns / weights.
+extern "C" EMEI_API int64_t emei_plan_mppi_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
+    if (n_envs < 1 || n_envs > INT32_MAX) return fail(EMEI_ERR_INVALID, "emei_plan_mppi_workspace_bytes: n_envs=%lld", (long long)n_envs);
+    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "emei_plan_mppi_workspace_bytes: n_candidates=%d < 1", n_candidates);
+    const int64_t nk = n_envs * (int64_t)n_candidates;
+    if (nk > INT32_MAX)
+        return fail(EMEI_ERR_INVALID, "emei_plan_mppi_workspace_bytes: n_envs * n_candidates = %lld exceeds 2^31 - 1", (long long)nk);
+    static_assert(sizeof(PlanPartial) % 16 == 0, "the returns behind the partials stay 16-byte aligned");
+    return (int64_t)sizeof(PlanPartial) * ((nk + kWave - 1) / kWave + n_envs) + (int64_t)sizeof(double) * nk;
+}
+
+extern "C" EMEI_API int emei_plan_mppi(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal, double sigma,
+                                       double discount, double temperature, const double* start_state, void* workspace,
+                                       float* nominal_out, double* best_return_out, int32_t* best_index_out, double* ess_out,
+                                       void* stream) {
+    if (horizon < 1) return fail(EMEI_ERR_INVALID, "emei_plan_mppi: horizon=%d < 1", horizon);
+    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "emei_plan_mppi: n_candidates=%d < 1", n_candidates);
+    if (!(discount > 0.0 && discount <= 1.0)) return fail(EMEI_ERR_INVALID, "emei_plan_mppi: discount=%g is outside (0, 1]", discount);
+    if (!(std::isfinite(temperature) && temperature > 0.0))
+        return fail(EMEI_ERR_INVALID, "emei_plan_mppi: temperature=%g must be finite and > 0", temperature);
+    CandidateSpec sp{};
+    sp.seed = seed;
+    // no actions leave this call: the dtype the shared checks see is one the env's kind takes
+    const int dtype = h && h->act_dim > 0 ? EMEI_ACT_F32 : EMEI_ACT_U8;
+    if (int rc = check_candidates("emei_plan_mppi", h, horizon, n_candidates, nominal, sigma, dtype, sp)) return rc;
+    if (!workspace) return fail(EMEI_ERR_INVALID, "emei_plan_mppi: null workspace");
+    if (!nominal_out) return fail(EMEI_ERR_INVALID, "emei_plan_mppi: null nominal_out");
+    EMEI_ON_DEVICE(h, "emei_plan_mppi");
+    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "emei_plan_mppi: call reset before using the state");
+    const int64_t nk = h->cfg.n_envs * (int64_t)n_candidates;
+    double* returns = (double*)((char*)workspace + sizeof(PlanPartial) * ((nk + kWave - 1) / kWave + h->cfg.n_envs));
+    int rc;
+    if (!steps_as_body(h->cfg)) {  // the kernel family emei_rollout runs for this handle
+        PendLaunch L = pend_base(h, stream);
+        L.op = PEND_OP_PLAN;
+        L.action_dtype = dtype, L.n_steps = horizon;
+        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
+        L.cand = sp, L.partials = workspace, L.return_out = returns;
+        rc = pend_launch(L);
+    } else {
+        BodyLaunch L = body_base(h, stream);
+        L.op = BODY_OP_PLAN;
+        L.n_steps = horizon;
+        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
+        L.cand = sp, L.partials = workspace, L.return_out = returns;
+        rc = body_launch(L);
+    }
+    if (rc == EMEI_OK)
+        rc = launch_plan_mppi_finish(workspace, returns, sp, h->cfg.n_envs, n_candidates, horizon, h->act_dim, temperature, nominal_out,
+                                     best_return_out, best_index_out, ess_out, (hipStream_t)stream);
+    return rc == EMEI_OK ? rc : fail(rc, "emei_plan_mppi: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+}
+
 extern "C" EMEI_API int emei_compact_done(emei_env* h, int32_t* idx_out, int32_t* count_out, void* stream) {
     if (!h || !idx_out || !count_out) return fail(EMEI_ERR_INVALID, "emei_compact_done: null argument");
     EMEI_ON_DEVICE(h, "emei_compact_done");

@@ -205,7 +205,8 @@ struct BodyLaunch {
     double discount = 1.0;
     double* return_out = nullptr;   // [n * K]
     int32_t* length_out = nullptr;  // [n * K]
-    // emei_plan_shooting (as PendLaunch): partials != null -> candidates drawn in the lanes, one PlanPartial per (wave, env) segment
+    // emei_plan_shooting (as PendLaunch): partials != null -> candidates drawn in the lanes, one PlanPartial per (wave, env) segment;
+    // emei_plan_mppi: return_out != null as well -> every candidate's return is kept there too
     CandidateSpec cand = {};
     void* partials = nullptr;
 };
@@ -694,7 +695,8 @@ __global__ void __launch_bounds__(kBlock)
 // DRAWN (emei_plan_shooting): the controls are the lane's own draws (emei_device.h:draw_action; every step starts its word
 // stream afresh, so no generator state is held across a step) and the lane keeps (ret, len) for plan_reduce_wave instead of
 // storing them at its last counted step.  The step is the same code either way.
-template <class Body, bool RK4, bool DRAWN = false>
+// KEEP (emei_plan_mppi, with DRAWN): every active lane also stores its return to ret_out[j], as pend_plan_kernel's.
+template <class Body, bool RK4, bool DRAWN = false, bool KEEP = false>
 __global__ void __launch_bounds__(kBlock)
     body_plan_kernel(const typename Body::real* state, const double* start_rows, const float* actions, int64_t n_envs,
                      int32_t n_cand, int32_t horizon, double discount, int freq_rate, int semi, typename Body::Model m,
@@ -772,6 +774,9 @@ __global__ void __launch_bounds__(kBlock)
         if (__ballot(live) == 0ull) break;  // wave-uniform
     }
     if constexpr (DRAWN) plan_reduce_wave(j, nk, i, n_cand, ret, len, partials);
+    if constexpr (DRAWN && KEEP) {
+        if (active) ret_out[j] = ret;
+    }
 }
 
 // every launch of one Body type (one translation unit instantiates exactly one Body: body_tu.hip)
@@ -918,6 +923,17 @@ static int launch_body(const BodyLaunch& L) {
             const int semi = (int)(L.integrator == EMEI_INTEG_SEMI_IMPLICIT);
             const SinCosEntry* tt = (const SinCosEntry*)L.trig;
             PlanPartial* pp = (PlanPartial*)L.partials;
+            if (pp && L.return_out) {  // emei_plan_mppi: as emei_plan_shooting, every candidate's return kept as well
+                if (L.integrator == EMEI_INTEG_RK4)
+                    hipLaunchKernelGGL((body_plan_kernel<Body, true, true, true>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state,
+                                       L.start_rows, (const float*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, 0, m,
+                                       tt, L.cap_hits, L.return_out, (int32_t*)nullptr, (float*)nullptr, L.cand, pp);
+                else
+                    hipLaunchKernelGGL((body_plan_kernel<Body, false, true, true>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state,
+                                       L.start_rows, (const float*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, semi,
+                                       m, tt, L.cap_hits, L.return_out, (int32_t*)nullptr, (float*)nullptr, L.cand, pp);
+                break;
+            }
             if (pp) {  // emei_plan_shooting
                 if (L.integrator == EMEI_INTEG_RK4)
                     hipLaunchKernelGGL((body_plan_kernel<Body, true, true>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state,

@@ -55,7 +55,8 @@ struct PendLaunch {
     double* return_out = nullptr;   // [n * K]
     int32_t* length_out = nullptr;  // [n * K]
     // emei_plan_shooting: partials != null -> the candidates are drawn in the lanes under `cand` and the kernel leaves one
-    // PlanPartial per (wave, env) segment instead of return_out / length_out
+    // PlanPartial per (wave, env) segment instead of return_out / length_out; emei_plan_mppi: with return_out != null as well, every
+    // candidate's return is kept there too
     CandidateSpec cand = {};
     void* partials = nullptr;
 };
@@ -76,5 +77,9 @@ int launch_sample_candidates(const CandidateSpec& sp, int64_t n_envs, int32_t n_
 int launch_plan_finish(const void* partials, const CandidateSpec& sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim,
                        void* best_action, int action_dtype, void* best_sequence, double* best_return, int32_t* best_index,
                        int32_t* best_length, hipStream_t s);
+// the second launch of emei_plan_mppi: `returns` [n_envs * n_cand] as the plan kernel left them (overwritten by the weights)
+int launch_plan_mppi_finish(const void* partials, double* returns, const CandidateSpec& sp, int64_t n_envs, int32_t n_cand, int32_t horizon,
+                            int act_dim, double temperature, float* nominal_out, double* best_return, int32_t* best_index, double* ess,
+                            hipStream_t s);
 
 }  // namespace emei

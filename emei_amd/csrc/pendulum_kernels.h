@@ -607,7 +607,9 @@ __global__ void __launch_bounds__(kBlock)
 // (emei_device.h:draw_action; ActT is then the drawn value's type, int or float, and `actions` unused), one Philox block per four
 // steps for the discrete envs instead of the prefetch — and instead of 12 B per candidate the wave leaves one PlanPartial per
 // (wave, env) segment (plan_reduce_wave).  The step loop is the same code either way.
-template <class Env, typename ActT, bool DRAWN = false>
+// KEEP (emei_plan_mppi, with DRAWN): every lane also stores its return to ret_out[j] (8 B per candidate) for the weights of
+// plan_mppi_finish_kernel; nothing else changes, and the instantiations without it are the code they were.
+template <class Env, typename ActT, bool DRAWN = false, bool KEEP = false>
 __global__ void __launch_bounds__(kBlock)
     pend_plan_kernel(const typename Env::real* state, const double* start_rows, const ActT* actions, int64_t n_envs, int32_t n_cand,
                      int32_t horizon, double discount, int freq_rate, typename Env::Params p, const SinCosEntry* trig,
@@ -671,6 +673,7 @@ __global__ void __launch_bounds__(kBlock)
         }
     }
     if constexpr (DRAWN) {
+        if constexpr (KEEP) ret_out[j] = ret;  // j < nk here
         plan_reduce_wave(j, nk, i, n_cand, ret, len, partials);
     } else {
         ret_out[j] = ret;
@@ -839,6 +842,12 @@ static int launch_env(const PendLaunch& L) {
             const R* st = (const R*)L.state;
             if (L.partials) {  // emei_plan_shooting: candidates drawn in the lanes, one partial per (wave, env) segment
                 using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
+                if (L.return_out) {  // emei_plan_mppi: every candidate's return is kept as well
+                    hipLaunchKernelGGL((pend_plan_kernel<Env, DrawT, true, true>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
+                                       (const DrawT*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p, a.trig,
+                                       L.return_out, (int32_t*)nullptr, (float4*)nullptr, L.cand, (PlanPartial*)L.partials);
+                    break;
+                }
                 hipLaunchKernelGGL((pend_plan_kernel<Env, DrawT, true>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
                                    (const DrawT*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p, a.trig,
                                    (double*)nullptr, (int32_t*)nullptr, (float4*)nullptr, L.cand, (PlanPartial*)L.partials);

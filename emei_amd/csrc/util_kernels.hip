@@ -153,6 +153,86 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
+// all lanes of the wave end with the same bits: x + y is commutative, so both partners of a butterfly step compute the same sum
+__device__ __forceinline__ double wave_sum_all(double v) {
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) v += __shfl_xor(v, d, kWave);
+    return v;
+}
+
+// Second launch of emei_plan_mppi, one wave per env, lane l owning the candidates k = l, l + 64, ...:
+//   1. (k*, r*) from the env's partials, as plan_finish_kernel finds them;
+//   2. the lane turns its candidates' returns (left by the plan kernel, 8 B each) into the weights of the header's case analysis
+//      and writes them back over the returns — it is the only reader of what it wrote, so nothing has to become visible to another
+//      lane — and Z = sum w, sum w^2 are reduced;
+//   3. the word stream is walked one Philox block at a time: block b carries the components c = 4b .. 4b + 3 (c = t * act_dim + a;
+//      four coin flips, four uniforms or two Box-Muller pairs: draw_action reads W[c] or the pair (W[c & ~1], W[c | 1]), inside
+//      block c >> 2 either way), the lane redraws them for each of its candidates through draw_action — each Philox block of each
+//      candidate once — and accumulates four weighted float64 sums, the wave reduces them and lane 0 stores the four means.
+// Summation order (the reproducibility clause): a lane adds its candidates in ascending k, the butterfly adds lanes l and l ^ d for
+// d = 1, 2, .., 32 — a tree over k alone, whatever n_envs, the shard or the first launch's waves were.
+// In place (nominal_out == sp.nominal): entry (t, i, a) is read by this wave in block c >> 2 only, before the block's stores, and
+// belongs to no other wave.
+__global__ void __launch_bounds__(kBlock)
+    plan_mppi_finish_kernel(const PlanPartial* partials, double* returns, CandidateSpec sp, int64_t n_envs, int32_t n_cand, int32_t horizon,
+                            int act_dim, double temperature, float* nominal_out, double* best_return, int32_t* best_index, double* ess) {
+    const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / kWave;  // wave-uniform
+    const int lane = (int)(threadIdx.x & (kWave - 1));
+    if (i >= n_envs) return;
+    const int64_t w0 = (i * n_cand) / kWave, w1 = ((i + 1) * n_cand - 1) / kWave;
+    double rs = __builtin_nan("");  // (NaN, INT32_MAX) loses to every partial
+    int32_t ks = INT32_MAX;
+    for (int64_t w = w0 + lane; w <= w1; w += kWave) {
+        const PlanPartial p = partials[w + i];
+        if (plan_replaces(rs, ks, p.ret, p.k)) rs = p.ret, ks = p.k;
+    }
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const double r2 = __shfl_xor(rs, d, kWave);
+        const int32_t k2 = __shfl_xor(ks, d, kWave);
+        if (plan_replaces(rs, ks, r2, k2)) rs = r2, ks = k2;
+    }
+    double* wt = returns + i * n_cand;
+    double z = 0.0, z2 = 0.0;
+    for (int32_t k = lane; k < n_cand; k += kWave) {
+        const double r = wt[k];
+        const double e = exp((r - rs) / temperature);  // r < r*: the argument is negative, -inf included
+        const double w = rs != rs ? 1.0 : (r != r ? 0.0 : (r == rs ? 1.0 : e));
+        wt[k] = w;
+        z += w, z2 += w * w;
+    }
+    z = wave_sum_all(z), z2 = wave_sum_all(z2);  // Z >= 1: candidate k* has weight 1
+    if (lane == 0) {
+        if (best_return) best_return[i] = rs;
+        if (best_index) best_index[i] = ks;
+        if (ess) ess[i] = z * z / z2;
+    }
+    const int na = act_dim > 0 ? act_dim : 1;
+    const int32_t n_comp = horizon * na;  // <= 2^31 - 1 (abi.hip:check_candidates)
+    for (int32_t c0 = 0; c0 < n_comp; c0 += 4) {
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int32_t k = lane; k < n_cand; k += kWave) {
+            const double w = wt[k];
+            CandidateWords cw(sp.seed, sp.env_offset + (uint64_t)i, (uint32_t)k);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int32_t c = min(c0 + u, n_comp - 1);  // past the end: the last component again, dropped below
+                const float v = draw_action(cw, sp, n_envs, i, c / na, c % na, act_dim);
+                acc[u] += w * (double)v;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] = wave_sum_all(acc[u]);
+        if (lane == 0) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int32_t c = c0 + u;
+                if (c < n_comp) nominal_out[((int64_t)(c / na) * n_envs + i) * na + c % na] = (float)(acc[u] / z);
+            }
+        }
+    }
+}
+
 int launch_sample_candidates(const CandidateSpec& sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim, void* actions_out,
                              int action_dtype, hipStream_t s) {
     dim3 grid((unsigned)((n_envs * n_cand + kBlock - 1) / kBlock));
@@ -165,6 +245,14 @@ int launch_plan_finish(const void* partials, const CandidateSpec& sp, int64_t n_
     dim3 grid((unsigned)((n_envs + kBlock / kWave - 1) / (kBlock / kWave)));
     hipLaunchKernelGGL(plan_finish_kernel, grid, dim3(kBlock), 0, s, (const PlanPartial*)partials, sp, n_envs, n_cand, horizon, act_dim,
                        best_action, action_dtype, best_sequence, best_return, best_index, best_length);
+    return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;
+}
+int launch_plan_mppi_finish(const void* partials, double* returns, const CandidateSpec& sp, int64_t n_envs, int32_t n_cand, int32_t horizon,
+                            int act_dim, double temperature, float* nominal_out, double* best_return, int32_t* best_index, double* ess,
+                            hipStream_t s) {
+    dim3 grid((unsigned)((n_envs + kBlock / kWave - 1) / (kBlock / kWave)));
+    hipLaunchKernelGGL(plan_mppi_finish_kernel, grid, dim3(kBlock), 0, s, (const PlanPartial*)partials, returns, sp, n_envs, n_cand, horizon,
+                       act_dim, temperature, nominal_out, best_return, best_index, ess);
     return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;
 }
 

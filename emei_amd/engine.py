@@ -395,6 +395,47 @@ class Engine:
         return (act, ret, idx) + ((seq,) if sequence else ()) + ((ln,) if length else ())
 
     @_on_device
+    def plan_mppi(self, H, K, seed, temperature, discount=1.0, nominal=None, sigma=None, start_state=None, out=None, ess=False):
+        """The MPPI update of a nominal sequence in two launches (emei_plan_mppi): the K candidates per env that
+        plan_shooting(H, K, seed, nominal=, sigma=) scores are scored the same way, weighted by exp((return - best) / temperature)
+        (NaN returns weigh 0, ties with the best 1) and averaged — the candidates redrawn on the device, never stored.
+        -> (nominal_out float32 [H, N(, act_dim)], best_return float64 [N], best_index int32 [N][, ess float64 [N]]): the weighted
+        mean (a mean inside the ctrlrange, or a Bernoulli probability for the discrete envs: the next call's `nominal`), plan_shooting's
+        winner bit for bit, and the effective sample size (sum w)^2 / sum w^2.  out: a float32 tensor of nominal_out's shape to write
+        into; it may be `nominal` itself (in place).  The handle is left as it is.  Other arguments as sample_candidates."""
+        H, K, nominal, sigma, _ = self._candidate_args(H, K, nominal, sigma, None)
+        temperature = float(temperature)
+        st = None
+        if start_state is not None:
+            st = torch.as_tensor(start_state, device=self.device)
+            if st.dtype != torch.float64 or tuple(st.shape) != (self.n_envs, self.state_dim) or not st.is_contiguous():
+                raise ValueError(f"start_state must be a contiguous float64 tensor {(self.n_envs, self.state_dim)} on {self.device}; "
+                                 f"got {st.dtype} {tuple(st.shape)}")
+        shape = (H, self.n_envs) + ((self.act_dim,) if self.act_dim > 1 else ())
+        if out is None:
+            out = torch.empty(shape if nominal is None else tuple(nominal.shape), dtype=torch.float32, device=self.device)
+        else:
+            if not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous() \
+                    or not (tuple(out.shape) == shape or (self.act_dim == 1 and tuple(out.shape) == (H, self.n_envs, 1))):
+                raise ValueError(f"out must be a contiguous float32 tensor {shape} on {self.device}")
+            if nominal is not None and out.data_ptr() != nominal.data_ptr():
+                lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * 4
+                if lo < nominal.data_ptr() + nominal.numel() * 4 and nominal.data_ptr() < hi:
+                    raise ValueError("out may be nominal itself, not a tensor that overlaps it partly")
+        need = int(L.lib().emei_plan_mppi_workspace_bytes(self.n_envs, K))
+        if need < 0:
+            L.check(need)
+        ws = getattr(self, "_mppi_ws", None)
+        if ws is None or ws.numel() * 8 < need:  # grow-only (float64 elements: 8-byte aligned records)
+            ws = self._mppi_ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+        ret = torch.empty(self.n_envs, dtype=torch.float64, device=self.device)
+        idx = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+        es = torch.empty(self.n_envs, dtype=torch.float64, device=self.device) if ess else None
+        L.check(L.lib().emei_plan_mppi(self._h, H, K, int(seed) & (2**64 - 1), _ptr(nominal), sigma, float(discount), temperature,
+                                       _ptr(st), _ptr(ws), _ptr(out), _ptr(ret), _ptr(idx), _ptr(es), _stream()))
+        return (out, ret, idx) + ((es,) if ess else ())
+
+    @_on_device
     def capture_step_graph(self, actions, auto_reset=False):
         """Capture one emei_step launch per row of `actions` [K, N(,act_dim)] into a hipGraph.
 

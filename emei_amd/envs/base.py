@@ -320,6 +320,32 @@ class HipEnv(EmeiEnv):
                                 sequence=sequence, length=length, dtype=dtype)
         return tuple(t.cpu().numpy() for t in out) if as_numpy else out
 
+    def plan_mppi(self, horizon, n_candidates, seed, temperature, discount=1.0, nominal=None, sigma=None, start_state=None,
+                  out=None, ess=False):
+        """MPPI's update of a nominal action sequence in two launches (Engine.plan_mppi, ABI emei_plan_mppi): the candidates of
+        plan_random_shooting(horizon, n_candidates, seed, nominal=, sigma=) are scored as there, weighted by
+        exp((return - best return) / temperature) and averaged on the device —
+        (nominal_out float32 [horizon, num_envs(, act_dim)], best_return float64 [num_envs], best_index int32 [num_envs]
+        [, ess float64 [num_envs]]).  nominal_out is the next call's `nominal`: means inside the action space (continuous) or
+        Bernoulli probabilities (discrete; clamp them away from 0 and 1 to keep exploring).  out: a float32 tensor to write
+        nominal_out into, `nominal` itself included (tensors only).  A NumPy `nominal` or `start_state` gives NumPy arrays;
+        otherwise tensors.  The env's state is left as it is."""
+        import torch
+
+        assert self.state is not None, "Call reset before using step method."  # base_control.py:67
+        eng = self.engine
+        as_numpy = isinstance(nominal, np.ndarray) or isinstance(start_state, np.ndarray)
+        nom = st = None
+        if nominal is not None:
+            nom = nominal if isinstance(nominal, torch.Tensor) else torch.as_tensor(np.asarray(nominal))
+            nom = nom.to(device=eng.device, dtype=torch.float32).contiguous()
+        if start_state is not None:
+            st = start_state if isinstance(start_state, torch.Tensor) else torch.as_tensor(np.asarray(start_state))
+            st = st.to(device=eng.device, dtype=torch.float64).contiguous()
+        res = eng.plan_mppi(horizon, n_candidates, seed, temperature, discount=discount, nominal=nom, sigma=sigma, start_state=st,
+                            out=out, ess=ess)
+        return tuple(t.cpu().numpy() for t in res) if as_numpy else res
+
 
 def joint_sigmas(params, nq):
     """init_noise_params / obs_noise_params -> (pos sigma [nq], vel sigma [nq]) per (1-dof) joint:

@@ -36,7 +36,9 @@ extern "C" {
  *    rollout kernel), EMEI_KERNEL_PEND_STAGED_PEERS_FREQ1 / EMEI_KERNEL_PEND_STAGED_PEERS.
  * 8: emei_evaluate_sequences (K candidate action sequences per env scored from the current or a given state in one launch).
  *    Additive under 8 (no existing prototype or struct changes): emei_plan_shooting_workspace_bytes, emei_sample_candidates,
- *    emei_plan_shooting (random-shooting planning with the candidates drawn and arg-maxed on the device). */
+ *    emei_plan_shooting (random-shooting planning with the candidates drawn and arg-maxed on the device);
+ *    emei_plan_mppi_workspace_bytes, emei_plan_mppi (the MPPI update of a nominal sequence: the return-weighted mean of the same
+ *    candidates, redrawn on the device). */
 #define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
@@ -356,6 +358,49 @@ EMEI_API int emei_plan_shooting(emei_env* h, int32_t horizon, int32_t n_candidat
                                 double discount, const double* start_state, void* workspace, void* best_action_out,
                                 int action_dtype, void* best_sequence_out, double* best_return_out, int32_t* best_index_out,
                                 int32_t* best_length_out, void* stream);
+
+/* MPPI planning on the true dynamics (information-theoretic MPC; the planner-side use of the query core.py:18-37,190-193 serves):
+ * the nominal sequence is replaced by the return-weighted (soft-max) mean of the candidates emei_plan_shooting would score.  A
+ * candidate is a pure function of (seed, g, k), so a second pass redraws every candidate — no dynamics — and accumulates the
+ * mean: nothing of size horizon * n_envs * n_candidates is ever stored (8 bytes per candidate are, in the workspace).
+ *
+ * Candidates, start-state rule, per-step arithmetic, return r_k = ret(i, k) and length are exactly emei_plan_shooting's for the
+ * same (seed, nominal, sigma, discount, start_state), and (k*, r*) is its winner under the planner's order.  nominal NULL: fair
+ * coins / uniform draws on the ctrlrange.
+ *
+ * Weights (normative), per env i, float64:
+ *     r* is NaN (every return is NaN)                        w_k = 1 for all k
+ *     otherwise, r_k is NaN                                  w_k = 0
+ *     otherwise, r_k == r* (a +-inf maximum and all ties)    w_k = 1
+ *     otherwise                                              w_k = exp((r_k - r*) / temperature)   (-inf gives 0)
+ * hence Z = sum_k w_k >= 1.  Outputs:
+ *   nominal_out[t, i(, a)]  float32 [horizon, n_envs(, act_dim)] in nominal's layout:
+ *                           (float)(sum_k w_k * (double)action_k[t, a] / Z), action_k the float32 value of the candidate
+ *                           specification above (0.f or 1.f for the discrete envs); sums and quotient in float64, one rounding to
+ *                           float32.  A new mean inside the ctrlrange (continuous) or a Bernoulli probability in [0, 1] (discrete):
+ *                           either is a valid `nominal` of the next call.  Required.  It may be the same pointer as nominal (in
+ *                           place); any other overlap is undefined.  Entry (t, i, a) depends on nominal only at (t, i, a): it is
+ *                           read before it is written, and no other env's entries are touched.
+ *   best_index_out[i]       k*, and
+ *   best_return_out[i]      r*: bit-identical to emei_plan_shooting's (either may be NULL)
+ *   ess_out[i]              Z^2 / sum_k w_k^2, float64, the effective sample size (NULL: skipped)
+ * Reproducibility: everything written for env i is a pure function of (seed, g = env_index_offset + i, n_candidates, horizon, env
+ * i's nominal entries, sigma, r_.).  The summation tree depends on k only (candidates k = l mod 64 in ascending order, then a
+ * butterfly over l) — not on how candidates fall onto waves or blocks, on n_envs or on the shard — so repeated calls, graph replays
+ * and different shardings give the same bits (up to the lane dependence of r_k the HalfCheetah documents, 1e-9 relative).
+ * workspace: emei_plan_mppi_workspace_bytes(n_envs, n_candidates) bytes of device memory, 16-byte aligned, contents irrelevant
+ * before and after (emei_plan_shooting's records plus 8 bytes per candidate).
+ * EMEI_ERR_INVALID before any HIP call, scalars first: horizon < 1, n_candidates < 1, discount outside (0, 1], temperature not
+ * finite or <= 0; then a NULL handle; emei_plan_shooting's other checks (sigma with a nominal on a continuous env, n_envs *
+ * n_candidates, horizon * act_dim); NULL workspace or nominal_out.  EMEI_ERR_STATE without a state.  The handle is untouched.
+ * Neither allocates nor synchronises (capturable).  Newton solves that end at the iteration cap count into
+ * emei_get_solver_cap_hits. */
+/* bytes of device scratch emei_plan_mppi needs for this shape; host only, no handle, no HIP call.
+ * Negative (EMEI_ERR_INVALID) where emei_plan_shooting_workspace_bytes is. */
+EMEI_API int64_t emei_plan_mppi_workspace_bytes(int64_t n_envs, int32_t n_candidates);
+EMEI_API int emei_plan_mppi(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal, double sigma,
+                            double discount, double temperature, const double* start_state, void* workspace, float* nominal_out,
+                            double* best_return_out, int32_t* best_index_out, double* ess_out, void* stream);
 
 /* Which kernel the LAST emei_step / emei_rollout of this handle launched (enum emei_kernel_id): a debug /
  * test getter, so that a parity test can assert that the path it checked is the path bench.py times. */
