@@ -123,6 +123,9 @@ SYMBOLS = {
     "emei_plan_shooting": (C.c_int, [_vp, _i32, _i32, _u64, _vp, _dbl, _dbl, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "emei_plan_mppi_workspace_bytes": (_i64, [_i64, _i32]),
     "emei_plan_mppi": (C.c_int, [_vp, _i32, _i32, _u64, _vp, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "emei_sample_candidates_sigma": (C.c_int, [_vp, _i32, _i32, _u64, _vp, _vp, _vp, C.c_int, _vp]),
+    "emei_plan_cem_workspace_bytes": (_i64, [_i64, _i32]),
+    "emei_plan_cem": (C.c_int, [_vp, _i32, _i32, _i32, _u64, _vp, _dbl, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "emei_compact_done": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emei_get_counters": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emei_episode_init_obs": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),

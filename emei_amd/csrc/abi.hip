@@ -827,14 +827,16 @@ extern "C" EMEI_API int emei_plan_shooting(emei_env* h, int32_t horizon, int32_t
 // ---------------------------------------------------------------------------------------------
 // emei_plan_mppi: the plan kernel of emei_plan_shooting with every return kept, then the weighted mean of the redrawn candidates.
 // Workspace: emei_plan_shooting's partials (a multiple of 16 bytes), then n_envs * n_candidates float64 returns / weights.
-extern "C" EMEI_API int64_t emei_plan_mppi_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
-    if (n_envs < 1 || n_envs > INT32_MAX) return fail(EMEI_ERR_INVALID, "emei_plan_mppi_workspace_bytes: n_envs=%lld", (long long)n_envs);
-    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "emei_plan_mppi_workspace_bytes: n_candidates=%d < 1", n_candidates);
+static int64_t keep_workspace_bytes(const char* fn, int64_t n_envs, int32_t n_candidates) {  // also emei_plan_cem's
+    if (n_envs < 1 || n_envs > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs=%lld", fn, (long long)n_envs);
+    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "%s: n_candidates=%d < 1", fn, n_candidates);
     const int64_t nk = n_envs * (int64_t)n_candidates;
-    if (nk > INT32_MAX)
-        return fail(EMEI_ERR_INVALID, "emei_plan_mppi_workspace_bytes: n_envs * n_candidates = %lld exceeds 2^31 - 1", (long long)nk);
+    if (nk > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs * n_candidates = %lld exceeds 2^31 - 1", fn, (long long)nk);
     static_assert(sizeof(PlanPartial) % 16 == 0, "the returns behind the partials stay 16-byte aligned");
     return (int64_t)sizeof(PlanPartial) * ((nk + kWave - 1) / kWave + n_envs) + (int64_t)sizeof(double) * nk;
+}
+extern "C" EMEI_API int64_t emei_plan_mppi_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
+    return keep_workspace_bytes("emei_plan_mppi_workspace_bytes", n_envs, n_candidates);
 }
 
 extern "C" EMEI_API int emei_plan_mppi(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal, double sigma,
@@ -877,6 +879,74 @@ extern "C" EMEI_API int emei_plan_mppi(emei_env* h, int32_t horizon, int32_t n_c
         rc = launch_plan_mppi_finish(workspace, returns, sp, h->cfg.n_envs, n_candidates, horizon, h->act_dim, temperature, nominal_out,
                                      best_return_out, best_index_out, ess_out, (hipStream_t)stream);
     return rc == EMEI_OK ? rc : fail(rc, "emei_plan_mppi: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+}
+
+// emei_sample_candidates_sigma: emei_sample_candidates' Gaussian mode with the sigma read per entry (the scalar's check does not apply)
+extern "C" EMEI_API int emei_sample_candidates_sigma(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal,
+                                                     const float* sigma_map, void* actions_out, int action_dtype, void* stream) {
+    CandidateSpec sp{};
+    sp.seed = seed;
+    if (int rc = check_candidates("emei_sample_candidates_sigma", h, horizon, n_candidates, nominal, 1.0, action_dtype, sp)) return rc;
+    if (h->act_dim == 0) return fail(EMEI_ERR_INVALID, "emei_sample_candidates_sigma: a discrete env takes no sigma_map");
+    if (!nominal || !sigma_map) return fail(EMEI_ERR_INVALID, "emei_sample_candidates_sigma: null nominal or sigma_map");
+    if (!actions_out) return fail(EMEI_ERR_INVALID, "emei_sample_candidates_sigma: null argument");
+    EMEI_ON_DEVICE(h, "emei_sample_candidates_sigma");
+    const int rc = launch_sample_candidates_sigma(CandidateSpecMap(sp, sigma_map), h->cfg.n_envs, n_candidates, horizon, h->act_dim,
+                                                  actions_out, (hipStream_t)stream);
+    return rc == EMEI_OK ? rc : fail(rc, "emei_sample_candidates_sigma: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+}
+
+// ---------------------------------------------------------------------------------------------
+// emei_plan_cem: emei_plan_mppi's first launch (with a sigma_map: its CandidateSpecMap instantiation), then the elite set and its
+// moments.  Workspace: emei_plan_mppi's layout — the selection's counters live in LDS.
+extern "C" EMEI_API int64_t emei_plan_cem_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
+    return keep_workspace_bytes("emei_plan_cem_workspace_bytes", n_envs, n_candidates);
+}
+
+extern "C" EMEI_API int emei_plan_cem(emei_env* h, int32_t horizon, int32_t n_candidates, int32_t n_elites, uint64_t seed,
+                                      const float* nominal, double sigma, const float* sigma_map, double discount,
+                                      const double* start_state, void* workspace, float* mean_out, float* std_out,
+                                      double* best_return_out, int32_t* best_index_out, double* elite_return_out, void* stream) {
+    if (horizon < 1) return fail(EMEI_ERR_INVALID, "emei_plan_cem: horizon=%d < 1", horizon);
+    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "emei_plan_cem: n_candidates=%d < 1", n_candidates);
+    if (n_elites < 1 || n_elites > n_candidates)
+        return fail(EMEI_ERR_INVALID, "emei_plan_cem: n_elites=%d is outside [1, n_candidates=%d]", n_elites, n_candidates);
+    if (!(discount > 0.0 && discount <= 1.0)) return fail(EMEI_ERR_INVALID, "emei_plan_cem: discount=%g is outside (0, 1]", discount);
+    CandidateSpec sp{};
+    sp.seed = seed;
+    // no actions leave this call: the dtype the shared checks see is one the env's kind takes
+    const int dtype = h && h->act_dim > 0 ? EMEI_ACT_F32 : EMEI_ACT_U8;
+    // with a sigma_map the scalar is ignored: the shared check sees one it accepts
+    if (int rc = check_candidates("emei_plan_cem", h, horizon, n_candidates, nominal, sigma_map ? 1.0 : sigma, dtype, sp)) return rc;
+    if (sigma_map && !nominal) return fail(EMEI_ERR_INVALID, "emei_plan_cem: a sigma_map needs a nominal");
+    if (h->act_dim == 0 && (sigma_map || std_out))
+        return fail(EMEI_ERR_INVALID, "emei_plan_cem: a discrete env takes no sigma_map and has no std_out");
+    if (!workspace) return fail(EMEI_ERR_INVALID, "emei_plan_cem: null workspace");
+    if (!mean_out) return fail(EMEI_ERR_INVALID, "emei_plan_cem: null mean_out");
+    EMEI_ON_DEVICE(h, "emei_plan_cem");
+    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "emei_plan_cem: call reset before using the state");
+    const int64_t nk = h->cfg.n_envs * (int64_t)n_candidates;
+    double* returns = (double*)((char*)workspace + sizeof(PlanPartial) * ((nk + kWave - 1) / kWave + h->cfg.n_envs));
+    int rc;
+    if (!steps_as_body(h->cfg)) {  // the kernel family emei_rollout runs for this handle
+        PendLaunch L = pend_base(h, stream);
+        L.op = PEND_OP_PLAN;
+        L.action_dtype = dtype, L.n_steps = horizon;
+        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
+        L.cand = sp, L.partials = workspace, L.return_out = returns, L.sigma_map = sigma_map;
+        rc = pend_launch(L);
+    } else {
+        BodyLaunch L = body_base(h, stream);
+        L.op = BODY_OP_PLAN;
+        L.n_steps = horizon;
+        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
+        L.cand = sp, L.partials = workspace, L.return_out = returns, L.sigma_map = sigma_map;
+        rc = body_launch(L);
+    }
+    if (rc == EMEI_OK)
+        rc = launch_plan_cem_finish(workspace, returns, sp, sigma_map, h->cfg.n_envs, n_candidates, n_elites, horizon, h->act_dim, mean_out,
+                                    std_out, best_return_out, best_index_out, elite_return_out, (hipStream_t)stream);
+    return rc == EMEI_OK ? rc : fail(rc, "emei_plan_cem: launch failed (%s)", hipGetErrorString(hipGetLastError()));
 }
 
 extern "C" EMEI_API int emei_compact_done(emei_env* h, int32_t* idx_out, int32_t* count_out, void* stream) {

@@ -209,6 +209,7 @@ struct BodyLaunch {
     // emei_plan_mppi: return_out != null as well -> every candidate's return is kept there too
     CandidateSpec cand = {};
     void* partials = nullptr;
+    const float* sigma_map = nullptr;  // emei_plan_cem: non-null -> the draws take their sigma per entry (CandidateSpecMap)
 };
 int body_launch(const BodyLaunch& L);  // body_dispatch.hip
 
@@ -696,12 +697,13 @@ __global__ void __launch_bounds__(kBlock)
 // stream afresh, so no generator state is held across a step) and the lane keeps (ret, len) for plan_reduce_wave instead of
 // storing them at its last counted step.  The step is the same code either way.
 // KEEP (emei_plan_mppi, with DRAWN): every active lane also stores its return to ret_out[j], as pend_plan_kernel's.
-template <class Body, bool RK4, bool DRAWN = false, bool KEEP = false>
+// Spec (emei_plan_cem with a sigma_map: CandidateSpecMap, with DRAWN and KEEP): as pend_plan_kernel's.
+template <class Body, bool RK4, bool DRAWN = false, bool KEEP = false, class Spec = CandidateSpec>
 __global__ void __launch_bounds__(kBlock)
     body_plan_kernel(const typename Body::real* state, const double* start_rows, const float* actions, int64_t n_envs,
                      int32_t n_cand, int32_t horizon, double discount, int freq_rate, int semi, typename Body::Model m,
                      const SinCosEntry* trig_tab, unsigned long long* cap_hits, double* ret_out, int32_t* len_out, float* final_obs,
-                     CandidateSpec sp, PlanPartial* partials) {
+                     Spec sp, PlanPartial* partials) {
     using R = typename Body::real;
     constexpr int NS = Body::NS, NO = Body::NO, NA = Body::NA;
     __shared__ SinCosEntry trig_s[kTrigTableSize];
@@ -923,6 +925,19 @@ static int launch_body(const BodyLaunch& L) {
             const int semi = (int)(L.integrator == EMEI_INTEG_SEMI_IMPLICIT);
             const SinCosEntry* tt = (const SinCosEntry*)L.trig;
             PlanPartial* pp = (PlanPartial*)L.partials;
+            if (L.sigma_map) {  // emei_plan_cem with a sigma per entry: every return kept
+                if (!pp || !L.return_out) return EMEI_ERR_INVALID;
+                const CandidateSpecMap spm(L.cand, L.sigma_map);
+                if (L.integrator == EMEI_INTEG_RK4)
+                    hipLaunchKernelGGL((body_plan_kernel<Body, true, true, true, CandidateSpecMap>), pgrid, dim3(kBlock), 0, L.stream,
+                                       (const R*)L.state, L.start_rows, (const float*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount,
+                                       L.freq_rate, 0, m, tt, L.cap_hits, L.return_out, (int32_t*)nullptr, (float*)nullptr, spm, pp);
+                else
+                    hipLaunchKernelGGL((body_plan_kernel<Body, false, true, true, CandidateSpecMap>), pgrid, dim3(kBlock), 0, L.stream,
+                                       (const R*)L.state, L.start_rows, (const float*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount,
+                                       L.freq_rate, semi, m, tt, L.cap_hits, L.return_out, (int32_t*)nullptr, (float*)nullptr, spm, pp);
+                break;
+            }
             if (pp && L.return_out) {  // emei_plan_mppi: as emei_plan_shooting, every candidate's return kept as well
                 if (L.integrator == EMEI_INTEG_RK4)
                     hipLaunchKernelGGL((body_plan_kernel<Body, true, true, true>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state,

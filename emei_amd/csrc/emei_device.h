@@ -601,9 +601,24 @@ __device__ __forceinline__ void boxmuller(uint32_t a, uint32_t b, float& z0, flo
 // Candidate (g, k) — g the GLOBAL env index, k the candidate — owns the word stream W[m] = philox4x32_10(seed, g, k, m >> 2).v[m & 3]:
 // k sits where the reset generator has the episode, `seed` is the call's own key.
 struct CandidateSpec {  // kernel argument
+    static constexpr bool kSigmaMap = false;
     uint64_t seed, env_offset;
     const float* nominal;  // null: Bernoulli(1/2) / uniform on the ctrlrange; else [horizon, n_envs(, act_dim)] probabilities / means
     float sigma, lo, hi;   // continuous envs: sigma of the Gaussian mode, the ctrlrange
+};
+// The Gaussian mode with a sigma per entry (emei_sample_candidates_sigma, emei_plan_cem): continuous envs only, `nominal` never null.
+// A type of its own, chosen at compile time by the kernels that take a spec as a template argument: the instantiations over
+// CandidateSpec are the code they were, and the float64 InvertedPendulum plan kernels (see CandidateWordsT) pay no scalar register for
+// a pointer they never read.
+struct CandidateSpecMap {  // kernel argument
+    static constexpr bool kSigmaMap = true;
+    uint64_t seed, env_offset;
+    const float* nominal;    // [horizon, n_envs, act_dim] means
+    const float* sigma_map;  // [horizon, n_envs, act_dim] sigmas, nominal's layout
+    float lo, hi;
+    CandidateSpecMap() = default;
+    CandidateSpecMap(const CandidateSpec& sp, const float* map)
+        : seed(sp.seed), env_offset(sp.env_offset), nominal(sp.nominal), sigma_map(map), lo(sp.lo), hi(sp.hi) {}
 };
 // (KEYS_IN_PLACE: as philox4x32_10's — for the 4-state plan kernels, whose float64 InvertedPendulum instantiations have no scalar
 // registers left for twenty precomputed round keys; the seed is a kernel argument there)
@@ -622,20 +637,27 @@ struct CandidateWordsT {  // W[] of one candidate, the last Philox block kept
 using CandidateWords = CandidateWordsT<false>;
 // THE draw: component a of step t of the candidate behind `cw`, env i of this shard.  na = the env's act_dim (0: discrete, the
 // value is 0.f or 1.f).  Used by the sampling kernel, by the plan kernels' step loops and by the kernel that rewrites the winner.
-template <class Words>
-__device__ __forceinline__ float draw_action(Words& cw, const CandidateSpec& sp, int64_t n_envs, int64_t i, int32_t t, int a, int na) {
-    if (na == 0) {
-        const float p = sp.nominal ? sp.nominal[(int64_t)t * n_envs + i] : 0.5f;
-        return u01(cw.word((uint32_t)t)) < p ? 1.f : 0.f;
+template <class Words, class Spec>
+__device__ __forceinline__ float draw_action(Words& cw, const Spec& sp, int64_t n_envs, int64_t i, int32_t t, int a, int na) {
+    if constexpr (!Spec::kSigmaMap) {
+        if (na == 0) {
+            const float p = sp.nominal ? sp.nominal[(int64_t)t * n_envs + i] : 0.5f;
+            return u01(cw.word((uint32_t)t)) < p ? 1.f : 0.f;
+        }
     }
     const uint32_t c = (uint32_t)t * (uint32_t)na + (uint32_t)a;
-    if (!sp.nominal) return fmaf(u01(cw.word(c)), sp.hi - sp.lo, sp.lo);
+    if constexpr (!Spec::kSigmaMap) {
+        if (!sp.nominal) return fmaf(u01(cw.word(c)), sp.hi - sp.lo, sp.lo);
+    }
     const uint32_t q = c >> 1;  // the pair (W[2q], W[2q + 1]) lies inside one Philox block
     float z0, z1;
     const uint32_t wa = cw.word(2u * q), wb = cw.word(2u * q + 1u);
     boxmuller(wa, wb, z0, z1);
     const float mean = sp.nominal[((int64_t)t * n_envs + i) * na + a];
-    return fminf(fmaxf(fmaf(sp.sigma, (c & 1u) ? z1 : z0, mean), sp.lo), sp.hi);
+    float sigma;
+    if constexpr (Spec::kSigmaMap) sigma = sp.sigma_map[((int64_t)t * n_envs + i) * na + a];
+    else sigma = sp.sigma;
+    return fminf(fmaxf(fmaf(sigma, (c & 1u) ? z1 : z0, mean), sp.lo), sp.hi);
 }
 __device__ __forceinline__ void store_action(void* p, int dtype, int64_t idx, float v) {
     switch (dtype) {  // wave-uniform

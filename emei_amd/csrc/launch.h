@@ -59,6 +59,7 @@ struct PendLaunch {
     // candidate's return is kept there too
     CandidateSpec cand = {};
     void* partials = nullptr;
+    const float* sigma_map = nullptr;  // emei_plan_cem: non-null -> the draws take their sigma per entry (CandidateSpecMap)
 };
 
 // pendulum_kernels.hip
@@ -81,5 +82,13 @@ int launch_plan_finish(const void* partials, const CandidateSpec& sp, int64_t n_
 int launch_plan_mppi_finish(const void* partials, double* returns, const CandidateSpec& sp, int64_t n_envs, int32_t n_cand, int32_t horizon,
                             int act_dim, double temperature, float* nominal_out, double* best_return, int32_t* best_index, double* ess,
                             hipStream_t s);
+// emei_sample_candidates_sigma: the Gaussian mode with a sigma per entry
+int launch_sample_candidates_sigma(const CandidateSpecMap& sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim, void* actions_out,
+                                   hipStream_t s);
+// the second launch of emei_plan_cem: `returns` as the plan kernel left them (overwritten by the 0 / 1 membership); sigma_map null:
+// the draws of `sp`, else those of CandidateSpecMap(sp, sigma_map)
+int launch_plan_cem_finish(const void* partials, double* returns, const CandidateSpec& sp, const float* sigma_map, int64_t n_envs,
+                           int32_t n_cand, int32_t n_elites, int32_t horizon, int act_dim, float* mean_out, float* std_out,
+                           double* best_return, int32_t* best_index, double* elite_return, hipStream_t s);
 
 }  // namespace emei

@@ -609,11 +609,12 @@ __global__ void __launch_bounds__(kBlock)
 // (wave, env) segment (plan_reduce_wave).  The step loop is the same code either way.
 // KEEP (emei_plan_mppi, with DRAWN): every lane also stores its return to ret_out[j] (8 B per candidate) for the weights of
 // plan_mppi_finish_kernel; nothing else changes, and the instantiations without it are the code they were.
-template <class Env, typename ActT, bool DRAWN = false, bool KEEP = false>
+// Spec (emei_plan_cem with a sigma_map: CandidateSpecMap, with DRAWN and KEEP): the type draw_action reads the candidate rule from.
+template <class Env, typename ActT, bool DRAWN = false, bool KEEP = false, class Spec = CandidateSpec>
 __global__ void __launch_bounds__(kBlock)
     pend_plan_kernel(const typename Env::real* state, const double* start_rows, const ActT* actions, int64_t n_envs, int32_t n_cand,
                      int32_t horizon, double discount, int freq_rate, typename Env::Params p, const SinCosEntry* trig,
-                     double* ret_out, int32_t* len_out, float4* final_obs, CandidateSpec sp, PlanPartial* partials) {
+                     double* ret_out, int32_t* len_out, float4* final_obs, Spec sp, PlanPartial* partials) {
     using R = typename Env::real;
     __shared__ SinCosEntry trig_s[kTrigTableSize];
     stage_trig_table(trig_s, trig, Env::trig_rot_c(), Env::trig_rot_s());
@@ -842,6 +843,18 @@ static int launch_env(const PendLaunch& L) {
             const R* st = (const R*)L.state;
             if (L.partials) {  // emei_plan_shooting: candidates drawn in the lanes, one partial per (wave, env) segment
                 using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
+                if (L.sigma_map) {  // emei_plan_cem with a sigma per entry: continuous envs, every return kept
+                    if constexpr (!Env::kDiscrete) {
+                        if (!L.return_out) return EMEI_ERR_INVALID;
+                        hipLaunchKernelGGL((pend_plan_kernel<Env, DrawT, true, true, CandidateSpecMap>), pgrid, dim3(kBlock), 0, L.stream, st,
+                                           L.start_rows, (const DrawT*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p,
+                                           a.trig, L.return_out, (int32_t*)nullptr, (float4*)nullptr, CandidateSpecMap(L.cand, L.sigma_map),
+                                           (PlanPartial*)L.partials);
+                        break;
+                    } else {
+                        return EMEI_ERR_INVALID;
+                    }
+                }
                 if (L.return_out) {  // emei_plan_mppi: every candidate's return is kept as well
                     hipLaunchKernelGGL((pend_plan_kernel<Env, DrawT, true, true>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
                                        (const DrawT*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p, a.trig,

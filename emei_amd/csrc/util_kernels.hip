@@ -101,8 +101,9 @@ int launch_compact_done(const unsigned long long* masks, int64_t n, int32_t* idx
 // ---------------------------------------------------------------------------------------------
 // emei_sample_candidates: lane j writes the sequence of candidate (i = j / K, k = j % K) — what the plan kernels draw in their
 // lanes (emei_device.h:draw_action) — step by step, the stores of a step contiguous over the lanes.
+template <class Spec>
 __global__ void __launch_bounds__(kBlock)
-    sample_candidates_kernel(CandidateSpec sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim, void* out, int action_dtype) {
+    sample_candidates_kernel(Spec sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim, void* out, int action_dtype) {
     const int64_t nk = n_envs * n_cand;
     const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (j >= nk) return;
@@ -233,10 +234,174 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// emei_plan_cem.  The planner's order as a 64-bit key: key(a) > key(b) <=> a comes before b whatever their k, key(a) == key(b) <=>
+// neither beats the other (+0.0 and -0.0 one key, every NaN the key 0 below -inf's 0x000f..f; the usual sign-flip map otherwise).
+__device__ __forceinline__ uint64_t plan_key(double r) {
+    if (r != r) return 0ull;
+    const uint64_t b = (uint64_t)__double_as_longlong(r + 0.0);  // -0.0 + 0.0 = +0.0
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// (k*, r*) of env i from its partials (slots w + i of the waves w its candidates lay on), as plan_finish_kernel finds them: the
+// lanes' strided pass, then the butterfly; every lane of the wave ends with the winner.  (plan_mppi_finish_kernel keeps the same lines
+// inline: called through here hipcc schedules that kernel differently, and DESIGN §4's measurements are of the code as it stands.)
+__device__ __forceinline__ void plan_winner(const PlanPartial* partials, int64_t i, int32_t n_cand, int lane, double& rs, int32_t& ks) {
+    const int64_t w0 = (i * n_cand) / kWave, w1 = ((i + 1) * n_cand - 1) / kWave;
+    rs = __builtin_nan("");  // (NaN, INT32_MAX) loses to every partial
+    ks = INT32_MAX;
+    for (int64_t w = w0 + lane; w <= w1; w += kWave) {
+        const PlanPartial p = partials[w + i];
+        if (plan_replaces(rs, ks, p.ret, p.k)) rs = p.ret, ks = p.k;
+    }
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const double r2 = __shfl_xor(rs, d, kWave);
+        const int32_t k2 = __shfl_xor(ks, d, kWave);
+        if (plan_replaces(rs, ks, r2, k2)) rs = r2, ks = k2;
+    }
+}
+
+// Second launch of emei_plan_cem, one wave per env, lane l owning the candidates k = l, l + 64, ... (plan_mppi_finish_kernel's layout):
+//   1. (k*, r*) from the env's partials, as plan_finish_kernel finds them;
+//   2. T = the key of the n_elites-th candidate in the planner's order, by an MSB-first radix select over the keys' eight bytes: a
+//      pass histograms the byte of the candidates whose higher bytes equal T's (256 LDS counters per wave, ds_add), lane l sums
+//      bins 4l .. 4l + 3, a suffix scan over the lanes finds the bin the rank falls into and the rank inside it — eight passes over
+//      the K returns (L2-resident: the plan kernel has just written them), no K^2 anywhere;
+//   3. membership, row of 64 by row of 64 in ascending k: key > T is in; of the key == T candidates the first `need` = n_elites -
+//      #{key > T} are (a ballot and a prefix popcount per row, a wave-uniform count of those taken so far), the last of them is
+//      the set's last member and gives elite_return; the lane writes 1.0 / 0.0 over the return — as MPPI's weights, read back by
+//      the lane that wrote them only;
+//   4. the moments: plan_mppi_finish_kernel's walk over the Philox blocks, the members alone redrawn, S1 = sum d and S2 = sum d^2 of
+//      d = (double)action - m0 in float64, the lane's members in ascending k, then the butterfly: a tree over k alone.
+// Every wave of the block takes the barriers of step 2 (a wave past n_envs with no candidates).
+// In place (mean_out == sp.nominal, std_out == sigma_map): entry (t, i, a) of either is read by this wave in block c >> 2 only — the
+// draws and m0 — before the block's stores, and belongs to no other wave.
+template <class Spec>
+__global__ void __launch_bounds__(kBlock)
+    plan_cem_finish_kernel(const PlanPartial* partials, double* returns, Spec sp, int64_t n_envs, int32_t n_cand, int32_t n_elites,
+                           int32_t horizon, int act_dim, float* mean_out, float* std_out, double* best_return, int32_t* best_index,
+                           double* elite_return) {
+    __shared__ uint32_t hist_s[kBlock / kWave][256];
+    const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / kWave;  // wave-uniform
+    const int lane = (int)(threadIdx.x & (kWave - 1));
+    const bool have = i < n_envs;
+    const int32_t nc = have ? n_cand : 0;
+    uint32_t* hist = hist_s[threadIdx.x / kWave];
+    double* wt = returns + (have ? i : 0) * n_cand;
+    if (have) {
+        double rs;
+        int32_t ks;
+        plan_winner(partials, i, n_cand, lane, rs, ks);
+        if (lane == 0) {
+            if (best_return) best_return[i] = rs;
+            if (best_index) best_index[i] = ks;
+        }
+    }
+    // 2. `need` = the rank looked for among the candidates whose bytes above `shift` equal `prefix`'s; there are >= need of them
+    uint64_t prefix = 0ull;
+    int32_t need = n_elites;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) hist[4 * lane + b] = 0u;
+        __syncthreads();
+        for (int32_t k = lane; k < nc; k += kWave) {
+            const uint64_t key = plan_key(wt[k]);
+            const uint64_t high = shift == 56 ? 0ull : key >> (shift + 8);
+            if (high == prefix) atomicAdd(&hist[(uint32_t)(key >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        int32_t c[4], own = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) c[b] = (int32_t)hist[4 * lane + b], own += c[b];
+        int32_t above = own;  // candidates in this lane's bins and in those of the lanes above it
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const int32_t t = __shfl_down(above, d, kWave);
+            if (lane + d < kWave) above += t;
+        }
+        above -= own;
+        const bool mine = above < need && need <= above + own;  // one lane (none in a wave without candidates)
+        int32_t digit = 0, rest = need;
+        if (mine) {
+            int32_t a = above;
+#pragma unroll
+            for (int b = 3; b >= 0; --b) {
+                if (a < need && need <= a + c[b]) digit = 4 * lane + b, rest = need - a;
+                a += c[b];
+            }
+        }
+        const unsigned long long owner = __ballot(mine);
+        const int src = owner ? __builtin_ctzll(owner) : 0;
+        digit = __shfl(digit, src, kWave), need = __shfl(rest, src, kWave);
+        prefix = (prefix << 8) | (uint64_t)(uint32_t)digit;
+        __syncthreads();  // the counters are read before the next pass clears them
+    }
+    if (!have) return;
+    // 3. prefix = T, need = how many of the key == T candidates are members (>= 1)
+    int32_t taken = 0;
+    for (int32_t k0 = 0; k0 < n_cand; k0 += kWave) {  // wave-uniform trip count: every lane takes part in the ballot
+        const int32_t k = k0 + lane;
+        const double r = k < n_cand ? wt[k] : 0.0;
+        const uint64_t key = plan_key(r);
+        const bool tie = k < n_cand && key == prefix;
+        const unsigned long long ties = __ballot(tie);
+        const int32_t rank = taken + (int32_t)__popcll(ties & ((1ull << lane) - 1ull));  // of this lane's tie among all ties, by k
+        const bool in = k < n_cand && (key > prefix || (tie && rank < need));
+        if (k < n_cand) wt[k] = in ? 1.0 : 0.0;
+        if (tie && rank == need - 1 && elite_return) elite_return[i] = r;
+        taken += (int32_t)__popcll(ties);
+    }
+    // 4.
+    const int na = act_dim > 0 ? act_dim : 1;
+    const int32_t n_comp = horizon * na;  // <= 2^31 - 1 (abi.hip:check_candidates)
+    const double m = (double)n_elites;
+    for (int32_t c0 = 0; c0 < n_comp; c0 += 4) {
+        double m0[4], s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int32_t c = min(c0 + u, n_comp - 1);  // past the end: the last component again, dropped below
+            if (act_dim == 0) m0[u] = 0.0;
+            else m0[u] = sp.nominal ? (double)sp.nominal[((int64_t)(c / na) * n_envs + i) * na + c % na] : (double)(0.5f * (sp.lo + sp.hi));
+        }
+        for (int32_t k = lane; k < n_cand; k += kWave) {
+            if (wt[k] == 0.0) continue;  // no draw for a candidate outside the set
+            CandidateWords cw(sp.seed, sp.env_offset + (uint64_t)i, (uint32_t)k);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int32_t c = min(c0 + u, n_comp - 1);
+                const double d = (double)draw_action(cw, sp, n_envs, i, c / na, c % na, act_dim) - m0[u];
+                s1[u] += d, s2[u] += d * d;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s1[u] = wave_sum_all(s1[u]), s2[u] = wave_sum_all(s2[u]);
+        if (lane == 0) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int32_t c = c0 + u;
+                if (c >= n_comp) continue;
+                const int64_t e = ((int64_t)(c / na) * n_envs + i) * na + c % na;
+                const double mu = s1[u] / m;
+                mean_out[e] = (float)(m0[u] + mu);
+                if (std_out) std_out[e] = (float)sqrt(fmax(s2[u] / m - mu * mu, 0.0));
+            }
+        }
+    }
+}
+
 int launch_sample_candidates(const CandidateSpec& sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim, void* actions_out,
                              int action_dtype, hipStream_t s) {
     dim3 grid((unsigned)((n_envs * n_cand + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(sample_candidates_kernel, grid, dim3(kBlock), 0, s, sp, n_envs, n_cand, horizon, act_dim, actions_out, action_dtype);
+    hipLaunchKernelGGL(sample_candidates_kernel<CandidateSpec>, grid, dim3(kBlock), 0, s, sp, n_envs, n_cand, horizon, act_dim, actions_out,
+                       action_dtype);
+    return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;
+}
+int launch_sample_candidates_sigma(const CandidateSpecMap& sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim, void* actions_out,
+                                   hipStream_t s) {
+    dim3 grid((unsigned)((n_envs * n_cand + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(sample_candidates_kernel<CandidateSpecMap>, grid, dim3(kBlock), 0, s, sp, n_envs, n_cand, horizon, act_dim, actions_out,
+                       (int)EMEI_ACT_F32);
     return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;
 }
 int launch_plan_finish(const void* partials, const CandidateSpec& sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim,
@@ -253,6 +418,19 @@ int launch_plan_mppi_finish(const void* partials, double* returns, const Candida
     dim3 grid((unsigned)((n_envs + kBlock / kWave - 1) / (kBlock / kWave)));
     hipLaunchKernelGGL(plan_mppi_finish_kernel, grid, dim3(kBlock), 0, s, (const PlanPartial*)partials, returns, sp, n_envs, n_cand, horizon,
                        act_dim, temperature, nominal_out, best_return, best_index, ess);
+    return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;
+}
+int launch_plan_cem_finish(const void* partials, double* returns, const CandidateSpec& sp, const float* sigma_map, int64_t n_envs,
+                           int32_t n_cand, int32_t n_elites, int32_t horizon, int act_dim, float* mean_out, float* std_out,
+                           double* best_return, int32_t* best_index, double* elite_return, hipStream_t s) {
+    dim3 grid((unsigned)((n_envs + kBlock / kWave - 1) / (kBlock / kWave)));
+    if (sigma_map)
+        hipLaunchKernelGGL(plan_cem_finish_kernel<CandidateSpecMap>, grid, dim3(kBlock), 0, s, (const PlanPartial*)partials, returns,
+                           CandidateSpecMap(sp, sigma_map), n_envs, n_cand, n_elites, horizon, act_dim, mean_out, std_out, best_return,
+                           best_index, elite_return);
+    else
+        hipLaunchKernelGGL(plan_cem_finish_kernel<CandidateSpec>, grid, dim3(kBlock), 0, s, (const PlanPartial*)partials, returns, sp, n_envs,
+                           n_cand, n_elites, horizon, act_dim, mean_out, std_out, best_return, best_index, elite_return);
     return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;
 }
 

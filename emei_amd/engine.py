@@ -315,18 +315,23 @@ class Engine:
         # [H, N, K(, act_dim)] is the rollout layout [H, N * K(, act_dim)] of N * K envs
         flat = actions.view((H, self.n_envs * K) + tuple(actions.shape[3:]))
         dt = self._check_actions_n(flat, (H,), self.n_envs * K)
-        st = None
-        if start_state is not None:
-            st = torch.as_tensor(start_state, device=self.device)
-            if st.dtype != torch.float64 or tuple(st.shape) != (self.n_envs, self.state_dim) or not st.is_contiguous():
-                raise ValueError(f"start_state must be a contiguous float64 tensor {(self.n_envs, self.state_dim)} on {self.device}; "
-                                 f"got {st.dtype} {tuple(st.shape)}")
+        st = self._start_rows(start_state)
         ret = torch.empty((self.n_envs, K), dtype=torch.float64, device=self.device)
         length = torch.empty((self.n_envs, K), dtype=torch.int32, device=self.device)
         fo = torch.empty((self.n_envs, K, self.obs_dim), dtype=torch.float32, device=self.device) if final_obs else None
         L.check(L.lib().emei_evaluate_sequences(self._h, H, K, _ptr(flat), dt, float(discount), _ptr(st), _ptr(ret), _ptr(length),
                                                 _ptr(fo), _stream()))
         return (ret, length, fo) if final_obs else (ret, length)
+
+    def _start_rows(self, start_state):
+        """validated start_state of the plan calls: None, or contiguous float64 rows [N, state_dim] on the engine's device"""
+        if start_state is None:
+            return None
+        st = torch.as_tensor(start_state, device=self.device)
+        if st.dtype != torch.float64 or tuple(st.shape) != (self.n_envs, self.state_dim) or not st.is_contiguous():
+            raise ValueError(f"start_state must be a contiguous float64 tensor {(self.n_envs, self.state_dim)} on {self.device}; "
+                             f"got {st.dtype} {tuple(st.shape)}")
+        return st
 
     # -- random-shooting planning: candidates drawn and arg-maxed on the device (emei_plan_shooting) -------------
     def _candidate_args(self, H, K, nominal, sigma, dtype):
@@ -349,12 +354,33 @@ class Engine:
                 raise ValueError("nominal on a continuous env needs sigma")
         return H, K, nominal, float(0.0 if sigma is None else sigma), dtype
 
+    def _sigma_map(self, nominal, sigma):
+        """validated per-entry sigma of sample_candidates / plan_cem: a float32 tensor of nominal's shape (continuous envs only)"""
+        if self.act_dim == 0:
+            raise ValueError("a discrete env takes no sigma tensor")
+        if nominal is None:
+            raise ValueError("a sigma tensor needs a nominal")
+        if sigma.device != self.device or sigma.dtype != torch.float32 or not sigma.is_contiguous() \
+                or sigma.numel() != nominal.numel() or sigma.dim() != nominal.dim():
+            raise ValueError(f"a sigma tensor must be a contiguous float32 tensor of nominal's shape {tuple(nominal.shape)} on "
+                             f"{self.device}; got {sigma.dtype} {tuple(sigma.shape)}")
+        return sigma
+
     @_on_device
     def sample_candidates(self, H, K, seed, nominal=None, sigma=None, dtype=None):
         """The candidate sequences plan_shooting(H, K, seed, nominal=, sigma=) draws, written out (emei_sample_candidates):
         [H, N, K(, act_dim)] in evaluate_sequences' layout.  nominal None: fair coin flips / uniform on the ctrlrange; else float32
         [H, N] Bernoulli probabilities (discrete) or [H, N, act_dim] means of clipped Gaussians with `sigma` (continuous).
+        sigma: a float, or a float32 tensor of nominal's shape with one sigma per entry (emei_sample_candidates_sigma: what
+        plan_cem(sigma=tensor) draws; an entry of 0 gives the clipped mean).
         dtype: uint8 / int32 / int64 (discrete; the default int64) or float32."""
+        if isinstance(sigma, torch.Tensor):
+            H, K, nominal, _, dtype = self._candidate_args(H, K, nominal, 1.0, dtype)
+            sigma = self._sigma_map(nominal, sigma)
+            out = torch.empty((H, self.n_envs, K) + ((self.act_dim,) if self.act_dim > 1 else ()), dtype=dtype, device=self.device)
+            L.check(L.lib().emei_sample_candidates_sigma(self._h, H, K, int(seed) & (2**64 - 1), _ptr(nominal), _ptr(sigma), _ptr(out),
+                                                         _ACT_DTYPES[dtype], _stream()))
+            return out
         H, K, nominal, sigma, dtype = self._candidate_args(H, K, nominal, sigma, dtype)
         shape = (H, self.n_envs, K) + ((self.act_dim,) if self.act_dim > 1 else ())
         out = torch.empty(shape, dtype=dtype, device=self.device)
@@ -371,12 +397,7 @@ class Engine:
         [, best_length int32 [N]]): the first maximum of evaluate_sequences(sample_candidates(...)) per env, NaN returns below
         everything.  The handle is left as it is.  Arguments as sample_candidates."""
         H, K, nominal, sigma, dtype = self._candidate_args(H, K, nominal, sigma, dtype)
-        st = None
-        if start_state is not None:
-            st = torch.as_tensor(start_state, device=self.device)
-            if st.dtype != torch.float64 or tuple(st.shape) != (self.n_envs, self.state_dim) or not st.is_contiguous():
-                raise ValueError(f"start_state must be a contiguous float64 tensor {(self.n_envs, self.state_dim)} on {self.device}; "
-                                 f"got {st.dtype} {tuple(st.shape)}")
+        st = self._start_rows(start_state)
         need = int(L.lib().emei_plan_shooting_workspace_bytes(self.n_envs, K))
         if need < 0:
             L.check(need)
@@ -405,23 +426,12 @@ class Engine:
         into; it may be `nominal` itself (in place).  The handle is left as it is.  Other arguments as sample_candidates."""
         H, K, nominal, sigma, _ = self._candidate_args(H, K, nominal, sigma, None)
         temperature = float(temperature)
-        st = None
-        if start_state is not None:
-            st = torch.as_tensor(start_state, device=self.device)
-            if st.dtype != torch.float64 or tuple(st.shape) != (self.n_envs, self.state_dim) or not st.is_contiguous():
-                raise ValueError(f"start_state must be a contiguous float64 tensor {(self.n_envs, self.state_dim)} on {self.device}; "
-                                 f"got {st.dtype} {tuple(st.shape)}")
+        st = self._start_rows(start_state)
         shape = (H, self.n_envs) + ((self.act_dim,) if self.act_dim > 1 else ())
         if out is None:
             out = torch.empty(shape if nominal is None else tuple(nominal.shape), dtype=torch.float32, device=self.device)
         else:
-            if not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous() \
-                    or not (tuple(out.shape) == shape or (self.act_dim == 1 and tuple(out.shape) == (H, self.n_envs, 1))):
-                raise ValueError(f"out must be a contiguous float32 tensor {shape} on {self.device}")
-            if nominal is not None and out.data_ptr() != nominal.data_ptr():
-                lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * 4
-                if lo < nominal.data_ptr() + nominal.numel() * 4 and nominal.data_ptr() < hi:
-                    raise ValueError("out may be nominal itself, not a tensor that overlaps it partly")
+            self._check_plan_out("out", out, shape, nominal, "nominal")
         need = int(L.lib().emei_plan_mppi_workspace_bytes(self.n_envs, K))
         if need < 0:
             L.check(need)
@@ -434,6 +444,64 @@ class Engine:
         L.check(L.lib().emei_plan_mppi(self._h, H, K, int(seed) & (2**64 - 1), _ptr(nominal), sigma, float(discount), temperature,
                                        _ptr(st), _ptr(ws), _ptr(out), _ptr(ret), _ptr(idx), _ptr(es), _stream()))
         return (out, ret, idx) + ((es,) if ess else ())
+
+    def _check_plan_out(self, name, out, shape, source, source_name):
+        """an output tensor of plan_mppi / plan_cem: float32 [H, N(, act_dim)], `source` itself (in place) or clear of it"""
+        if not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous() \
+                or not (tuple(out.shape) == shape or (self.act_dim == 1 and tuple(out.shape) == shape + (1,))):
+            raise ValueError(f"{name} must be a contiguous float32 tensor {shape} on {self.device}")
+        if source is not None and out.data_ptr() != source.data_ptr():
+            lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * 4
+            if lo < source.data_ptr() + source.numel() * 4 and source.data_ptr() < hi:
+                raise ValueError(f"{name} may be {source_name} itself, not a tensor that overlaps it partly")
+
+    @_on_device
+    def plan_cem(self, H, K, n_elites, seed, discount=1.0, nominal=None, sigma=None, start_state=None, out=None, out_sigma=None,
+                 elite_return=False):
+        """One cross-entropy-method iteration in two launches (emei_plan_cem): the K candidates per env that plan_shooting(H, K, seed,
+        nominal=, sigma=) scores are scored the same way, the n_elites best per env — the planner's order: higher return first, NaN
+        last, ties to the lower index — are selected on the device, redrawn and their mean and population standard deviation taken.
+        sigma: a float, or a float32 tensor of nominal's shape (one sigma per entry: the std of the previous iteration).
+        -> (mean float32 [H, N(, act_dim)], std (the same shape; None for the discrete envs, whose mean is a Bernoulli probability),
+        best_return float64 [N], best_index int32 [N][, elite_return float64 [N]: the return of the last candidate admitted]).
+        out / out_sigma: float32 tensors to write mean / std into; they may be `nominal` / the sigma tensor themselves (in place).
+        The handle is left as it is.  Other arguments as sample_candidates."""
+        sigma_map = None
+        if isinstance(sigma, torch.Tensor):
+            H, K, nominal, _, _ = self._candidate_args(H, K, nominal, 1.0, None)
+            sigma_map, sigma = self._sigma_map(nominal, sigma), 0.0
+        else:
+            H, K, nominal, sigma, _ = self._candidate_args(H, K, nominal, sigma, None)
+        n_elites = int(n_elites)
+        if not 1 <= n_elites <= K:
+            raise ValueError(f"n_elites={n_elites} is outside [1, n_candidates={K}]")
+        st = self._start_rows(start_state)
+        shape = (H, self.n_envs) + ((self.act_dim,) if self.act_dim > 1 else ())
+        like = shape if nominal is None else tuple(nominal.shape)
+        if out is None:
+            out = torch.empty(like, dtype=torch.float32, device=self.device)
+        else:
+            self._check_plan_out("out", out, shape, nominal, "nominal")
+        if self.act_dim == 0:
+            if out_sigma is not None:
+                raise ValueError("a discrete env has no standard deviation: out_sigma must be None")
+        elif out_sigma is None:
+            out_sigma = torch.empty(like, dtype=torch.float32, device=self.device)
+        else:
+            self._check_plan_out("out_sigma", out_sigma, shape, sigma_map, "the sigma tensor")
+        need = int(L.lib().emei_plan_cem_workspace_bytes(self.n_envs, K))
+        if need < 0:
+            L.check(need)
+        ws = getattr(self, "_cem_ws", None)
+        if ws is None or ws.numel() * 8 < need:  # grow-only (float64 elements: 8-byte aligned records)
+            ws = self._cem_ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+        ret = torch.empty(self.n_envs, dtype=torch.float64, device=self.device)
+        idx = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+        er = torch.empty(self.n_envs, dtype=torch.float64, device=self.device) if elite_return else None
+        L.check(L.lib().emei_plan_cem(self._h, H, K, n_elites, int(seed) & (2**64 - 1), _ptr(nominal), sigma, _ptr(sigma_map),
+                                      float(discount), _ptr(st), _ptr(ws), _ptr(out), _ptr(out_sigma), _ptr(ret), _ptr(idx), _ptr(er),
+                                      _stream()))
+        return (out, out_sigma, ret, idx) + ((er,) if elite_return else ())
 
     @_on_device
     def capture_step_graph(self, actions, auto_reset=False):

@@ -346,6 +346,39 @@ class HipEnv(EmeiEnv):
                             out=out, ess=ess)
         return tuple(t.cpu().numpy() for t in res) if as_numpy else res
 
+    def plan_cem(self, horizon, n_candidates, n_elites, seed, discount=1.0, nominal=None, sigma=None, start_state=None, iterations=1,
+                 elite_return=False):
+        """The cross-entropy method's refit of a sampling distribution over action sequences, two launches per iteration
+        (Engine.plan_cem, ABI emei_plan_cem): iteration j draws the candidates of plan_random_shooting(horizon, n_candidates,
+        seed + j, nominal=mean, sigma=std), scores them as there, and replaces (mean, std) by the mean and the population standard
+        deviation of the n_elites best per env —
+        (mean float32 [horizon, num_envs(, act_dim)], std of the same shape (None for the discrete envs: mean is a Bernoulli
+        probability), best_return float64 [num_envs], best_index int32 [num_envs][, elite_return float64 [num_envs]]) of the LAST
+        iteration.  nominal / sigma: the first iteration's distribution — sigma a float or an array of nominal's shape; None / None:
+        fair coins / uniform on the action space.  They are copied, the caller's arrays are not written.  A NumPy `nominal`, `sigma`
+        or `start_state` gives NumPy arrays; otherwise tensors.  The env's state is left as it is."""
+        import torch
+
+        assert self.state is not None, "Call reset before using step method."  # base_control.py:67
+        if int(iterations) < 1:
+            raise ValueError(f"iterations={iterations} must be >= 1")
+        eng = self.engine
+        as_numpy = any(isinstance(x, np.ndarray) for x in (nominal, sigma, start_state))
+
+        def own(x, dtype):  # a device copy the iterations may write
+            x = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+            return x.to(device=eng.device, dtype=dtype).contiguous().clone()
+
+        mean = None if nominal is None else own(nominal, torch.float32)
+        std = own(sigma, torch.float32) if isinstance(sigma, (torch.Tensor, np.ndarray)) else sigma
+        st = None if start_state is None else own(start_state, torch.float64)
+        for j in range(int(iterations)):
+            res = eng.plan_cem(horizon, n_candidates, n_elites, int(seed) + j, discount=discount, nominal=mean, sigma=std,
+                               start_state=st, out=mean, out_sigma=std if isinstance(std, torch.Tensor) else None,
+                               elite_return=elite_return)
+            mean, std = res[0], res[1]
+        return tuple(None if t is None else t.cpu().numpy() for t in res) if as_numpy else res
+
 
 def joint_sigmas(params, nq):
     """init_noise_params / obs_noise_params -> (pos sigma [nq], vel sigma [nq]) per (1-dof) joint:

@@ -38,7 +38,10 @@ extern "C" {
  *    Additive under 8 (no existing prototype or struct changes): emei_plan_shooting_workspace_bytes, emei_sample_candidates,
  *    emei_plan_shooting (random-shooting planning with the candidates drawn and arg-maxed on the device);
  *    emei_plan_mppi_workspace_bytes, emei_plan_mppi (the MPPI update of a nominal sequence: the return-weighted mean of the same
- *    candidates, redrawn on the device). */
+ *    candidates, redrawn on the device);
+ *    emei_sample_candidates_sigma (the Gaussian candidates with a sigma per entry), emei_plan_cem_workspace_bytes, emei_plan_cem
+ *    (one cross-entropy-method iteration: exact per-env selection of the n_elites best candidates on the device, their mean and
+ *    standard deviation). */
 #define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
@@ -325,6 +328,10 @@ EMEI_API int emei_evaluate_sequences(emei_env* h, int32_t horizon, int32_t n_can
  *       (the kernels' model constants: +-3 for the InvertedPendulum family, +-1 otherwise)
  *   continuous, nominal = float32 [horizon, n_envs, act_dim] means: c = t * act_dim + a, q = c >> 1, (z0, z1) = the reset
  *       generator's Box-Muller of (W[2q], W[2q + 1]), z = (c & 1) ? z1 : z0, action = min(max(fmaf((float)sigma, z, mean), lo), hi)
+ *   continuous, nominal and a sigma_map = float32 [horizon, n_envs, act_dim] in nominal's layout (emei_sample_candidates_sigma,
+ *       emei_plan_cem): the same z, action = min(max(fmaf(sigma_map[t, i, a], z, mean), lo), hi) — the map replaces the scalar.  An
+ *       entry of 0 is legal and gives the clipped mean itself.  Negative or non-finite entries are the caller's error: the result for
+ *       that env is unspecified, the call does not fault.
  *
  * emei_sample_candidates writes them out, actions_out [horizon, n_envs, n_candidates(, act_dim)] in emei_evaluate_sequences'
  * layout and in action_dtype (U8 / I32 / I64 for the discrete envs, F32 for the continuous ones): for tests and for callers that
@@ -401,6 +408,57 @@ EMEI_API int64_t emei_plan_mppi_workspace_bytes(int64_t n_envs, int32_t n_candid
 EMEI_API int emei_plan_mppi(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal, double sigma,
                             double discount, double temperature, const double* start_state, void* workspace, float* nominal_out,
                             double* best_return_out, int32_t* best_index_out, double* ess_out, void* stream);
+
+/* emei_sample_candidates for the Gaussian mode with a sigma per entry (the sigma_map clause of the candidate specification above):
+ * actions_out float32 [horizon, n_envs, n_candidates, act_dim].  emei_sample_candidates' checks, and EMEI_ERR_INVALID for a NULL
+ * nominal, a NULL sigma_map, or a discrete env. */
+EMEI_API int emei_sample_candidates_sigma(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal,
+                                          const float* sigma_map, void* actions_out, int action_dtype, void* stream);
+
+/* One iteration of the cross-entropy method on the true dynamics (the planner of PETS / PlaNet-style MPC; the planner-side use of
+ * the query core.py:18-37,190-193 serves): the sampling distribution (nominal, sigma) is refitted to the n_elites best of the
+ * candidates emei_plan_shooting would score.  The elites are selected exactly and per env on the device and redrawn, so nothing of
+ * size horizon * n_envs * n_candidates is ever stored (8 bytes per candidate are, in the workspace).
+ *
+ * Candidates, start-state rule, per-step arithmetic, return r_k = ret(i, k) and (k*, r*) are exactly emei_plan_shooting's for the
+ * same (seed, nominal, sigma, discount, start_state); with a sigma_map, those of the sigma_map clause of the candidate
+ * specification (nominal required, the scalar sigma ignored).
+ *
+ * The elite set (normative).  Per env i the n_candidates candidates are sorted by the planner's order: a comes before b if
+ * ret_a > ret_b, or if ret_b is NaN and ret_a is not; otherwise the lower k comes first.  So +0.0 and -0.0 tie, all NaNs tie with
+ * each other and come last, +-inf are ordinary values.  E_i is the first n_elites candidates of that sequence; it depends on the
+ * returns and on k only — not on waves, blocks, n_envs or the shard.  (k*, r*) is its first member.
+ *
+ * The moments (normative), float64, a_k the float32 value of the candidate specification:
+ *   discrete envs    mean_out[t, i] = (float)(sum_{k in E} a_k / n_elites), a_k in {0, 1}: a Bernoulli probability, the next call's
+ *                    nominal.  std_out and sigma_map must be NULL, sigma is ignored.
+ *   continuous envs  m0 = (double)nominal[t, i, a], or (double)(0.5f * (lo + hi)) with nominal NULL; d_k = (double)a_k - m0,
+ *                    S1 = sum_{k in E} d_k, S2 = sum_{k in E} d_k^2 (the shifted one-pass form: meaningful when sigma has collapsed),
+ *                    mean_out[t, i, a] = (float)(m0 + S1 / n_elites)
+ *                    std_out[t, i, a]  = (float)sqrt(max(S2 / n_elites - (S1 / n_elites)^2, 0))   the population value; may be NULL
+ *   Summation tree: emei_plan_mppi's — the members k = l mod 64 in ascending k, then a butterfly over the lanes l, distances 1, 2, .., 32 — a function
+ *   of k alone, so repeated calls, graph replays and different shardings give the same bits (up to the lane dependence of r_k the
+ *   HalfCheetah documents).
+ * Outputs: mean_out, std_out float32 [horizon, n_envs(, act_dim)] in nominal's layout; mean_out may be the same pointer as nominal and
+ * std_out the same pointer as sigma_map (in place: entry (t, i, a) of either is read before it is written, by env i's wave only); any
+ * other overlap is undefined.
+ *   best_index_out[i], best_return_out[i]  k*, r*: bit-identical to emei_plan_shooting's (either may be NULL)
+ *   elite_return_out[i]                    the return of the LAST member of E_i, float64: the admission threshold; NaN if NaN returns
+ *                                          had to be admitted (NULL: skipped)
+ * workspace: emei_plan_cem_workspace_bytes(n_envs, n_candidates) bytes of device memory, 16-byte aligned, contents irrelevant before
+ * and after (at least emei_plan_mppi's).
+ * EMEI_ERR_INVALID before any HIP call, scalars first: horizon < 1, n_candidates < 1, n_elites < 1 or > n_candidates, discount outside
+ * (0, 1]; then a NULL handle; emei_plan_shooting's candidate checks (with a nominal and no sigma_map on a continuous env, sigma finite
+ * and > 0; n_envs * n_candidates; horizon * act_dim); a sigma_map without a nominal; a sigma_map or a std_out on a discrete env; NULL
+ * workspace or mean_out.  EMEI_ERR_STATE without a state.  The handle is untouched.  Neither allocates nor synchronises (capturable).
+ * Newton solves that end at the iteration cap count into emei_get_solver_cap_hits. */
+/* bytes of device scratch emei_plan_cem needs for this shape; host only, no handle, no HIP call.
+ * Negative (EMEI_ERR_INVALID) where emei_plan_mppi_workspace_bytes is. */
+EMEI_API int64_t emei_plan_cem_workspace_bytes(int64_t n_envs, int32_t n_candidates);
+EMEI_API int emei_plan_cem(emei_env* h, int32_t horizon, int32_t n_candidates, int32_t n_elites, uint64_t seed, const float* nominal,
+                           double sigma, const float* sigma_map, double discount, const double* start_state, void* workspace,
+                           float* mean_out, float* std_out, double* best_return_out, int32_t* best_index_out,
+                           double* elite_return_out, void* stream);
 
 /* Which kernel the LAST emei_step / emei_rollout of this handle launched (enum emei_kernel_id): a debug /
  * test getter, so that a parity test can assert that the path it checked is the path bench.py times. */
