@@ -949,6 +949,68 @@ extern "C" EMEI_API int emei_plan_cem(emei_env* h, int32_t horizon, int32_t n_ca
     return rc == EMEI_OK ? rc : fail(rc, "emei_plan_cem: launch failed (%s)", hipGetErrorString(hipGetLastError()));
 }
 
+// ---------------------------------------------------------------------------------------------
+// emei_mpc_mppi: n_steps control steps of "emei_plan_mppi, act, emei_step, shift" in one kernel of one wave per env
+// (pendulum_kernels.h:pend_mpc_mppi_kernel), then the done mask packed by a small second launch.
+extern "C" EMEI_API int64_t emei_mpc_mppi_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
+    const char* fn = "emei_mpc_mppi_workspace_bytes";
+    if (n_envs < 1 || n_envs > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs=%lld", fn, (long long)n_envs);
+    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "%s: n_candidates=%d < 1", fn, n_candidates);
+    const int64_t nk = n_envs * (int64_t)n_candidates;
+    if (nk > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs * n_candidates = %lld exceeds 2^31 - 1", fn, (long long)nk);
+    return (int64_t)sizeof(double) * nk;  // every candidate's return, then its weight
+}
+
+extern "C" EMEI_API int emei_mpc_mppi(emei_env* h, int32_t n_steps, int32_t horizon, int32_t n_candidates, uint64_t seed, float* nominal,
+                                      double sigma, double discount, double temperature, float refill, float nominal_lo,
+                                      float nominal_hi, void* workspace, void* actions_out, int action_dtype, float* obs_out,
+                                      float* reward_out, uint8_t* done_out, double* plan_return_out, double* ess_out, uint32_t flags,
+                                      void* stream) {
+    if (n_steps < 1) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: n_steps=%d < 1", n_steps);
+    if (horizon < 1) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: horizon=%d < 1", horizon);
+    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: n_candidates=%d < 1", n_candidates);
+    if (!(discount > 0.0 && discount <= 1.0)) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: discount=%g is outside (0, 1]", discount);
+    if (!(std::isfinite(temperature) && temperature > 0.0))
+        return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: temperature=%g must be finite and > 0", temperature);
+    if (!std::isfinite(refill)) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: refill=%g must be finite", (double)refill);
+    if (!(nominal_lo <= nominal_hi))  // also refuses a NaN bound
+        return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: nominal_lo=%g, nominal_hi=%g: need nominal_lo <= nominal_hi", (double)nominal_lo,
+                    (double)nominal_hi);
+    if (horizon > EMEI_MPC_MAX_HORIZON)
+        return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: horizon=%d exceeds EMEI_MPC_MAX_HORIZON=%d (the nominal lives in LDS)", horizon,
+                    EMEI_MPC_MAX_HORIZON);
+    CandidateSpec sp{};
+    sp.seed = seed;
+    // the call always plans around a nominal, so sigma always counts: the shared check sees a non-null one even before the
+    // call's own NULL check below (it dereferences nothing)
+    if (int rc = check_candidates("emei_mpc_mppi", h, horizon, n_candidates, nominal ? nominal : &refill, sigma, action_dtype, sp)) return rc;
+    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: unknown flags 0x%x", flags);
+    if (!nominal) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: null nominal");
+    if (!workspace) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: null workspace");
+    if (!actions_out) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: null actions_out");
+    EMEI_ON_DEVICE(h, "emei_mpc_mppi");
+    if (!h->has_state) return fail(EMEI_ERR_STATE, "emei_mpc_mppi: call reset before using the state");
+    if (steps_as_body(h->cfg))
+        return fail(EMEI_ERR_UNSUPPORTED, "emei_mpc_mppi: this handle steps on the body kernels (a multi-body env, or an InvertedPendulum with "
+                                          "a non-euler integrator or observation noise); the fused controller serves the 4-state kernels only");
+    if (h->peers.count > 0)
+        return fail(EMEI_ERR_UNSUPPORTED, "emei_mpc_mppi: observation peers are set (emei_set_obs_peers), which this kernel does not serve");
+    PendLaunch L = pend_base(h, stream);
+    L.op = PEND_OP_MPC;
+    L.n_steps = n_steps, L.horizon = horizon, L.n_candidates = n_candidates, L.discount = discount, L.temperature = temperature;
+    L.cand = sp, L.cand.nominal = nullptr;
+    L.mpc_nominal = nominal, L.return_out = (double*)workspace;
+    L.mpc_actions_out = actions_out, L.action_dtype = action_dtype;
+    L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
+    L.plan_return_out = plan_return_out, L.ess_out = ess_out;
+    L.refill = refill, L.nominal_lo = nominal_lo, L.nominal_hi = nominal_hi;
+    L.flags = flags;
+    L.selected = &h->last_kernel;
+    int rc = pend_launch(L);
+    if (rc == EMEI_OK) rc = launch_mpc_done_pack((const double*)workspace, n_candidates, h->cfg.n_envs, h->done_mask, (hipStream_t)stream);
+    return rc == EMEI_OK ? rc : fail(rc, "emei_mpc_mppi: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+}
+
 extern "C" EMEI_API int emei_compact_done(emei_env* h, int32_t* idx_out, int32_t* count_out, void* stream) {
     if (!h || !idx_out || !count_out) return fail(EMEI_ERR_INVALID, "emei_compact_done: null argument");
     EMEI_ON_DEVICE(h, "emei_compact_done");

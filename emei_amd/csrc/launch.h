@@ -7,7 +7,7 @@
 
 namespace emei {
 
-enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN };
+enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC };
 
 // emei_set_obs_peers: the gathered buffers the staged rollout kernel also writes every observation row to
 struct ObsPeers {
@@ -60,6 +60,16 @@ struct PendLaunch {
     CandidateSpec cand = {};
     void* partials = nullptr;
     const float* sigma_map = nullptr;  // emei_plan_cem: non-null -> the draws take their sigma per entry (CandidateSpecMap)
+    // PEND_OP_MPC (emei_mpc_mppi): n_steps control steps of MPPI with n_candidates candidates over `horizon` steps; `cand` carries the
+    // call's seed, sigma and the ctrlrange (its nominal is unused: the kernel keeps the nominal in LDS), `seed` the handle's reset key;
+    // return_out = the workspace [n * K], actions / obs_out / reward_out / done_out as PEND_OP_ROLLOUT's outputs
+    int32_t horizon = 1;
+    float* mpc_nominal = nullptr;  // in/out [horizon, n(, act_dim)]
+    void* mpc_actions_out = nullptr;
+    double* plan_return_out = nullptr;  // [n_steps, n] or null
+    double* ess_out = nullptr;          // [n_steps, n] or null
+    double temperature = 1.0;
+    float refill = 0.f, nominal_lo = 0.f, nominal_hi = 0.f;
 };
 
 // pendulum_kernels.hip
@@ -72,6 +82,8 @@ const void* emei_trig_table(int device);
 int launch_state_unpack(const double* aos, void* soa, int precision, int64_t n, int dim, hipStream_t s);
 int launch_state_pack(const void* soa, double* aos, int precision, int64_t n, int dim, hipStream_t s);
 int launch_compact_done(const unsigned long long* masks, int64_t n, int32_t* idx_out, int32_t* count_out, hipStream_t s);
+// emei_mpc_mppi's follow-up: env i's last done code (word 0 of its workspace row of `stride` doubles) -> one ballot word per 64 envs
+int launch_mpc_done_pack(const double* work, int64_t stride, int64_t n, unsigned long long* done_mask, hipStream_t s);
 // emei_sample_candidates / the second launch of emei_plan_shooting (act_dim 0: a discrete env)
 int launch_sample_candidates(const CandidateSpec& sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim, void* actions_out,
                              int action_dtype, hipStream_t s);

@@ -684,6 +684,232 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // ---------------------------------------------------------------------------------------------
+// emei_mpc_mppi: receding-horizon MPPI control episodes in ONE launch (the normative text: include/emei_hip.h).
+// draw_action's Spec with the nominal in LDS: the wave's own slice [horizon(, act_dim)], indexed as a one-env nominal
+// (draw_action is called with n_envs = 1, i = 0).  A type of its own: the CandidateSpec / CandidateSpecMap instantiations are
+// the code they were.
+// The slice may sit at LDS address 0, which IS the null pointer of that address space: draw_action's "is there a nominal" tests must not
+// look at the address (the first wave of a block would draw as if it had no nominal), hence a type that is always "there".
+struct LdsNominal {
+    const __attribute__((address_space(3))) float* p;
+    __device__ __forceinline__ explicit operator bool() const { return true; }
+    __device__ __forceinline__ float operator[](int64_t idx) const { return p[idx]; }
+};
+struct CandidateSpecLds {
+    static constexpr bool kSigmaMap = false;
+    uint64_t seed, env_offset;
+    LdsNominal nominal;
+    float sigma, lo, hi;
+};
+
+template <class Env>
+struct MpcArgs {
+    typename Env::real* state;  // SoA: 4 arrays of n
+    int32_t* steps;
+    uint32_t* episode;
+    const SinCosEntry* trig;
+    float* nominal;  // in/out [horizon, n(, act_dim)]
+    double* work;    // [n, n_cand] returns, then weights; word 0 of env i's row ends as its last done code (mpc_done_pack_kernel)
+    void* actions_out;
+    float4* obs_out;
+    float* reward_out;
+    uint8_t* done_out;
+    double* plan_return_out;
+    double* ess_out;
+    int64_t n;
+    int32_t n_steps, horizon, n_cand, freq_rate, action_dtype, max_episode_steps;
+    uint32_t flags;
+    uint64_t reset_seed, env_offset, seed;
+    double discount, temperature;
+    float sigma, lo, hi, refill, nominal_lo, nominal_hi;
+    typename Env::Params p;
+};
+
+// One WAVE per env, for all n_steps control steps; lane l owns the candidates k = l, l + 64, ... (plan_mppi_finish_kernel's layout,
+// so the summation tree is that kernel's by construction).  Per control step:
+//   1. the lanes clamp the nominal (the wave's LDS slice);
+//   2. every lane scores its candidates with pend_plan_kernel's DRAWN loop from the register copy of the env's real state
+//      (ret = ret + g * (double)(float)rew in step order; the wave leaves a pass once a ballot finds no lane live), keeps the
+//      return in `work` (8 B per candidate: no cap on n_candidates; a lane reads back only what it wrote) and folds (k*, r*) in
+//      ascending k, then over the lanes — the planner's order is total, so this is plan_finish_kernel's winner;
+//   3. weights, Z, the effective sample size and the weighted mean are plan_mppi_finish_kernel's lines, copied rather than shared
+//      (that kernel's comment: it must not be rescheduled); lane 0 writes the new nominal into LDS;
+//   4. the first entry is the action; the real state — wave-uniform values in registers, computed redundantly by every lane —
+//      takes emei_step's step (the carry primed from the state, as a launch of its own would), TimeLimit and auto-reset as
+//      pend_rollout_kernel; lane 0 stores the step's outputs.  Those stores are small and uncoalesced, which is accepted: this
+//      path is bound by the latency of one wave's dependent arithmetic, not by HBM;
+//   5. the nominal is shifted (or refilled after a reset).
+// The nominal is read from global memory once and written back once.  stage_trig_table's block barrier is taken by every wave,
+// also by those past n; after it the waves of a block run different trip counts, so there is NO block barrier: what lane 0
+// writes into LDS reaches the other lanes through wave_lds_fence().
+template <class Env>
+__global__ void __launch_bounds__(kBlock) pend_mpc_mppi_kernel(const MpcArgs<Env> a) {
+    using R = typename Env::real;
+    using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
+    constexpr int kWavesPerBlock = kBlock / kWave;
+    constexpr int na = Env::kActDim;                          // components per step of the nominal
+    constexpr int act_dim = Env::kDiscrete ? 0 : Env::kActDim;  // draw_action's: 0 = coin flips
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    __shared__ float nom_s[kWavesPerBlock][EMEI_MPC_MAX_HORIZON * na];
+    stage_trig_table(trig_s, a.trig, Env::trig_rot_c(), Env::trig_rot_s());
+    const int lane = (int)(threadIdx.x & (kWave - 1));
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    const int64_t i = (int64_t)blockIdx.x * kWavesPerBlock + wv;  // wave-uniform
+    if (i >= a.n) return;
+    const int64_t n = a.n;
+    const int32_t n_cand = a.n_cand, horizon = a.horizon;
+    const int32_t n_comp = horizon * na;  // <= EMEI_MPC_MAX_HORIZON * na (abi.hip)
+    float* nom = nom_s[wv];
+    for (int32_t c = lane; c < n_comp; c += kWave) nom[c] = a.nominal[((int64_t)(c / na) * n + i) * na + c % na];
+
+    R s[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = a.state[k * n + i];
+    int32_t steps = a.steps[i];
+    uint32_t episode = a.episode[i];
+    typename Env::Carry c;
+    trig_ctx_init(c.trig, trig_s);
+    const bool auto_reset = (a.flags & EMEI_FLAG_AUTO_RESET) != 0;
+    const uint64_t g = a.env_offset + (uint64_t)i;
+    double* wt = a.work + i * n_cand;
+    CandidateSpecLds sp;
+    sp.env_offset = a.env_offset;
+    sp.nominal.p = (const __attribute__((address_space(3))) float*)nom;
+    sp.sigma = a.sigma, sp.lo = a.lo, sp.hi = a.hi;
+    uint32_t done = 0;
+
+    for (int32_t t = 0; t < a.n_steps; ++t) {
+        // 1.
+        for (int32_t cc = lane; cc < n_comp; cc += kWave) nom[cc] = fminf(fmaxf(nom[cc], a.nominal_lo), a.nominal_hi);
+        wave_lds_fence();
+        // 2.
+        sp.seed = a.seed + (uint64_t)t;
+        Env::prime(s, c, a.p);
+        double rs = __builtin_nan("");  // (NaN, INT32_MAX) loses to every candidate
+        int32_t ks = INT32_MAX;
+        for (int32_t k0 = 0; k0 < n_cand; k0 += kWave) {  // wave-uniform trip count: every lane takes part in the ballot
+            const int32_t k = k0 + lane;
+            R cs[4] = {s[0], s[1], s[2], s[3]};
+            typename Env::Carry cc = c;
+            CandidateWordsT<true> cw(sp.seed, g, (uint32_t)k);
+            double ret = 0.0, gd = 1.0;
+            bool live = k < n_cand;
+            for (int32_t h = 0; h < horizon; ++h) {
+                R o[4], rew;
+                bool term;
+                const DrawT act = (DrawT)draw_action(cw, sp, 1, 0, h, 0, act_dim);
+                Env::step(cs, cc, Env::decode_t(act), a.p, a.freq_rate, o, rew, term);
+                if (live) {
+                    ret = ret + gd * (double)(float)rew;
+                    gd = gd * a.discount;
+                    if (term) live = false;
+                }
+                if (__ballot(live) == 0ull) break;  // wave-uniform
+            }
+            if (k < n_cand) {
+                wt[k] = ret;
+                if (plan_replaces(rs, ks, ret, k)) rs = ret, ks = k;
+            }
+        }
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const double r2 = __shfl_xor(rs, d, kWave);
+            const int32_t k2 = __shfl_xor(ks, d, kWave);
+            if (plan_replaces(rs, ks, r2, k2)) rs = r2, ks = k2;
+        }
+        // 3.
+        double z = 0.0, z2 = 0.0;
+        for (int32_t k = lane; k < n_cand; k += kWave) {
+            const double r = wt[k];
+            const double e = exp((r - rs) / a.temperature);  // r < r*: the argument is negative, -inf included
+            const double w = rs != rs ? 1.0 : (r != r ? 0.0 : (r == rs ? 1.0 : e));
+            wt[k] = w;
+            z += w, z2 += w * w;
+        }
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) z += __shfl_xor(z, d, kWave);
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) z2 += __shfl_xor(z2, d, kWave);
+        if (lane == 0) {
+            if (a.plan_return_out) a.plan_return_out[(int64_t)t * n + i] = rs;
+            if (a.ess_out) a.ess_out[(int64_t)t * n + i] = z * z / z2;
+        }
+        for (int32_t c0 = 0; c0 < n_comp; c0 += 4) {
+            double acc[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int32_t k = lane; k < n_cand; k += kWave) {
+                const double w = wt[k];
+                CandidateWordsT<true> cw(sp.seed, g, (uint32_t)k);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int32_t cc = min(c0 + u, n_comp - 1);  // past the end: the last component again, dropped below
+                    const float v = draw_action(cw, sp, 1, 0, cc / na, cc % na, act_dim);
+                    acc[u] += w * (double)v;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+#pragma unroll
+                for (int d = 1; d < kWave; d <<= 1) acc[u] += __shfl_xor(acc[u], d, kWave);
+            }
+            wave_lds_fence();  // every lane's draws of this block have read the entries lane 0 now replaces
+            if (lane == 0) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int32_t cc = c0 + u;
+                    if (cc < n_comp) nom[cc] = (float)(acc[u] / z);
+                }
+            }
+        }
+        wave_lds_fence();  // lane 0's nominal is what every lane reads from here on
+        // 4.
+        float av[na];
+#pragma unroll
+        for (int q = 0; q < na; ++q) {
+            av[q] = nom[q];
+            if constexpr (Env::kDiscrete) av[q] = av[q] >= 0.5f ? 1.f : 0.f;
+            if (lane == 0) store_action(a.actions_out, a.action_dtype, ((int64_t)t * n + i) * na + q, av[q]);
+        }
+        {
+            R o[4], rew;
+            bool term;
+            Env::step(s, c, Env::decode_t((DrawT)av[0]), a.p, a.freq_rate, o, rew, term);
+            ++steps;
+            const bool trunc = (a.max_episode_steps > 0) & (steps >= a.max_episode_steps);
+            done = (term ? EMEI_DONE_TERMINAL : 0u) | (trunc ? EMEI_DONE_TRUNCATED : 0u);
+            if (lane == 0) {
+                const int64_t at = (int64_t)t * n + i;
+                if (a.obs_out) a.obs_out[at] = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
+                if (a.reward_out) a.reward_out[at] = (float)rew;
+                if (a.done_out) a.done_out[at] = (uint8_t)done;
+            }
+        }
+        const bool reset_now = auto_reset && __builtin_amdgcn_readfirstlane(done) != 0u;  // wave-uniform
+        if (reset_now) {
+            ++episode;
+            steps = 0;
+            Env::init(s, a.reset_seed, g, episode, a.p);
+        }
+        // 5. pass by pass in ascending order: a pass reads [base + na, base + 64 + na) and writes [base, base + 64)
+        for (int32_t base = 0; base < n_comp; base += kWave) {
+            const int32_t cc = base + lane;
+            const float v = (!reset_now && cc + na < n_comp) ? nom[cc + na] : a.refill;
+            wave_lds_fence();
+            if (cc < n_comp) nom[cc] = v;
+            wave_lds_fence();
+        }
+    }
+
+    for (int32_t cc = lane; cc < n_comp; cc += kWave) a.nominal[((int64_t)(cc / na) * n + i) * na + cc % na] = nom[cc];
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a.state[k * n + i] = s[k];
+        a.steps[i] = steps;
+        a.episode[i] = episode;
+        ((unsigned long long*)wt)[0] = (unsigned long long)done;  // lane 0's own slot, after its last use
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 #ifndef EMEI_XCD_CONTIGUOUS
@@ -887,6 +1113,26 @@ static int launch_env(const PendLaunch& L) {
                                    (const float*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p, a.trig,
                                    L.return_out, L.length_out, (float4*)L.obs_out, none, (PlanPartial*)nullptr);
             }
+            break;
+        }
+        case PEND_OP_MPC: {
+            MpcArgs<Env> m;
+            m.state = (R*)L.state, m.steps = L.steps, m.episode = L.episode, m.trig = a.trig;
+            m.nominal = L.mpc_nominal, m.work = L.return_out, m.actions_out = L.mpc_actions_out;
+            m.obs_out = (float4*)L.obs_out, m.reward_out = L.reward_out, m.done_out = L.done_out;
+            m.plan_return_out = L.plan_return_out, m.ess_out = L.ess_out;
+            m.n = L.n, m.n_steps = L.n_steps, m.horizon = L.horizon, m.n_cand = L.n_candidates, m.freq_rate = L.freq_rate;
+            m.action_dtype = L.action_dtype, m.max_episode_steps = L.max_episode_steps, m.flags = L.flags;
+            m.reset_seed = L.seed, m.env_offset = L.env_offset, m.seed = L.cand.seed;
+            m.discount = L.discount, m.temperature = L.temperature;
+            m.sigma = L.cand.sigma, m.lo = L.cand.lo, m.hi = L.cand.hi;
+            m.refill = L.refill, m.nominal_lo = L.nominal_lo, m.nominal_hi = L.nominal_hi;
+            m.p = a.p;
+            if (L.horizon < 1 || L.horizon > EMEI_MPC_MAX_HORIZON) return EMEI_ERR_INVALID;  // the LDS slice of the nominal
+            constexpr int kWavesPerBlock = kBlock / kWave;  // one wave per env
+            const dim3 mgrid((unsigned)((L.n + kWavesPerBlock - 1) / kWavesPerBlock));
+            hipLaunchKernelGGL(pend_mpc_mppi_kernel<Env>, mgrid, dim3(kBlock), 0, L.stream, m);
+            if (L.selected) *L.selected = EMEI_KERNEL_PEND_MPC_MPPI;
             break;
         }
         default: return EMEI_ERR_INVALID;

@@ -98,6 +98,22 @@ int launch_compact_done(const unsigned long long* masks, int64_t n, int32_t* idx
     return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;
 }
 
+// emei_mpc_mppi keeps one wave per env, so no wave holds the done bits of 64 envs: its kernel leaves env i's last done code in word 0
+// of the env's workspace row, and this follow-up launch ballots them into the mask words emei_compact_done reads (no atomics).
+__global__ void __launch_bounds__(kBlock)
+    mpc_done_pack_kernel(const unsigned long long* work, int64_t stride, int64_t n, unsigned long long* done_mask) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool done = i < n && work[i * stride] != 0ull;  // lanes past n ballot zeros
+    const unsigned long long m = __ballot(done);
+    if (i < n && (threadIdx.x & (kWave - 1)) == 0) done_mask[i / kWave] = m;
+}
+
+int launch_mpc_done_pack(const double* work, int64_t stride, int64_t n, unsigned long long* done_mask, hipStream_t s) {
+    dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(mpc_done_pack_kernel, grid, dim3(kBlock), 0, s, (const unsigned long long*)work, stride, n, done_mask);
+    return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;
+}
+
 // ---------------------------------------------------------------------------------------------
 // emei_sample_candidates: lane j writes the sequence of candidate (i = j / K, k = j % K) — what the plan kernels draw in their
 // lanes (emei_device.h:draw_action) — step by step, the stores of a step contiguous over the lanes.

@@ -32,20 +32,36 @@ def random_actions(env, n_steps, generator=None):
     return (lo + (hi - lo) * u).float().contiguous()
 
 
-def collect(env, n_steps, actions=None, seed=0, device_rng=True, policy=None):
+def collect(env, n_steps, actions=None, seed=0, device_rng=True, policy=None, mpc=None):
     """Roll every env of `env` (a vectorised emei_amd env) for n_steps with auto-reset and return
     (dataset dict of torch tensors with N*n_steps rows, rollout_info dict like zoo/util.py:85-91).
 
     Actions: `actions` [T, N(, act_dim)] if given; else `policy(obs [N, obs_dim] float32 on the device) ->
     actions [N(, act_dim)]` evaluated between steps (the agent.predict loop of zoo/util.py:54-59: one
     emei_step launch per step, observations after a device reset rebuilt the same way); else uniform random
-    actions (`env.action_space.sample()`, zoo/util.py:58) in ONE fused rollout launch."""
+    actions (`env.action_space.sample()`, zoo/util.py:58) in ONE fused rollout launch.
+    mpc: instead of either, dict(horizon=, n_candidates=, temperature=[, seed=, discount=, sigma=, refill=, clamp=, nominal=]) — an
+    MPPI controller on the true dynamics acts (Engine.mpc_mppi: ONE launch with auto-reset, the 4-state envs; seed defaults to
+    `seed`, nominal to `refill` everywhere)."""
     eng = env.engine
     N, T, od = eng.n_envs, int(n_steps), eng.obs_dim
     obs0, _ = env.reset(seed=seed, options={"device_rng": True} if device_rng else None)
     obs0 = torch.as_tensor(obs0, device=eng.device).reshape(N, od).float()
     _, epi0 = eng.get_counters()
-    if actions is None and policy is not None:
+    if mpc is not None:
+        if actions is not None or policy is not None:
+            raise ValueError("collect: mpc= is an action source of its own; give neither actions= nor policy=")
+        kw = dict(mpc)
+        H, K, temperature = int(kw.pop("horizon")), int(kw.pop("n_candidates")), float(kw.pop("temperature"))
+        refill = kw.get("refill")
+        if refill is None:
+            refill = kw["refill"] = 0.5 if eng.act_dim == 0 else 0.0
+        nominal = kw.pop("nominal", None)
+        if nominal is None:
+            shape = (H, N) + ((eng.act_dim,) if eng.act_dim > 1 else ())
+            nominal = torch.full(shape, float(refill), dtype=torch.float32, device=eng.device)
+        actions, next_obs, rew, done = eng.mpc_mppi(T, H, K, kw.pop("seed", seed), temperature, nominal, auto_reset=True, **kw)
+    elif actions is None and policy is not None:
         next_obs, rew, done = eng.alloc_outputs(T)
         acts_t, cur, epi = [], obs0, epi0.clone()
         for t in range(T):

@@ -14,6 +14,10 @@ _ACT_DTYPES = {torch.uint8: L.ACT_U8, torch.int32: L.ACT_I32, torch.int64: L.ACT
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
+# ctrlrange of the continuous envs mpc_mppi serves (inverted_pendulum.xml:23), its default clamp of the nominal
+_CTRL_RANGE = {name: (-3.0, 3.0) for name in L.ENV_IDS if name.endswith(("InvertedPendulumBalancing", "InvertedPendulumSwingUp"))}
+
+
 def _stream():
     """hipStream_t of torch's current stream on the current device (the raw getter avoids building a
     Stream object on every call: 0.3 us instead of 3 us on the per-step path)."""
@@ -444,6 +448,45 @@ class Engine:
         L.check(L.lib().emei_plan_mppi(self._h, H, K, int(seed) & (2**64 - 1), _ptr(nominal), sigma, float(discount), temperature,
                                        _ptr(st), _ptr(ws), _ptr(out), _ptr(ret), _ptr(idx), _ptr(es), _stream()))
         return (out, ret, idx) + ((es,) if ess else ())
+
+    @_on_device
+    def mpc_mppi(self, T, H, K, seed, temperature, nominal, discount=1.0, sigma=None, refill=None, clamp=None, auto_reset=False,
+                 out=None, diagnostics=False):
+        """T control steps of receding-horizon MPPI in one launch (emei_mpc_mppi; the 4-state envs on their own kernels): per
+        step the nominal is clamped to `clamp`, updated as plan_mppi(H, K, seed + t, temperature, nominal=nominal, out=nominal)
+        updates it, its first entry is the action (discrete envs: entry >= 0.5), the envs take step(action, auto_reset), and the
+        nominal is shifted by one step with `refill` behind it (an env that was reset: `refill` everywhere) — bit for bit what
+        that loop of plan_mppi and step computes, state, counters and compact_done() included.
+        nominal: float32 [H, N(, act_dim)] on the engine's device, updated IN PLACE (ready for the next call: T = a + b steps equal
+        a call with (a, seed) and one with (b, seed + a)).  refill: default 0.5 (discrete) / 0.0 (continuous).  clamp: (lo, hi),
+        default (0.05, 0.95) on the discrete envs and the ctrlrange on the continuous ones.  out: (obs, reward, done) as rollout's.
+        -> (actions [T, N(, act_dim)] int64 / float32, obs [T, N, obs_dim] f32, reward [T, N] f32, done [T, N] u8
+        [, plan_return float64 [T, N], ess float64 [T, N]]: every step's best candidate return and effective sample size)."""
+        T = int(T)
+        if T < 1:
+            raise ValueError(f"n_steps={T} must be >= 1")
+        if nominal is None:
+            raise ValueError("mpc_mppi needs a nominal tensor (it is updated in place)")
+        H, K, nominal, sigma, dtype = self._candidate_args(H, K, nominal, sigma, None)
+        if refill is None:
+            refill = 0.5 if self.act_dim == 0 else 0.0
+        if clamp is None:
+            clamp = (0.05, 0.95) if self.act_dim == 0 else _CTRL_RANGE.get(self.env_name, (-1.0, 1.0))
+        lo, hi = float(clamp[0]), float(clamp[1])
+        obs, rew, done = self._check_outputs(out, (T,)) if out is not None else self.alloc_outputs(T)
+        need = int(L.lib().emei_mpc_mppi_workspace_bytes(self.n_envs, K))
+        if need < 0:
+            L.check(need)
+        ws = getattr(self, "_mpc_ws", None)
+        if ws is None or ws.numel() * 8 < need:  # grow-only
+            ws = self._mpc_ws = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+        act = torch.empty((T, self.n_envs) + ((self.act_dim,) if self.act_dim > 1 else ()), dtype=dtype, device=self.device)
+        pr = torch.empty((T, self.n_envs), dtype=torch.float64, device=self.device) if diagnostics else None
+        es = torch.empty((T, self.n_envs), dtype=torch.float64, device=self.device) if diagnostics else None
+        L.check(L.lib().emei_mpc_mppi(self._h, T, H, K, int(seed) & (2**64 - 1), _ptr(nominal), sigma, float(discount), float(temperature),
+                                      float(refill), lo, hi, _ptr(ws), _ptr(act), _ACT_DTYPES[dtype], _ptr(obs), _ptr(rew), _ptr(done),
+                                      _ptr(pr), _ptr(es), L.FLAG_AUTO_RESET if auto_reset else 0, _stream()))
+        return (act, obs, rew, done) + ((pr, es) if diagnostics else ())
 
     def _check_plan_out(self, name, out, shape, source, source_name):
         """an output tensor of plan_mppi / plan_cem: float32 [H, N(, act_dim)], `source` itself (in place) or clear of it"""

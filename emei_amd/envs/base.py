@@ -346,6 +346,34 @@ class HipEnv(EmeiEnv):
                             out=out, ess=ess)
         return tuple(t.cpu().numpy() for t in res) if as_numpy else res
 
+    def mpc_mppi(self, n_steps, horizon, n_candidates, seed, temperature, nominal, discount=1.0, sigma=None, refill=None, clamp=None,
+                 auto_reset=None, diagnostics=False):
+        """n_steps control steps of receding-horizon MPPI in one launch (Engine.mpc_mppi, ABI emei_mpc_mppi; the 4-state envs):
+        per step plan_mppi(horizon, n_candidates, seed + t, temperature, nominal=nominal, out=nominal) on the clamped nominal, its first
+        entry as the action (discrete envs: >= 0.5), step(), and the nominal shifted by one step with `refill` behind it — the same
+        bits as that loop —
+        (actions [n_steps, num_envs(, act_dim)], obs float32 [n_steps, num_envs, obs_dim], reward float32, terminal bool, truncated
+        bool [, plan_return float64 [n_steps, num_envs], ess float64 [n_steps, num_envs]]).
+        nominal: float32 [horizon, num_envs(, act_dim)].  A tensor on the env's device is updated in place and tensors come back; a
+        NumPy array is left as it is and NumPy arrays come back, the updated nominal appended as the last element.  auto_reset: the
+        env's own setting unless given.  Other arguments as Engine.mpc_mppi."""
+        import torch
+
+        assert self.state is not None, "Call reset before using step method."  # base_control.py:67
+        eng = self.engine
+        as_numpy = not isinstance(nominal, torch.Tensor)
+        nom = nominal if isinstance(nominal, torch.Tensor) else torch.as_tensor(np.asarray(nominal))
+        nom = nom.to(device=eng.device, dtype=torch.float32).contiguous()
+        res = eng.mpc_mppi(n_steps, horizon, n_candidates, seed, temperature, nom, discount=discount, sigma=sigma, refill=refill,
+                           clamp=clamp, auto_reset=self.auto_reset if auto_reset is None else auto_reset, diagnostics=diagnostics)
+        act, obs, rew, done = res[:4]
+        out = (act, obs, rew, (done & 1).bool(), (done & 2).bool()) + tuple(res[4:])
+        if not as_numpy:
+            if nom.data_ptr() != nominal.data_ptr():
+                nominal.copy_(nom.reshape(nominal.shape))  # a tensor that had to be moved or converted: still updated in place
+            return out
+        return tuple(t.cpu().numpy() for t in out + (nom,))
+
     def plan_cem(self, horizon, n_candidates, n_elites, seed, discount=1.0, nominal=None, sigma=None, start_state=None, iterations=1,
                  elite_return=False):
         """The cross-entropy method's refit of a sampling distribution over action sequences, two launches per iteration

@@ -41,7 +41,9 @@ extern "C" {
  *    candidates, redrawn on the device);
  *    emei_sample_candidates_sigma (the Gaussian candidates with a sigma per entry), emei_plan_cem_workspace_bytes, emei_plan_cem
  *    (one cross-entropy-method iteration: exact per-env selection of the n_elites best candidates on the device, their mean and
- *    standard deviation). */
+ *    standard deviation);
+ *    emei_mpc_mppi_workspace_bytes, emei_mpc_mppi (receding-horizon MPPI control episodes of the 4-state family in one launch:
+ *    plan, act, step, auto-reset and warm start per control step without leaving the device), EMEI_KERNEL_PEND_MPC_MPPI. */
 #define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
@@ -460,6 +462,52 @@ EMEI_API int emei_plan_cem(emei_env* h, int32_t horizon, int32_t n_candidates, i
                            float* mean_out, float* std_out, double* best_return_out, int32_t* best_index_out,
                            double* elite_return_out, void* stream);
 
+/* Receding-horizon MPPI control on the true dynamics, whole episodes in ONE launch (plus a small one that packs the done mask): what
+ * the loop "emei_plan_mppi, threshold / first entry, emei_step, shift the nominal" does in three launches and a handful of array
+ * operations per control step.  For the 4-state family on its own kernels (CartPole, CartPoleRK4, InvertedPendulum with the euler
+ * integrator and no observation noise), where a plan is microseconds of arithmetic and the loop is bound by launches.
+ *
+ * Semantics (normative).  For every env i and t = 0 .. n_steps - 1, m being env i's column of `nominal`:
+ *   1. Clamp.  m[h(, a)] = fminf(fmaxf(m[h(, a)], nominal_lo), nominal_hi); -inf / +inf: no clamp.  Non-finite nominal entries are the
+ *      caller's error: the results of that env are unspecified (the call does not fault).
+ *   2. Plan.  Exactly emei_plan_mppi(h, horizon, n_candidates, seed + t (mod 2^64), nominal = m, sigma, discount, temperature,
+ *      start_state = NULL, nominal_out = m) for env i: the same candidates (seed + t, g = env_index_offset + i, k), the same start
+ *      state (the env's current one), returns, (k*, r*), weight case analysis and summation tree (lane l adds its candidates
+ *      k = l, l + 64, .. in ascending order, then the butterfly d = 1 .. 32), one rounding to float32.
+ *      plan_return_out[t, i] = r*, ess_out[t, i] as emei_plan_mppi's ess_out (float64 [n_steps, n_envs]; either may be NULL).
+ *   3. Act.  Continuous envs: a_t = m[0, :]; discrete envs: a_t = (m[0] >= 0.5f) ? 1 : 0.  actions_out[t, i(, :)] in action_dtype
+ *      (U8 / I32 / I64 discrete, F32 continuous), [n_steps, n_envs(, act_dim)].  Required.
+ *   4. Step.  Exactly emei_step(a_t, flags) for env i, with emei_rollout's arithmetic: the TimeLimit counter, the EMEI_DONE_* bits
+ *      and EMEI_FLAG_AUTO_RESET with the handle's reset key and episode counter.  obs_out / reward_out / done_out at [t, i] as
+ *      emei_rollout writes them; any of the three may be NULL.
+ *   5. Warm start.  The step was done and auto-reset is on: m[h] = refill for all h (a new episode gets no warm start).  Otherwise
+ *      m[h] = m[h + 1] for h < horizon - 1 and m[horizon - 1] = refill.
+ * After the call `nominal` (float32 [horizon, n_envs(, act_dim)], in/out, required) holds m after the last shift, ready for the next
+ * call, and the handle is as after the equivalent loop: state, step and episode counters, the done mask emei_compact_done reads.
+ * Every output is bit-identical to that loop's.
+ * Consequences.  Chunking: n_steps = a + b in one call equals a call with (a, seed) followed by one with (b, seed + a) — a large
+ * n_steps * n_candidates * horizon is ONE long kernel, and splitting it costs nothing but launches.  Sharding: results depend on g,
+ * not on n_envs or the shard.  Stream: the call neither allocates nor synchronises (capturable).
+ * Work split: one wave per env, its candidates spread over the 64 lanes; many candidates with few envs favour emei_plan_mppi's route,
+ * which spreads all candidates over the device.
+ * workspace: emei_mpc_mppi_workspace_bytes(n_envs, n_candidates) = 8 * n_envs * n_candidates bytes of device memory, 8-byte aligned,
+ * contents irrelevant before and after.
+ * EMEI_ERR_INVALID before any HIP call, scalars first, in this order: n_steps < 1, horizon < 1, n_candidates < 1; discount outside
+ * (0, 1]; temperature not finite or <= 0; refill not finite, nominal_lo > nominal_hi or either NaN; horizon > EMEI_MPC_MAX_HORIZON
+ * (the nominal lives in LDS); then a NULL handle; emei_plan_shooting's candidate checks (sigma finite and > 0 on a continuous env,
+ * n_envs * n_candidates, a wrong action_dtype), unknown flags; NULL nominal, workspace or actions_out.  EMEI_ERR_STATE without a
+ * state.  EMEI_ERR_UNSUPPORTED, the message naming the reason, for a handle emei_rollout runs on the body kernels (HalfCheetah,
+ * Hopper, InvertedDoublePendulum; InvertedPendulum with another integrator or observation noise) and for a handle with observation
+ * peers set (emei_set_obs_peers). */
+#define EMEI_MPC_MAX_HORIZON 256
+/* bytes of device scratch emei_mpc_mppi needs for this shape; host only, no handle, no HIP call.
+ * Negative (EMEI_ERR_INVALID) where emei_plan_mppi_workspace_bytes is. */
+EMEI_API int64_t emei_mpc_mppi_workspace_bytes(int64_t n_envs, int32_t n_candidates);
+EMEI_API int emei_mpc_mppi(emei_env* h, int32_t n_steps, int32_t horizon, int32_t n_candidates, uint64_t seed, float* nominal,
+                           double sigma, double discount, double temperature, float refill, float nominal_lo, float nominal_hi,
+                           void* workspace, void* actions_out, int action_dtype, float* obs_out, float* reward_out, uint8_t* done_out,
+                           double* plan_return_out, double* ess_out, uint32_t flags, void* stream);
+
 /* Which kernel the LAST emei_step / emei_rollout of this handle launched (enum emei_kernel_id): a debug /
  * test getter, so that a parity test can assert that the path it checked is the path bench.py times. */
 enum emei_kernel_id {
@@ -473,7 +521,8 @@ enum emei_kernel_id {
     EMEI_KERNEL_BODY_CHUNKED = 7,      /* body_rollout_kernel<Body, false> as (64 envs) x (chunk of steps) work items (rollout_chunk_steps) */
     EMEI_KERNEL_BODY_RK4_CHUNKED = 8,  /* body_rollout_kernel<Body, true> likewise */
     EMEI_KERNEL_PEND_STAGED_PEERS_FREQ1 = 9, /* pend_rollout_staged_peers_kernel<Env, ActT, true>: with the peer stores of emei_set_obs_peers */
-    EMEI_KERNEL_PEND_STAGED_PEERS = 10       /* pend_rollout_staged_peers_kernel<Env, ActT, false> */
+    EMEI_KERNEL_PEND_STAGED_PEERS = 10,      /* pend_rollout_staged_peers_kernel<Env, ActT, false> */
+    EMEI_KERNEL_PEND_MPC_MPPI = 11           /* pend_mpc_mppi_kernel<Env>: emei_mpc_mppi (it steps the handle, so it reports here) */
 };
 EMEI_API int emei_last_rollout_kernel(emei_env* h);
 

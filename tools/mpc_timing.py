@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""Receding-horizon MPPI control episodes, two ways, in the same run: Engine.mpc_mppi (emei_mpc_mppi: one wave per env plans, acts,
+steps, auto-resets and shifts for all T control steps in ONE launch) against the loop it replaces, built from the API that was there
+before it — per control step a clamp, plan_mppi in place (two launches), a threshold, step (one launch), a roll and a refill
+(README, "MPPI").  The loop is the comparator; the fused call is never its own yardstick.  Both start every timed episode from the
+same state and nominal (restored outside the timed window) and compute the same bits (tests/test_gpu_mpc.py).
+Method: after `--warmup` untimed episodes of each route (code objects loaded, workspaces allocated, clocks settled), `--repeats`
+rounds; every round times ONE episode of each route with device events around it (the loop's host overhead is inside its window: the
+events bracket everything its T iterations enqueue), the two routes alternating inside the round so that drift hits both alike.
+Reported per shape: the median over the rounds and the spread (min, max) of either route, and the ratio of the medians.
+Shapes: CartPoleSwingUp N = 256 and N = 65 536, ReboundInvertedPendulumSwingUp N = 256; K = 64, H = 30; T = 200 (20 at N = 65 536).
+One JSON line per shape.  Run on the GPU box:
+    python tools/mpc_timing.py [--warmup 2] [--repeats 7] [--only INDEX]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from emei_amd.engine import Engine  # noqa: E402
+
+# (env, N, K, H, T, sigma)
+SHAPES = [
+    ("CartPoleSwingUp", 256, 64, 30, 200, None),
+    ("CartPoleSwingUp", 65536, 64, 30, 20, None),
+    ("ReboundInvertedPendulumSwingUp", 256, 64, 30, 200, 0.5),
+]
+TEMPERATURE, DISCOUNT = 0.5, 0.99
+
+
+def loop_episode(eng, T, H, K, seed, nominal, sigma, refill, lo, hi):
+    """the README loop, statement for statement (at the Engine level: less host work per call than through the env classes, so the
+    comparator is not handicapped): what a user ran before the fused call existed"""
+    for t in range(T):
+        nominal = torch.roll(nominal, -1, 0)
+        nominal[-1] = refill
+        nominal.clamp_(lo, hi)
+        eng.plan_mppi(H, K, seed + t, TEMPERATURE, discount=DISCOUNT, nominal=nominal, sigma=sigma, out=nominal)
+        eng.step((nominal[0] >= 0.5).long() if eng.act_dim == 0 else nominal[0], auto_reset=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--only", type=int, default=None, help="index of the one shape to run")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("mpc_timing.py needs a GPU")
+    for idx, (name, N, K, H, T, sigma) in enumerate(SHAPES):
+        if args.only is not None and args.only != idx:
+            continue
+        eng = Engine(name, N)
+        eng.reset(seed=0)
+        state0 = eng.get_state().clone()
+        refill = 0.5 if eng.act_dim == 0 else 0.0
+        lo, hi = (0.05, 0.95) if eng.act_dim == 0 else (-3.0, 3.0)
+        nominal = torch.empty((H, N), dtype=torch.float32, device=eng.device)
+        outs = eng.alloc_outputs(T)
+
+        def restore():
+            eng.reset(seed=0)
+            eng.set_state(state0)
+            nominal.fill_(refill)
+            torch.cuda.synchronize()
+
+        def fused():
+            eng.mpc_mppi(T, H, K, 1, TEMPERATURE, nominal, discount=DISCOUNT, sigma=sigma, refill=refill, clamp=(lo, hi), auto_reset=True,
+                         out=outs)
+
+        def loop():
+            loop_episode(eng, T, H, K, 1, nominal, sigma, refill, lo, hi)
+
+        def timed(fn):
+            restore()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1)
+
+        for _ in range(args.warmup):
+            timed(fused), timed(loop)
+        ms = {"fused": [], "loop": []}
+        for _ in range(args.repeats):
+            ms["fused"].append(timed(fused))
+            ms["loop"].append(timed(loop))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        print(json.dumps({
+            "env": name, "n_envs": N, "n_candidates": K, "horizon": H, "n_steps": T, "repeats": args.repeats,
+            "fused_ms": round(med["fused"], 4), "fused_ms_min_max": [round(min(ms["fused"]), 4), round(max(ms["fused"]), 4)],
+            "loop_ms": round(med["loop"], 4), "loop_ms_min_max": [round(min(ms["loop"]), 4), round(max(ms["loop"]), 4)],
+            "loop_over_fused": round(med["loop"] / med["fused"], 3),
+            "fused_us_per_control_step": round(1e3 * med["fused"] / T, 3), "loop_us_per_control_step": round(1e3 * med["loop"] / T, 3),
+        }), flush=True)
+        eng.close()
+
+
+if __name__ == "__main__":
+    main()
