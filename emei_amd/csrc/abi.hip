@@ -703,51 +703,86 @@ extern "C" EMEI_API int emei_step(emei_env* h, const void* actions, int action_d
     return emei_rollout(h, 1, actions, action_dtype, obs_out, reward_out, done_out, flags, stream);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The planner entry points refuse in one order: the scalars (without a handle and before any HIP call), the handle, what needs the
+// handle, the call's own pointers, the device, the state.  The refusals more than one of them makes:
+static int check_plan_scalars(const char* fn, int32_t horizon, int32_t n_candidates, double discount) {
+    if (horizon < 1) return fail(EMEI_ERR_INVALID, "%s: horizon=%d < 1", fn, horizon);
+    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "%s: n_candidates=%d < 1", fn, n_candidates);
+    if (!(discount > 0.0 && discount <= 1.0)) return fail(EMEI_ERR_INVALID, "%s: discount=%g is outside (0, 1]", fn, discount);
+    return EMEI_OK;
+}
+
+static int check_temperature(const char* fn, double temperature) {
+    if (!(std::isfinite(temperature) && temperature > 0.0))
+        return fail(EMEI_ERR_INVALID, "%s: temperature=%g must be finite and > 0", fn, temperature);
+    return EMEI_OK;
+}
+
+// one lane per candidate, 32-bit lane indices (as emei_create's bound on n_envs)
+static int check_plan_lanes(const char* fn, const emei_env* h, int32_t n_candidates) {
+    const int64_t nk = h->cfg.n_envs * (int64_t)n_candidates;
+    if (nk > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs * n_candidates = %lld exceeds 2^31 - 1", fn, (long long)nk);
+    return EMEI_OK;
+}
+
+// of the *_workspace_bytes functions -> n_envs * n_candidates, or the refusal's (negative) code
+static int64_t check_plan_shape(const char* fn, int64_t n_envs, int32_t n_candidates) {
+    if (n_envs < 1 || n_envs > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs=%lld", fn, (long long)n_envs);
+    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "%s: n_candidates=%d < 1", fn, n_candidates);
+    const int64_t nk = n_envs * (int64_t)n_candidates;
+    if (nk > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs * n_candidates = %lld exceeds 2^31 - 1", fn, (long long)nk);
+    return nk;
+}
+
+// The workspace of the drawn plans starts with one PlanPartial per (wave, env) segment of the plan kernel: at most waves + envs of
+// them (emei_device.h:plan_reduce_wave).  emei_plan_mppi / emei_plan_cem keep nk float64 returns / weights behind them.
+static int64_t plan_partials_bytes(int64_t n_envs, int64_t nk) {
+    static_assert(sizeof(PlanPartial) % 16 == 0, "the returns behind the partials stay 16-byte aligned");
+    return (int64_t)sizeof(PlanPartial) * ((nk + kWave - 1) / kWave + n_envs);
+}
+static double* plan_returns(const emei_env* h, int32_t n_candidates, void* workspace) {
+    return (double*)((char*)workspace + plan_partials_bytes(h->cfg.n_envs, h->cfg.n_envs * (int64_t)n_candidates));
+}
+
+// the plan kernel of the family emei_rollout runs for this handle; actions / action_dtype / final_obs: PLAN_GIVEN only
+static int launch_plan(emei_env* h, const PlanLaunch& p, int32_t horizon, const void* actions, int action_dtype, float* final_obs,
+                       void* stream) {
+    if (!steps_as_body(h->cfg)) {
+        PendLaunch L = pend_base(h, stream);
+        L.op = PEND_OP_PLAN, L.plan = p;
+        L.actions = actions, L.action_dtype = action_dtype, L.n_steps = horizon, L.obs_out = final_obs;
+        return pend_launch(L);
+    }
+    BodyLaunch L = body_base(h, stream);
+    L.op = BODY_OP_PLAN, L.plan = p;
+    L.actions = actions, L.n_steps = horizon, L.obs_out = final_obs;
+    return body_launch(L);
+}
+
 extern "C" EMEI_API int emei_evaluate_sequences(emei_env* h, int32_t horizon, int32_t n_candidates, const void* actions, int action_dtype,
                                                 double discount, const double* start_state, double* return_out, int32_t* length_out,
                                                 float* final_obs_out, void* stream) {
-    // the scalar arguments first: they are refused without a handle and before any HIP call
-    if (horizon < 1) return fail(EMEI_ERR_INVALID, "emei_evaluate_sequences: horizon=%d < 1", horizon);
-    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "emei_evaluate_sequences: n_candidates=%d < 1", n_candidates);
-    if (!(discount > 0.0 && discount <= 1.0))
-        return fail(EMEI_ERR_INVALID, "emei_evaluate_sequences: discount=%g is outside (0, 1]", discount);
-    if (!h) return fail(EMEI_ERR_INVALID, "emei_evaluate_sequences: null handle");
-    if (!actions || !return_out || !length_out) return fail(EMEI_ERR_INVALID, "emei_evaluate_sequences: null argument");
-    const int64_t nk = h->cfg.n_envs * (int64_t)n_candidates;
-    if (nk > INT32_MAX)  // one lane per candidate, 32-bit lane indices (as emei_create's bound on n_envs)
-        return fail(EMEI_ERR_INVALID, "emei_evaluate_sequences: n_envs * n_candidates = %lld exceeds 2^31 - 1", (long long)nk);
+    const char* fn = "emei_evaluate_sequences";
+    if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
+    if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
+    if (!actions || !return_out || !length_out) return fail(EMEI_ERR_INVALID, "%s: null argument", fn);
+    if (int rc = check_plan_lanes(fn, h, n_candidates)) return rc;
     if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
-    EMEI_ON_DEVICE(h, "emei_evaluate_sequences");
-    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "emei_evaluate_sequences: call reset before using the state");
-    int rc;
-    if (!steps_as_body(h->cfg)) {  // the kernel family emei_rollout runs for this handle
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_PLAN;
-        L.actions = actions, L.action_dtype = action_dtype, L.n_steps = horizon;
-        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
-        L.return_out = return_out, L.length_out = length_out, L.obs_out = final_obs_out;
-        rc = pend_launch(L);
-    } else {
-        BodyLaunch L = body_base(h, stream);
-        L.op = BODY_OP_PLAN;
-        L.actions = actions, L.n_steps = horizon;
-        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
-        L.return_out = return_out, L.length_out = length_out, L.obs_out = final_obs_out;
-        rc = body_launch(L);
-    }
-    return rc == EMEI_OK ? rc : fail(rc, "emei_evaluate_sequences: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+    EMEI_ON_DEVICE(h, fn);
+    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    PlanLaunch p;
+    p.mode = PLAN_GIVEN, p.start_rows = start_state, p.n_candidates = n_candidates, p.discount = discount;
+    p.return_out = return_out, p.length_out = length_out;
+    const int rc = launch_plan(h, p, horizon, actions, action_dtype, final_obs_out, stream);
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
 }
 
 // ---------------------------------------------------------------------------------------------
 // emei_plan_shooting / emei_sample_candidates
 extern "C" EMEI_API int64_t emei_plan_shooting_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
-    if (n_envs < 1 || n_envs > INT32_MAX) return fail(EMEI_ERR_INVALID, "emei_plan_shooting_workspace_bytes: n_envs=%lld", (long long)n_envs);
-    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "emei_plan_shooting_workspace_bytes: n_candidates=%d < 1", n_candidates);
-    const int64_t nk = n_envs * (int64_t)n_candidates;
-    if (nk > INT32_MAX)
-        return fail(EMEI_ERR_INVALID, "emei_plan_shooting_workspace_bytes: n_envs * n_candidates = %lld exceeds 2^31 - 1", (long long)nk);
-    // one PlanPartial per (wave, env) segment of the plan kernel: at most waves + envs of them (emei_device.h:plan_reduce_wave)
-    return (int64_t)sizeof(PlanPartial) * ((nk + kWave - 1) / kWave + n_envs);
+    const int64_t nk = check_plan_shape("emei_plan_shooting_workspace_bytes", n_envs, n_candidates);
+    return nk < 0 ? nk : plan_partials_bytes(n_envs, nk);
 }
 
 // the env's ctrlrange from the kernels' own model constants (the Python classes' action_space bounds)
@@ -759,81 +794,67 @@ static void ctrl_range(int env_id, float& lo, float& hi) {
     else lo = 0.f, hi = 1.f;  // discrete: unused
 }
 
-// the checks the two entry points share, in emei_evaluate_sequences' order: scalars, the handle, what needs the handle
-static int check_candidates(const char* fn, emei_env* h, int32_t horizon, int32_t n_candidates, const float* nominal, double sigma,
-                            int action_dtype, CandidateSpec& sp) {
+// What the calls that draw candidates refuse alike, from the handle on.  sigma_counts: the call draws around a nominal under the
+// scalar `sigma` (which a continuous env then reads).  A call that emits actions checks their dtype next (check_action_dtype).
+static int check_candidates(const char* fn, const emei_env* h, int32_t horizon, int32_t n_candidates, bool sigma_counts, double sigma) {
     if (horizon < 1) return fail(EMEI_ERR_INVALID, "%s: horizon=%d < 1", fn, horizon);
     if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "%s: n_candidates=%d < 1", fn, n_candidates);
     if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
-    if (nominal && h->act_dim > 0 && !(std::isfinite(sigma) && sigma > 0.0))
+    if (sigma_counts && h->act_dim > 0 && !(std::isfinite(sigma) && sigma > 0.0))
         return fail(EMEI_ERR_INVALID, "%s: sigma=%g with a nominal sequence must be finite and > 0", fn, sigma);
-    const int64_t nk = h->cfg.n_envs * (int64_t)n_candidates;
-    if (nk > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs * n_candidates = %lld exceeds 2^31 - 1", fn, (long long)nk);
+    if (int rc = check_plan_lanes(fn, h, n_candidates)) return rc;
     if ((int64_t)horizon * (h->act_dim > 0 ? h->act_dim : 1) > INT32_MAX)  // 32-bit word index of the candidate's stream
         return fail(EMEI_ERR_INVALID, "%s: horizon * act_dim exceeds 2^31 - 1", fn);
-    if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
-    sp.env_offset = h->cfg.env_index_offset, sp.nominal = nominal, sp.sigma = (float)sigma;
-    ctrl_range(h->cfg.env_id, sp.lo, sp.hi);
     return EMEI_OK;
+}
+
+// the candidate rule of a checked call; `sigma` is read only where check_candidates' sigma_counts held
+static CandidateSpec candidate_spec(const emei_env* h, uint64_t seed, const float* nominal, double sigma) {
+    CandidateSpec sp{};
+    sp.seed = seed, sp.env_offset = h->cfg.env_index_offset, sp.nominal = nominal, sp.sigma = (float)sigma;
+    ctrl_range(h->cfg.env_id, sp.lo, sp.hi);
+    return sp;
 }
 
 extern "C" EMEI_API int emei_sample_candidates(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal,
                                                double sigma, void* actions_out, int action_dtype, void* stream) {
-    CandidateSpec sp{};
-    sp.seed = seed;
-    if (int rc = check_candidates("emei_sample_candidates", h, horizon, n_candidates, nominal, sigma, action_dtype, sp)) return rc;
-    if (!actions_out) return fail(EMEI_ERR_INVALID, "emei_sample_candidates: null argument");
-    EMEI_ON_DEVICE(h, "emei_sample_candidates");
-    const int rc = launch_sample_candidates(sp, h->cfg.n_envs, n_candidates, horizon, h->act_dim, actions_out, action_dtype, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "emei_sample_candidates: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+    const char* fn = "emei_sample_candidates";
+    if (int rc = check_candidates(fn, h, horizon, n_candidates, nominal != nullptr, sigma)) return rc;
+    if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
+    if (!actions_out) return fail(EMEI_ERR_INVALID, "%s: null argument", fn);
+    EMEI_ON_DEVICE(h, fn);
+    const int rc = launch_sample_candidates(candidate_spec(h, seed, nominal, sigma), h->cfg.n_envs, n_candidates, horizon, h->act_dim,
+                                            actions_out, action_dtype, (hipStream_t)stream);
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
 }
 
 extern "C" EMEI_API int emei_plan_shooting(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal,
                                            double sigma, double discount, const double* start_state, void* workspace,
                                            void* best_action_out, int action_dtype, void* best_sequence_out, double* best_return_out,
                                            int32_t* best_index_out, int32_t* best_length_out, void* stream) {
-    if (horizon < 1) return fail(EMEI_ERR_INVALID, "emei_plan_shooting: horizon=%d < 1", horizon);
-    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "emei_plan_shooting: n_candidates=%d < 1", n_candidates);
-    if (!(discount > 0.0 && discount <= 1.0)) return fail(EMEI_ERR_INVALID, "emei_plan_shooting: discount=%g is outside (0, 1]", discount);
-    CandidateSpec sp{};
-    sp.seed = seed;
-    if (int rc = check_candidates("emei_plan_shooting", h, horizon, n_candidates, nominal, sigma, action_dtype, sp)) return rc;
-    if (!workspace || !best_action_out || !best_return_out || !best_index_out)
-        return fail(EMEI_ERR_INVALID, "emei_plan_shooting: null argument");
-    EMEI_ON_DEVICE(h, "emei_plan_shooting");
-    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "emei_plan_shooting: call reset before using the state");
-    int rc;
-    if (!steps_as_body(h->cfg)) {  // the kernel family emei_rollout runs for this handle
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_PLAN;
-        L.action_dtype = action_dtype, L.n_steps = horizon;
-        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
-        L.cand = sp, L.partials = workspace;
-        rc = pend_launch(L);
-    } else {
-        BodyLaunch L = body_base(h, stream);
-        L.op = BODY_OP_PLAN;
-        L.n_steps = horizon;
-        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
-        L.cand = sp, L.partials = workspace;
-        rc = body_launch(L);
-    }
+    const char* fn = "emei_plan_shooting";
+    if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
+    if (int rc = check_candidates(fn, h, horizon, n_candidates, nominal != nullptr, sigma)) return rc;
+    if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
+    if (!workspace || !best_action_out || !best_return_out || !best_index_out) return fail(EMEI_ERR_INVALID, "%s: null argument", fn);
+    EMEI_ON_DEVICE(h, fn);
+    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    PlanLaunch p;
+    p.mode = PLAN_DRAWN, p.start_rows = start_state, p.n_candidates = n_candidates, p.discount = discount;
+    p.cand = candidate_spec(h, seed, nominal, sigma), p.partials = workspace;
+    int rc = launch_plan(h, p, horizon, nullptr, 0, nullptr, stream);
     if (rc == EMEI_OK)
-        rc = launch_plan_finish(workspace, sp, h->cfg.n_envs, n_candidates, horizon, h->act_dim, best_action_out, action_dtype,
+        rc = launch_plan_finish(workspace, p.cand, h->cfg.n_envs, n_candidates, horizon, h->act_dim, best_action_out, action_dtype,
                                 best_sequence_out, best_return_out, best_index_out, best_length_out, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "emei_plan_shooting: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
 }
 
 // ---------------------------------------------------------------------------------------------
 // emei_plan_mppi: the plan kernel of emei_plan_shooting with every return kept, then the weighted mean of the redrawn candidates.
 // Workspace: emei_plan_shooting's partials (a multiple of 16 bytes), then n_envs * n_candidates float64 returns / weights.
 static int64_t keep_workspace_bytes(const char* fn, int64_t n_envs, int32_t n_candidates) {  // also emei_plan_cem's
-    if (n_envs < 1 || n_envs > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs=%lld", fn, (long long)n_envs);
-    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "%s: n_candidates=%d < 1", fn, n_candidates);
-    const int64_t nk = n_envs * (int64_t)n_candidates;
-    if (nk > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs * n_candidates = %lld exceeds 2^31 - 1", fn, (long long)nk);
-    static_assert(sizeof(PlanPartial) % 16 == 0, "the returns behind the partials stay 16-byte aligned");
-    return (int64_t)sizeof(PlanPartial) * ((nk + kWave - 1) / kWave + n_envs) + (int64_t)sizeof(double) * nk;
+    const int64_t nk = check_plan_shape(fn, n_envs, n_candidates);
+    return nk < 0 ? nk : plan_partials_bytes(n_envs, nk) + (int64_t)sizeof(double) * nk;
 }
 extern "C" EMEI_API int64_t emei_plan_mppi_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
     return keep_workspace_bytes("emei_plan_mppi_workspace_bytes", n_envs, n_candidates);
@@ -843,57 +864,37 @@ extern "C" EMEI_API int emei_plan_mppi(emei_env* h, int32_t horizon, int32_t n_c
                                        double discount, double temperature, const double* start_state, void* workspace,
                                        float* nominal_out, double* best_return_out, int32_t* best_index_out, double* ess_out,
                                        void* stream) {
-    if (horizon < 1) return fail(EMEI_ERR_INVALID, "emei_plan_mppi: horizon=%d < 1", horizon);
-    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "emei_plan_mppi: n_candidates=%d < 1", n_candidates);
-    if (!(discount > 0.0 && discount <= 1.0)) return fail(EMEI_ERR_INVALID, "emei_plan_mppi: discount=%g is outside (0, 1]", discount);
-    if (!(std::isfinite(temperature) && temperature > 0.0))
-        return fail(EMEI_ERR_INVALID, "emei_plan_mppi: temperature=%g must be finite and > 0", temperature);
-    CandidateSpec sp{};
-    sp.seed = seed;
-    // no actions leave this call: the dtype the shared checks see is one the env's kind takes
-    const int dtype = h && h->act_dim > 0 ? EMEI_ACT_F32 : EMEI_ACT_U8;
-    if (int rc = check_candidates("emei_plan_mppi", h, horizon, n_candidates, nominal, sigma, dtype, sp)) return rc;
-    if (!workspace) return fail(EMEI_ERR_INVALID, "emei_plan_mppi: null workspace");
-    if (!nominal_out) return fail(EMEI_ERR_INVALID, "emei_plan_mppi: null nominal_out");
-    EMEI_ON_DEVICE(h, "emei_plan_mppi");
-    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "emei_plan_mppi: call reset before using the state");
-    const int64_t nk = h->cfg.n_envs * (int64_t)n_candidates;
-    double* returns = (double*)((char*)workspace + sizeof(PlanPartial) * ((nk + kWave - 1) / kWave + h->cfg.n_envs));
-    int rc;
-    if (!steps_as_body(h->cfg)) {  // the kernel family emei_rollout runs for this handle
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_PLAN;
-        L.action_dtype = dtype, L.n_steps = horizon;
-        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
-        L.cand = sp, L.partials = workspace, L.return_out = returns;
-        rc = pend_launch(L);
-    } else {
-        BodyLaunch L = body_base(h, stream);
-        L.op = BODY_OP_PLAN;
-        L.n_steps = horizon;
-        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
-        L.cand = sp, L.partials = workspace, L.return_out = returns;
-        rc = body_launch(L);
-    }
+    const char* fn = "emei_plan_mppi";
+    if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
+    if (int rc = check_temperature(fn, temperature)) return rc;
+    if (int rc = check_candidates(fn, h, horizon, n_candidates, nominal != nullptr, sigma)) return rc;
+    if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
+    if (!nominal_out) return fail(EMEI_ERR_INVALID, "%s: null nominal_out", fn);
+    EMEI_ON_DEVICE(h, fn);
+    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    PlanLaunch p;
+    p.mode = PLAN_DRAWN_KEEP, p.start_rows = start_state, p.n_candidates = n_candidates, p.discount = discount;
+    p.cand = candidate_spec(h, seed, nominal, sigma), p.partials = workspace, p.return_out = plan_returns(h, n_candidates, workspace);
+    int rc = launch_plan(h, p, horizon, nullptr, 0, nullptr, stream);
     if (rc == EMEI_OK)
-        rc = launch_plan_mppi_finish(workspace, returns, sp, h->cfg.n_envs, n_candidates, horizon, h->act_dim, temperature, nominal_out,
+        rc = launch_plan_mppi_finish(workspace, p.return_out, p.cand, h->cfg.n_envs, n_candidates, horizon, h->act_dim, temperature, nominal_out,
                                      best_return_out, best_index_out, ess_out, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "emei_plan_mppi: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
 }
 
-// emei_sample_candidates_sigma: emei_sample_candidates' Gaussian mode with the sigma read per entry (the scalar's check does not apply)
+// emei_sample_candidates_sigma: emei_sample_candidates' Gaussian mode with the sigma read per entry (there is no scalar to check)
 extern "C" EMEI_API int emei_sample_candidates_sigma(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal,
                                                      const float* sigma_map, void* actions_out, int action_dtype, void* stream) {
-    CandidateSpec sp{};
-    sp.seed = seed;
-    if (int rc = check_candidates("emei_sample_candidates_sigma", h, horizon, n_candidates, nominal, 1.0, action_dtype, sp)) return rc;
-    if (h->act_dim == 0) return fail(EMEI_ERR_INVALID, "emei_sample_candidates_sigma: a discrete env takes no sigma_map");
-    if (!nominal || !sigma_map) return fail(EMEI_ERR_INVALID, "emei_sample_candidates_sigma: null nominal or sigma_map");
-    if (!actions_out) return fail(EMEI_ERR_INVALID, "emei_sample_candidates_sigma: null argument");
-    EMEI_ON_DEVICE(h, "emei_sample_candidates_sigma");
-    const int rc = launch_sample_candidates_sigma(CandidateSpecMap(sp, sigma_map), h->cfg.n_envs, n_candidates, horizon, h->act_dim,
-                                                  actions_out, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "emei_sample_candidates_sigma: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+    const char* fn = "emei_sample_candidates_sigma";
+    if (int rc = check_candidates(fn, h, horizon, n_candidates, false, 0.0)) return rc;
+    if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
+    if (h->act_dim == 0) return fail(EMEI_ERR_INVALID, "%s: a discrete env takes no sigma_map", fn);
+    if (!nominal || !sigma_map) return fail(EMEI_ERR_INVALID, "%s: null nominal or sigma_map", fn);
+    if (!actions_out) return fail(EMEI_ERR_INVALID, "%s: null argument", fn);
+    EMEI_ON_DEVICE(h, fn);
+    const int rc = launch_sample_candidates_sigma(CandidateSpecMap(candidate_spec(h, seed, nominal, 0.0), sigma_map), h->cfg.n_envs,
+                                                  n_candidates, horizon, h->act_dim, actions_out, (hipStream_t)stream);
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -907,58 +908,37 @@ extern "C" EMEI_API int emei_plan_cem(emei_env* h, int32_t horizon, int32_t n_ca
                                       const float* nominal, double sigma, const float* sigma_map, double discount,
                                       const double* start_state, void* workspace, float* mean_out, float* std_out,
                                       double* best_return_out, int32_t* best_index_out, double* elite_return_out, void* stream) {
-    if (horizon < 1) return fail(EMEI_ERR_INVALID, "emei_plan_cem: horizon=%d < 1", horizon);
-    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "emei_plan_cem: n_candidates=%d < 1", n_candidates);
-    if (n_elites < 1 || n_elites > n_candidates)
-        return fail(EMEI_ERR_INVALID, "emei_plan_cem: n_elites=%d is outside [1, n_candidates=%d]", n_elites, n_candidates);
-    if (!(discount > 0.0 && discount <= 1.0)) return fail(EMEI_ERR_INVALID, "emei_plan_cem: discount=%g is outside (0, 1]", discount);
-    CandidateSpec sp{};
-    sp.seed = seed;
-    // no actions leave this call: the dtype the shared checks see is one the env's kind takes
-    const int dtype = h && h->act_dim > 0 ? EMEI_ACT_F32 : EMEI_ACT_U8;
-    // with a sigma_map the scalar is ignored: the shared check sees one it accepts
-    if (int rc = check_candidates("emei_plan_cem", h, horizon, n_candidates, nominal, sigma_map ? 1.0 : sigma, dtype, sp)) return rc;
-    if (sigma_map && !nominal) return fail(EMEI_ERR_INVALID, "emei_plan_cem: a sigma_map needs a nominal");
+    const char* fn = "emei_plan_cem";
+    // n_elites is refused after horizon and n_candidates, before discount
+    if (horizon >= 1 && n_candidates >= 1 && (n_elites < 1 || n_elites > n_candidates))
+        return fail(EMEI_ERR_INVALID, "%s: n_elites=%d is outside [1, n_candidates=%d]", fn, n_elites, n_candidates);
+    if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
+    // with a sigma_map the scalar is ignored
+    if (int rc = check_candidates(fn, h, horizon, n_candidates, nominal && !sigma_map, sigma)) return rc;
+    if (sigma_map && !nominal) return fail(EMEI_ERR_INVALID, "%s: a sigma_map needs a nominal", fn);
     if (h->act_dim == 0 && (sigma_map || std_out))
-        return fail(EMEI_ERR_INVALID, "emei_plan_cem: a discrete env takes no sigma_map and has no std_out");
-    if (!workspace) return fail(EMEI_ERR_INVALID, "emei_plan_cem: null workspace");
-    if (!mean_out) return fail(EMEI_ERR_INVALID, "emei_plan_cem: null mean_out");
-    EMEI_ON_DEVICE(h, "emei_plan_cem");
-    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "emei_plan_cem: call reset before using the state");
-    const int64_t nk = h->cfg.n_envs * (int64_t)n_candidates;
-    double* returns = (double*)((char*)workspace + sizeof(PlanPartial) * ((nk + kWave - 1) / kWave + h->cfg.n_envs));
-    int rc;
-    if (!steps_as_body(h->cfg)) {  // the kernel family emei_rollout runs for this handle
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_PLAN;
-        L.action_dtype = dtype, L.n_steps = horizon;
-        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
-        L.cand = sp, L.partials = workspace, L.return_out = returns, L.sigma_map = sigma_map;
-        rc = pend_launch(L);
-    } else {
-        BodyLaunch L = body_base(h, stream);
-        L.op = BODY_OP_PLAN;
-        L.n_steps = horizon;
-        L.start_rows = start_state, L.n_candidates = n_candidates, L.discount = discount;
-        L.cand = sp, L.partials = workspace, L.return_out = returns, L.sigma_map = sigma_map;
-        rc = body_launch(L);
-    }
+        return fail(EMEI_ERR_INVALID, "%s: a discrete env takes no sigma_map and has no std_out", fn);
+    if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
+    if (!mean_out) return fail(EMEI_ERR_INVALID, "%s: null mean_out", fn);
+    EMEI_ON_DEVICE(h, fn);
+    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    PlanLaunch p;
+    p.mode = PLAN_DRAWN_KEEP, p.start_rows = start_state, p.n_candidates = n_candidates, p.discount = discount;
+    p.cand = candidate_spec(h, seed, nominal, sigma), p.sigma_map = sigma_map;
+    p.partials = workspace, p.return_out = plan_returns(h, n_candidates, workspace);
+    int rc = launch_plan(h, p, horizon, nullptr, 0, nullptr, stream);
     if (rc == EMEI_OK)
-        rc = launch_plan_cem_finish(workspace, returns, sp, sigma_map, h->cfg.n_envs, n_candidates, n_elites, horizon, h->act_dim, mean_out,
+        rc = launch_plan_cem_finish(workspace, p.return_out, p.cand, sigma_map, h->cfg.n_envs, n_candidates, n_elites, horizon, h->act_dim, mean_out,
                                     std_out, best_return_out, best_index_out, elite_return_out, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "emei_plan_cem: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
 }
 
 // ---------------------------------------------------------------------------------------------
 // emei_mpc_mppi: n_steps control steps of "emei_plan_mppi, act, emei_step, shift" in one kernel of one wave per env
 // (pendulum_kernels.h:pend_mpc_mppi_kernel), then the done mask packed by a small second launch.
 extern "C" EMEI_API int64_t emei_mpc_mppi_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
-    const char* fn = "emei_mpc_mppi_workspace_bytes";
-    if (n_envs < 1 || n_envs > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs=%lld", fn, (long long)n_envs);
-    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "%s: n_candidates=%d < 1", fn, n_candidates);
-    const int64_t nk = n_envs * (int64_t)n_candidates;
-    if (nk > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs * n_candidates = %lld exceeds 2^31 - 1", fn, (long long)nk);
-    return (int64_t)sizeof(double) * nk;  // every candidate's return, then its weight
+    const int64_t nk = check_plan_shape("emei_mpc_mppi_workspace_bytes", n_envs, n_candidates);
+    return nk < 0 ? nk : (int64_t)sizeof(double) * nk;  // every candidate's return, then its weight
 }
 
 extern "C" EMEI_API int emei_mpc_mppi(emei_env* h, int32_t n_steps, int32_t horizon, int32_t n_candidates, uint64_t seed, float* nominal,
@@ -966,40 +946,38 @@ extern "C" EMEI_API int emei_mpc_mppi(emei_env* h, int32_t n_steps, int32_t hori
                                       float nominal_hi, void* workspace, void* actions_out, int action_dtype, float* obs_out,
                                       float* reward_out, uint8_t* done_out, double* plan_return_out, double* ess_out, uint32_t flags,
                                       void* stream) {
-    if (n_steps < 1) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: n_steps=%d < 1", n_steps);
-    if (horizon < 1) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: horizon=%d < 1", horizon);
-    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: n_candidates=%d < 1", n_candidates);
-    if (!(discount > 0.0 && discount <= 1.0)) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: discount=%g is outside (0, 1]", discount);
-    if (!(std::isfinite(temperature) && temperature > 0.0))
-        return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: temperature=%g must be finite and > 0", temperature);
-    if (!std::isfinite(refill)) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: refill=%g must be finite", (double)refill);
+    const char* fn = "emei_mpc_mppi";
+    if (n_steps < 1) return fail(EMEI_ERR_INVALID, "%s: n_steps=%d < 1", fn, n_steps);
+    if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
+    if (int rc = check_temperature(fn, temperature)) return rc;
+    if (!std::isfinite(refill)) return fail(EMEI_ERR_INVALID, "%s: refill=%g must be finite", fn, (double)refill);
     if (!(nominal_lo <= nominal_hi))  // also refuses a NaN bound
-        return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: nominal_lo=%g, nominal_hi=%g: need nominal_lo <= nominal_hi", (double)nominal_lo,
+        return fail(EMEI_ERR_INVALID, "%s: nominal_lo=%g, nominal_hi=%g: need nominal_lo <= nominal_hi", fn, (double)nominal_lo,
                     (double)nominal_hi);
     if (horizon > EMEI_MPC_MAX_HORIZON)
-        return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: horizon=%d exceeds EMEI_MPC_MAX_HORIZON=%d (the nominal lives in LDS)", horizon,
+        return fail(EMEI_ERR_INVALID, "%s: horizon=%d exceeds EMEI_MPC_MAX_HORIZON=%d (the nominal lives in LDS)", fn, horizon,
                     EMEI_MPC_MAX_HORIZON);
-    CandidateSpec sp{};
-    sp.seed = seed;
-    // the call always plans around a nominal, so sigma always counts: the shared check sees a non-null one even before the
-    // call's own NULL check below (it dereferences nothing)
-    if (int rc = check_candidates("emei_mpc_mppi", h, horizon, n_candidates, nominal ? nominal : &refill, sigma, action_dtype, sp)) return rc;
-    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: unknown flags 0x%x", flags);
-    if (!nominal) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: null nominal");
-    if (!workspace) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: null workspace");
-    if (!actions_out) return fail(EMEI_ERR_INVALID, "emei_mpc_mppi: null actions_out");
-    EMEI_ON_DEVICE(h, "emei_mpc_mppi");
-    if (!h->has_state) return fail(EMEI_ERR_STATE, "emei_mpc_mppi: call reset before using the state");
+    // the call always plans around a nominal, so sigma always counts (the nominal's own NULL check comes a few refusals later)
+    if (int rc = check_candidates(fn, h, horizon, n_candidates, true, sigma)) return rc;
+    if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
+    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "%s: unknown flags 0x%x", fn, flags);
+    if (!nominal) return fail(EMEI_ERR_INVALID, "%s: null nominal", fn);
+    if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
+    if (!actions_out) return fail(EMEI_ERR_INVALID, "%s: null actions_out", fn);
+    EMEI_ON_DEVICE(h, fn);
+    if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
     if (steps_as_body(h->cfg))
-        return fail(EMEI_ERR_UNSUPPORTED, "emei_mpc_mppi: this handle steps on the body kernels (a multi-body env, or an InvertedPendulum with "
-                                          "a non-euler integrator or observation noise); the fused controller serves the 4-state kernels only");
+        return fail(EMEI_ERR_UNSUPPORTED, "%s: this handle steps on the body kernels (a multi-body env, or an InvertedPendulum with "
+                                          "a non-euler integrator or observation noise); the fused controller serves the 4-state kernels only",
+                    fn);
     if (h->peers.count > 0)
-        return fail(EMEI_ERR_UNSUPPORTED, "emei_mpc_mppi: observation peers are set (emei_set_obs_peers), which this kernel does not serve");
+        return fail(EMEI_ERR_UNSUPPORTED, "%s: observation peers are set (emei_set_obs_peers), which this kernel does not serve", fn);
     PendLaunch L = pend_base(h, stream);
     L.op = PEND_OP_MPC;
-    L.n_steps = n_steps, L.horizon = horizon, L.n_candidates = n_candidates, L.discount = discount, L.temperature = temperature;
-    L.cand = sp, L.cand.nominal = nullptr;
-    L.mpc_nominal = nominal, L.return_out = (double*)workspace;
+    L.n_steps = n_steps, L.horizon = horizon, L.temperature = temperature;
+    L.plan.n_candidates = n_candidates, L.plan.discount = discount;
+    L.plan.cand = candidate_spec(h, seed, nullptr, sigma);  // the kernel keeps the nominal in LDS
+    L.mpc_nominal = nominal, L.plan.return_out = (double*)workspace;
     L.mpc_actions_out = actions_out, L.action_dtype = action_dtype;
     L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
     L.plan_return_out = plan_return_out, L.ess_out = ess_out;
@@ -1008,7 +986,7 @@ extern "C" EMEI_API int emei_mpc_mppi(emei_env* h, int32_t n_steps, int32_t hori
     L.selected = &h->last_kernel;
     int rc = pend_launch(L);
     if (rc == EMEI_OK) rc = launch_mpc_done_pack((const double*)workspace, n_candidates, h->cfg.n_envs, h->done_mask, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "emei_mpc_mppi: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
 }
 
 extern "C" EMEI_API int emei_compact_done(emei_env* h, int32_t* idx_out, int32_t* count_out, void* stream) {

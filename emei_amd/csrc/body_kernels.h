@@ -31,6 +31,7 @@
 // (4.5 KiB per wave and step for the cheetah).  LDS slices are wave-private: no barrier.
 #pragma once
 #include "emei_device.h"
+#include "launch.h"  // PlanLaunch
 
 namespace emei {
 
@@ -199,17 +200,7 @@ struct BodyLaunch {
     int32_t resident_waves = 0;  // waves of the rollout kernel the device holds at once (automatic policy); 0 = unknown
     hipStream_t stream = nullptr;
     int* selected = nullptr;  // out: enum emei_kernel_id of the rollout kernel launched
-    // BODY_OP_PLAN (emei_evaluate_sequences): n_candidates per env, n_steps = the horizon, obs_out = final_obs [n * K, NO] or null
-    const double* start_rows = nullptr;  // [n, NS] float64; null = the handle's state
-    int32_t n_candidates = 1;
-    double discount = 1.0;
-    double* return_out = nullptr;   // [n * K]
-    int32_t* length_out = nullptr;  // [n * K]
-    // emei_plan_shooting (as PendLaunch): partials != null -> candidates drawn in the lanes, one PlanPartial per (wave, env) segment;
-    // emei_plan_mppi: return_out != null as well -> every candidate's return is kept there too
-    CandidateSpec cand = {};
-    void* partials = nullptr;
-    const float* sigma_map = nullptr;  // emei_plan_cem: non-null -> the draws take their sigma per entry (CandidateSpecMap)
+    PlanLaunch plan;  // BODY_OP_PLAN; n_steps = the horizon, obs_out = final_obs [n * K, NO] or null
 };
 int body_launch(const BodyLaunch& L);  // body_dispatch.hip
 
@@ -781,6 +772,20 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
+// the one launch of body_plan_kernel: DRAWN kernels read no actions and write no lengths or final observations, and only KEEP
+// gives them a return_out; one lane per candidate, n * n_candidates < 2^31 (checked in abi.hip)
+template <class Body, bool RK4, bool DRAWN, bool KEEP, class Spec>
+static void launch_body_plan(const BodyLaunch& L, const typename Body::Model& m, const Spec& sp) {
+    const PlanLaunch& P = L.plan;
+    const dim3 pgrid((unsigned)((L.n * P.n_candidates + kBlock - 1) / kBlock));
+    const int semi = RK4 ? 0 : (int)(L.integrator == EMEI_INTEG_SEMI_IMPLICIT);
+    hipLaunchKernelGGL((body_plan_kernel<Body, RK4, DRAWN, KEEP, Spec>), pgrid, dim3(kBlock), 0, L.stream,
+                       (const typename Body::real*)L.state, P.start_rows, DRAWN ? nullptr : (const float*)L.actions, L.n, P.n_candidates,
+                       L.n_steps, P.discount, L.freq_rate, semi, m, (const SinCosEntry*)L.trig, L.cap_hits,
+                       DRAWN && !KEEP ? nullptr : P.return_out, DRAWN ? nullptr : P.length_out, DRAWN ? nullptr : L.obs_out, sp,
+                       DRAWN ? (PlanPartial*)P.partials : nullptr);
+}
+
 // every launch of one Body type (one translation unit instantiates exactly one Body: body_tu.hip)
 template <class Body>
 static int launch_body(const BodyLaunch& L) {
@@ -920,54 +925,24 @@ static int launch_body(const BodyLaunch& L) {
                 return EMEI_ERR_UNSUPPORTED;  // e.g. the double pendulum's observation "wrap" is not invertible
             }
         case BODY_OP_PLAN: {
-            // one lane per candidate; n * n_candidates < 2^31 (checked in abi.hip)
-            const dim3 pgrid((unsigned)((L.n * L.n_candidates + kBlock - 1) / kBlock));
-            const int semi = (int)(L.integrator == EMEI_INTEG_SEMI_IMPLICIT);
-            const SinCosEntry* tt = (const SinCosEntry*)L.trig;
-            PlanPartial* pp = (PlanPartial*)L.partials;
-            if (L.sigma_map) {  // emei_plan_cem with a sigma per entry: every return kept
-                if (!pp || !L.return_out) return EMEI_ERR_INVALID;
-                const CandidateSpecMap spm(L.cand, L.sigma_map);
-                if (L.integrator == EMEI_INTEG_RK4)
-                    hipLaunchKernelGGL((body_plan_kernel<Body, true, true, true, CandidateSpecMap>), pgrid, dim3(kBlock), 0, L.stream,
-                                       (const R*)L.state, L.start_rows, (const float*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount,
-                                       L.freq_rate, 0, m, tt, L.cap_hits, L.return_out, (int32_t*)nullptr, (float*)nullptr, spm, pp);
-                else
-                    hipLaunchKernelGGL((body_plan_kernel<Body, false, true, true, CandidateSpecMap>), pgrid, dim3(kBlock), 0, L.stream,
-                                       (const R*)L.state, L.start_rows, (const float*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount,
-                                       L.freq_rate, semi, m, tt, L.cap_hits, L.return_out, (int32_t*)nullptr, (float*)nullptr, spm, pp);
-                break;
+            const PlanLaunch& P = L.plan;
+            if (P.mode != PLAN_GIVEN && !P.partials) return EMEI_ERR_INVALID;
+            if (P.mode == PLAN_DRAWN_KEEP && !P.return_out) return EMEI_ERR_INVALID;
+            if (P.sigma_map) {  // emei_plan_cem with a sigma per entry: every return kept
+                if (P.mode != PLAN_DRAWN_KEEP) return EMEI_ERR_INVALID;
+                const CandidateSpecMap spm(P.cand, P.sigma_map);
+                if (L.integrator == EMEI_INTEG_RK4) launch_body_plan<Body, true, true, true>(L, m, spm);
+                else launch_body_plan<Body, false, true, true>(L, m, spm);
+            } else if (P.mode == PLAN_DRAWN_KEEP) {
+                if (L.integrator == EMEI_INTEG_RK4) launch_body_plan<Body, true, true, true>(L, m, P.cand);
+                else launch_body_plan<Body, false, true, true>(L, m, P.cand);
+            } else if (P.mode == PLAN_DRAWN) {
+                if (L.integrator == EMEI_INTEG_RK4) launch_body_plan<Body, true, true, false>(L, m, P.cand);
+                else launch_body_plan<Body, false, true, false>(L, m, P.cand);
+            } else {
+                if (L.integrator == EMEI_INTEG_RK4) launch_body_plan<Body, true, false, false>(L, m, P.cand);
+                else launch_body_plan<Body, false, false, false>(L, m, P.cand);
             }
-            if (pp && L.return_out) {  // emei_plan_mppi: as emei_plan_shooting, every candidate's return kept as well
-                if (L.integrator == EMEI_INTEG_RK4)
-                    hipLaunchKernelGGL((body_plan_kernel<Body, true, true, true>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state,
-                                       L.start_rows, (const float*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, 0, m,
-                                       tt, L.cap_hits, L.return_out, (int32_t*)nullptr, (float*)nullptr, L.cand, pp);
-                else
-                    hipLaunchKernelGGL((body_plan_kernel<Body, false, true, true>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state,
-                                       L.start_rows, (const float*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, semi,
-                                       m, tt, L.cap_hits, L.return_out, (int32_t*)nullptr, (float*)nullptr, L.cand, pp);
-                break;
-            }
-            if (pp) {  // emei_plan_shooting
-                if (L.integrator == EMEI_INTEG_RK4)
-                    hipLaunchKernelGGL((body_plan_kernel<Body, true, true>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state,
-                                       L.start_rows, (const float*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, 0, m,
-                                       tt, L.cap_hits, (double*)nullptr, (int32_t*)nullptr, (float*)nullptr, L.cand, pp);
-                else
-                    hipLaunchKernelGGL((body_plan_kernel<Body, false, true>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state,
-                                       L.start_rows, (const float*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, semi,
-                                       m, tt, L.cap_hits, (double*)nullptr, (int32_t*)nullptr, (float*)nullptr, L.cand, pp);
-                break;
-            }
-            if (L.integrator == EMEI_INTEG_RK4)
-                hipLaunchKernelGGL((body_plan_kernel<Body, true>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state, L.start_rows,
-                                   (const float*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, 0, m, tt,
-                                   L.cap_hits, L.return_out, L.length_out, L.obs_out, L.cand, pp);
-            else
-                hipLaunchKernelGGL((body_plan_kernel<Body, false>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state, L.start_rows,
-                                   (const float*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, semi, m, tt,
-                                   L.cap_hits, L.return_out, L.length_out, L.obs_out, L.cand, pp);
             break;
         }
         default: return EMEI_ERR_INVALID;

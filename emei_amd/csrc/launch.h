@@ -17,6 +17,26 @@ struct ObsPeers {
     int32_t max_steps = 0;  // rows of every buffer
 };
 
+// What the plan kernels of both families take beyond their base descriptor (PEND_OP_PLAN / BODY_OP_PLAN): n_candidates lanes per
+// env score `horizon` steps each from one start state.
+enum PlanMode {
+    PLAN_GIVEN = 0,   // emei_evaluate_sequences: the candidates are `actions`; return_out / length_out (and final_obs) per candidate
+    PLAN_DRAWN,       // emei_plan_shooting: the candidates are drawn in the lanes under `cand`, and the kernel leaves one PlanPartial
+                      // per (wave, env) segment in `partials` instead of return_out / length_out
+    PLAN_DRAWN_KEEP,  // emei_plan_mppi / emei_plan_cem: as PLAN_DRAWN, and every candidate's return is kept in return_out as well
+};
+struct PlanLaunch {
+    int mode = PLAN_GIVEN;
+    const double* start_rows = nullptr;  // [n, state_dim] float64; null = the handle's state
+    int32_t n_candidates = 1;
+    double discount = 1.0;
+    double* return_out = nullptr;   // [n * K]
+    int32_t* length_out = nullptr;  // [n * K]
+    CandidateSpec cand = {};
+    void* partials = nullptr;
+    const float* sigma_map = nullptr;  // emei_plan_cem: non-null -> the draws take their sigma per entry (CandidateSpecMap)
+};
+
 struct PendLaunch {
     int op = PEND_OP_ROLLOUT;
     int env_id = 0, precision = 0;
@@ -48,21 +68,11 @@ struct PendLaunch {
     uint32_t* host_flag = nullptr;
     uint32_t flag_value = 0;
     ObsPeers peers;  // PEND_OP_ROLLOUT: count > 0 -> the staged peers kernel or EMEI_ERR_UNSUPPORTED
-    // PEND_OP_PLAN (emei_evaluate_sequences): n_candidates per env, n_steps = the horizon, obs_out = final_obs [n * K, 4] or null
-    const double* start_rows = nullptr;  // [n, 4] float64; null = the handle's state
-    int32_t n_candidates = 1;
-    double discount = 1.0;
-    double* return_out = nullptr;   // [n * K]
-    int32_t* length_out = nullptr;  // [n * K]
-    // emei_plan_shooting: partials != null -> the candidates are drawn in the lanes under `cand` and the kernel leaves one
-    // PlanPartial per (wave, env) segment instead of return_out / length_out; emei_plan_mppi: with return_out != null as well, every
-    // candidate's return is kept there too
-    CandidateSpec cand = {};
-    void* partials = nullptr;
-    const float* sigma_map = nullptr;  // emei_plan_cem: non-null -> the draws take their sigma per entry (CandidateSpecMap)
-    // PEND_OP_MPC (emei_mpc_mppi): n_steps control steps of MPPI with n_candidates candidates over `horizon` steps; `cand` carries the
-    // call's seed, sigma and the ctrlrange (its nominal is unused: the kernel keeps the nominal in LDS), `seed` the handle's reset key;
-    // return_out = the workspace [n * K], actions / obs_out / reward_out / done_out as PEND_OP_ROLLOUT's outputs
+    PlanLaunch plan;  // PEND_OP_PLAN; n_steps = the horizon, obs_out = final_obs [n * K, 4] or null
+    // PEND_OP_MPC (emei_mpc_mppi): n_steps control steps of MPPI with plan.n_candidates candidates over `horizon` steps under
+    // plan.discount; plan.cand carries the call's seed, sigma and the ctrlrange (its nominal is unused: the kernel keeps the nominal
+    // in LDS), `seed` the handle's reset key; plan.return_out = the workspace [n * K], actions / obs_out / reward_out / done_out as
+    // PEND_OP_ROLLOUT's outputs
     int32_t horizon = 1;
     float* mpc_nominal = nullptr;  // in/out [horizon, n(, act_dim)]
     void* mpc_actions_out = nullptr;

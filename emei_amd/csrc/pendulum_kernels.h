@@ -989,6 +989,19 @@ static int launch_rollout_full(const RolloutArgs<Env>& a, dim3 grid, hipStream_t
     return EMEI_KERNEL_PEND_GENERIC;
 }
 
+// the one launch of pend_plan_kernel: DRAWN kernels read no actions and write no lengths or final observations, and only KEEP
+// gives them a return_out; one lane per candidate, n * n_candidates < 2^31 (checked in abi.hip)
+template <class Env, class ActT, bool DRAWN, bool KEEP, class Spec>
+static void launch_pend_plan(const PendLaunch& L, const RolloutArgs<Env>& a, const Spec& sp) {
+    const PlanLaunch& P = L.plan;
+    const dim3 pgrid((unsigned)((L.n * P.n_candidates + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL((pend_plan_kernel<Env, ActT, DRAWN, KEEP, Spec>), pgrid, dim3(kBlock), 0, L.stream,
+                       (const typename Env::real*)L.state, P.start_rows, DRAWN ? nullptr : (const ActT*)L.actions, L.n, P.n_candidates,
+                       L.n_steps, P.discount, L.freq_rate, a.p, a.trig, DRAWN && !KEEP ? nullptr : P.return_out,
+                       DRAWN ? nullptr : P.length_out, DRAWN ? nullptr : (float4*)L.obs_out, sp,
+                       DRAWN ? (PlanPartial*)P.partials : nullptr);
+}
+
 // host-side dispatch over (env id, precision)
 // every launch of one Env type (one translation unit instantiates exactly one Env: pendulum_tu.hip)
 template <class Env>
@@ -1064,68 +1077,49 @@ static int launch_env(const PendLaunch& L) {
                                    L.actions, L.action_dtype, (float*)L.obs_out, L.n, L.freq_rate, a.p, a.trig);
             break;
         case PEND_OP_PLAN: {
-            // one lane per candidate; n * n_candidates < 2^31 (checked in abi.hip)
-            const dim3 pgrid((unsigned)((L.n * L.n_candidates + kBlock - 1) / kBlock));
-            const R* st = (const R*)L.state;
-            if (L.partials) {  // emei_plan_shooting: candidates drawn in the lanes, one partial per (wave, env) segment
-                using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
-                if (L.sigma_map) {  // emei_plan_cem with a sigma per entry: continuous envs, every return kept
-                    if constexpr (!Env::kDiscrete) {
-                        if (!L.return_out) return EMEI_ERR_INVALID;
-                        hipLaunchKernelGGL((pend_plan_kernel<Env, DrawT, true, true, CandidateSpecMap>), pgrid, dim3(kBlock), 0, L.stream, st,
-                                           L.start_rows, (const DrawT*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p,
-                                           a.trig, L.return_out, (int32_t*)nullptr, (float4*)nullptr, CandidateSpecMap(L.cand, L.sigma_map),
-                                           (PlanPartial*)L.partials);
-                        break;
-                    } else {
-                        return EMEI_ERR_INVALID;
-                    }
+            const PlanLaunch& P = L.plan;
+            if (P.mode == PLAN_GIVEN) {
+                // discrete envs take uint8/int32/int64 actions, continuous envs float32
+                const CandidateSpec none{};
+                if constexpr (Env::kDiscrete) {
+                    if (L.action_dtype == EMEI_ACT_U8) launch_pend_plan<Env, uint8_t, false, false>(L, a, none);
+                    else if (L.action_dtype == EMEI_ACT_I32) launch_pend_plan<Env, int32_t, false, false>(L, a, none);
+                    else if (L.action_dtype == EMEI_ACT_I64) launch_pend_plan<Env, int64_t, false, false>(L, a, none);
+                    else return EMEI_ERR_INVALID;
+                } else {
+                    if (L.action_dtype != EMEI_ACT_F32) return EMEI_ERR_INVALID;
+                    launch_pend_plan<Env, float, false, false>(L, a, none);
                 }
-                if (L.return_out) {  // emei_plan_mppi: every candidate's return is kept as well
-                    hipLaunchKernelGGL((pend_plan_kernel<Env, DrawT, true, true>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
-                                       (const DrawT*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p, a.trig,
-                                       L.return_out, (int32_t*)nullptr, (float4*)nullptr, L.cand, (PlanPartial*)L.partials);
-                    break;
-                }
-                hipLaunchKernelGGL((pend_plan_kernel<Env, DrawT, true>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
-                                   (const DrawT*)nullptr, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p, a.trig,
-                                   (double*)nullptr, (int32_t*)nullptr, (float4*)nullptr, L.cand, (PlanPartial*)L.partials);
                 break;
             }
-            const CandidateSpec none{};
-            if constexpr (Env::kDiscrete) {
-                if (L.action_dtype == EMEI_ACT_U8)
-                    hipLaunchKernelGGL((pend_plan_kernel<Env, uint8_t>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
-                                       (const uint8_t*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p,
-                                       a.trig, L.return_out, L.length_out, (float4*)L.obs_out, none, (PlanPartial*)nullptr);
-                else if (L.action_dtype == EMEI_ACT_I32)
-                    hipLaunchKernelGGL((pend_plan_kernel<Env, int32_t>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
-                                       (const int32_t*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p,
-                                       a.trig, L.return_out, L.length_out, (float4*)L.obs_out, none, (PlanPartial*)nullptr);
-                else if (L.action_dtype == EMEI_ACT_I64)
-                    hipLaunchKernelGGL((pend_plan_kernel<Env, int64_t>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
-                                       (const int64_t*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p,
-                                       a.trig, L.return_out, L.length_out, (float4*)L.obs_out, none, (PlanPartial*)nullptr);
-                else return EMEI_ERR_INVALID;
+            using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
+            if (!P.partials) return EMEI_ERR_INVALID;
+            if (P.mode == PLAN_DRAWN_KEEP && !P.return_out) return EMEI_ERR_INVALID;
+            if (P.sigma_map) {  // emei_plan_cem with a sigma per entry: continuous envs, every return kept
+                if constexpr (!Env::kDiscrete) {
+                    if (P.mode != PLAN_DRAWN_KEEP) return EMEI_ERR_INVALID;
+                    launch_pend_plan<Env, DrawT, true, true>(L, a, CandidateSpecMap(P.cand, P.sigma_map));
+                } else {
+                    return EMEI_ERR_INVALID;
+                }
+            } else if (P.mode == PLAN_DRAWN_KEEP) {
+                launch_pend_plan<Env, DrawT, true, true>(L, a, P.cand);
             } else {
-                if (L.action_dtype != EMEI_ACT_F32) return EMEI_ERR_INVALID;
-                hipLaunchKernelGGL((pend_plan_kernel<Env, float>), pgrid, dim3(kBlock), 0, L.stream, st, L.start_rows,
-                                   (const float*)L.actions, L.n, L.n_candidates, L.n_steps, L.discount, L.freq_rate, a.p, a.trig,
-                                   L.return_out, L.length_out, (float4*)L.obs_out, none, (PlanPartial*)nullptr);
+                launch_pend_plan<Env, DrawT, true, false>(L, a, P.cand);
             }
             break;
         }
         case PEND_OP_MPC: {
             MpcArgs<Env> m;
             m.state = (R*)L.state, m.steps = L.steps, m.episode = L.episode, m.trig = a.trig;
-            m.nominal = L.mpc_nominal, m.work = L.return_out, m.actions_out = L.mpc_actions_out;
+            m.nominal = L.mpc_nominal, m.work = L.plan.return_out, m.actions_out = L.mpc_actions_out;
             m.obs_out = (float4*)L.obs_out, m.reward_out = L.reward_out, m.done_out = L.done_out;
             m.plan_return_out = L.plan_return_out, m.ess_out = L.ess_out;
-            m.n = L.n, m.n_steps = L.n_steps, m.horizon = L.horizon, m.n_cand = L.n_candidates, m.freq_rate = L.freq_rate;
+            m.n = L.n, m.n_steps = L.n_steps, m.horizon = L.horizon, m.n_cand = L.plan.n_candidates, m.freq_rate = L.freq_rate;
             m.action_dtype = L.action_dtype, m.max_episode_steps = L.max_episode_steps, m.flags = L.flags;
-            m.reset_seed = L.seed, m.env_offset = L.env_offset, m.seed = L.cand.seed;
-            m.discount = L.discount, m.temperature = L.temperature;
-            m.sigma = L.cand.sigma, m.lo = L.cand.lo, m.hi = L.cand.hi;
+            m.reset_seed = L.seed, m.env_offset = L.env_offset, m.seed = L.plan.cand.seed;
+            m.discount = L.plan.discount, m.temperature = L.temperature;
+            m.sigma = L.plan.cand.sigma, m.lo = L.plan.cand.lo, m.hi = L.plan.cand.hi;
             m.refill = L.refill, m.nominal_lo = L.nominal_lo, m.nominal_hi = L.nominal_hi;
             m.p = a.p;
             if (L.horizon < 1 || L.horizon > EMEI_MPC_MAX_HORIZON) return EMEI_ERR_INVALID;  // the LDS slice of the nominal

@@ -37,6 +37,11 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _seed64(seed):
+    """a Python int as the ABI's uint64_t seed"""
+    return int(seed) & (2**64 - 1)
+
+
 def env_dims(env_name):
     od, ad, sd = C.c_int(), C.c_int(), C.c_int()
     L.check(L.lib().emei_env_dims(L.ENV_IDS[env_name], C.byref(od), C.byref(ad), C.byref(sd)))
@@ -139,11 +144,11 @@ class Engine:
     # -- state ---------------------------------------------------------------------------------
     @_on_device
     def reset(self, seed=0):
-        L.check(L.lib().emei_reset(self._h, int(seed) & (2**64 - 1), _stream()))
+        L.check(L.lib().emei_reset(self._h, _seed64(seed), _stream()))
 
     def set_seed(self, seed):
         """Re-key the device reset generator (auto-reset episodes) without touching the state."""
-        L.check(L.lib().emei_set_seed(self._h, int(seed) & (2**64 - 1)))
+        L.check(L.lib().emei_set_seed(self._h, _seed64(seed)))
 
     @_on_device
     def solver_cap_hits(self):
@@ -210,6 +215,23 @@ class Engine:
     @_on_device
     def unfreeze(self):
         L.check(L.lib().emei_unfreeze(self._h, _stream()))
+
+    @property
+    def _act_tail(self):
+        """the trailing dimensions of an action array: (act_dim,) for act_dim > 1, nothing otherwise"""
+        return (self.act_dim,) if self.act_dim > 1 else ()
+
+    def _workspace(self, attr, size_fn, K):
+        """the cached device workspace `attr` of a plan call, at least size_fn(n_envs, K) bytes: grow-only (a captured graph keeps
+        using the tensor it was captured with), float64 elements (8-byte aligned records), one per method"""
+        need = int(size_fn(self.n_envs, K))
+        if need < 0:
+            L.check(need)
+        ws = getattr(self, attr, None)
+        if ws is None or ws.numel() * 8 < need:
+            ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+            setattr(self, attr, ws)
+        return ws
 
     # -- hot path ------------------------------------------------------------------------------
     def _check_actions(self, actions, lead):
@@ -378,18 +400,14 @@ class Engine:
         sigma: a float, or a float32 tensor of nominal's shape with one sigma per entry (emei_sample_candidates_sigma: what
         plan_cem(sigma=tensor) draws; an entry of 0 gives the clipped mean).
         dtype: uint8 / int32 / int64 (discrete; the default int64) or float32."""
-        if isinstance(sigma, torch.Tensor):
-            H, K, nominal, _, dtype = self._candidate_args(H, K, nominal, 1.0, dtype)
-            sigma = self._sigma_map(nominal, sigma)
-            out = torch.empty((H, self.n_envs, K) + ((self.act_dim,) if self.act_dim > 1 else ()), dtype=dtype, device=self.device)
-            L.check(L.lib().emei_sample_candidates_sigma(self._h, H, K, int(seed) & (2**64 - 1), _ptr(nominal), _ptr(sigma), _ptr(out),
-                                                         _ACT_DTYPES[dtype], _stream()))
-            return out
-        H, K, nominal, sigma, dtype = self._candidate_args(H, K, nominal, sigma, dtype)
-        shape = (H, self.n_envs, K) + ((self.act_dim,) if self.act_dim > 1 else ())
-        out = torch.empty(shape, dtype=dtype, device=self.device)
-        L.check(L.lib().emei_sample_candidates(self._h, H, K, int(seed) & (2**64 - 1), _ptr(nominal), sigma, _ptr(out),
-                                               _ACT_DTYPES[dtype], _stream()))
+        is_map = isinstance(sigma, torch.Tensor)
+        H, K, nominal, scalar, dtype = self._candidate_args(H, K, nominal, 1.0 if is_map else sigma, dtype)
+        if is_map:
+            fn, sig = L.lib().emei_sample_candidates_sigma, _ptr(self._sigma_map(nominal, sigma))
+        else:
+            fn, sig = L.lib().emei_sample_candidates, scalar
+        out = torch.empty((H, self.n_envs, K) + self._act_tail, dtype=dtype, device=self.device)
+        L.check(fn(self._h, H, K, _seed64(seed), _ptr(nominal), sig, _ptr(out), _ACT_DTYPES[dtype], _stream()))
         return out
 
     @_on_device
@@ -402,19 +420,14 @@ class Engine:
         everything.  The handle is left as it is.  Arguments as sample_candidates."""
         H, K, nominal, sigma, dtype = self._candidate_args(H, K, nominal, sigma, dtype)
         st = self._start_rows(start_state)
-        need = int(L.lib().emei_plan_shooting_workspace_bytes(self.n_envs, K))
-        if need < 0:
-            L.check(need)
-        ws = getattr(self, "_plan_ws", None)
-        if ws is None or ws.numel() * 8 < need:  # grow-only (float64 elements: 8-byte aligned records)
-            ws = self._plan_ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
-        tail = (self.act_dim,) if self.act_dim > 1 else ()
+        ws = self._workspace("_plan_ws", L.lib().emei_plan_shooting_workspace_bytes, K)
+        tail = self._act_tail
         act = torch.empty((self.n_envs,) + tail, dtype=dtype, device=self.device)
         seq = torch.empty((H, self.n_envs) + tail, dtype=dtype, device=self.device) if sequence else None
         ret = torch.empty(self.n_envs, dtype=torch.float64, device=self.device)
         idx = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
         ln = torch.empty(self.n_envs, dtype=torch.int32, device=self.device) if length else None
-        L.check(L.lib().emei_plan_shooting(self._h, H, K, int(seed) & (2**64 - 1), _ptr(nominal), sigma, float(discount), _ptr(st),
+        L.check(L.lib().emei_plan_shooting(self._h, H, K, _seed64(seed), _ptr(nominal), sigma, float(discount), _ptr(st),
                                            _ptr(ws), _ptr(act), _ACT_DTYPES[dtype], _ptr(seq), _ptr(ret), _ptr(idx), _ptr(ln),
                                            _stream()))
         return (act, ret, idx) + ((seq,) if sequence else ()) + ((ln,) if length else ())
@@ -431,21 +444,16 @@ class Engine:
         H, K, nominal, sigma, _ = self._candidate_args(H, K, nominal, sigma, None)
         temperature = float(temperature)
         st = self._start_rows(start_state)
-        shape = (H, self.n_envs) + ((self.act_dim,) if self.act_dim > 1 else ())
+        shape = (H, self.n_envs) + self._act_tail
         if out is None:
             out = torch.empty(shape if nominal is None else tuple(nominal.shape), dtype=torch.float32, device=self.device)
         else:
             self._check_plan_out("out", out, shape, nominal, "nominal")
-        need = int(L.lib().emei_plan_mppi_workspace_bytes(self.n_envs, K))
-        if need < 0:
-            L.check(need)
-        ws = getattr(self, "_mppi_ws", None)
-        if ws is None or ws.numel() * 8 < need:  # grow-only (float64 elements: 8-byte aligned records)
-            ws = self._mppi_ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+        ws = self._workspace("_mppi_ws", L.lib().emei_plan_mppi_workspace_bytes, K)
         ret = torch.empty(self.n_envs, dtype=torch.float64, device=self.device)
         idx = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
         es = torch.empty(self.n_envs, dtype=torch.float64, device=self.device) if ess else None
-        L.check(L.lib().emei_plan_mppi(self._h, H, K, int(seed) & (2**64 - 1), _ptr(nominal), sigma, float(discount), temperature,
+        L.check(L.lib().emei_plan_mppi(self._h, H, K, _seed64(seed), _ptr(nominal), sigma, float(discount), temperature,
                                        _ptr(st), _ptr(ws), _ptr(out), _ptr(ret), _ptr(idx), _ptr(es), _stream()))
         return (out, ret, idx) + ((es,) if ess else ())
 
@@ -474,16 +482,11 @@ class Engine:
             clamp = (0.05, 0.95) if self.act_dim == 0 else _CTRL_RANGE.get(self.env_name, (-1.0, 1.0))
         lo, hi = float(clamp[0]), float(clamp[1])
         obs, rew, done = self._check_outputs(out, (T,)) if out is not None else self.alloc_outputs(T)
-        need = int(L.lib().emei_mpc_mppi_workspace_bytes(self.n_envs, K))
-        if need < 0:
-            L.check(need)
-        ws = getattr(self, "_mpc_ws", None)
-        if ws is None or ws.numel() * 8 < need:  # grow-only
-            ws = self._mpc_ws = torch.empty(need // 8, dtype=torch.float64, device=self.device)
-        act = torch.empty((T, self.n_envs) + ((self.act_dim,) if self.act_dim > 1 else ()), dtype=dtype, device=self.device)
+        ws = self._workspace("_mpc_ws", L.lib().emei_mpc_mppi_workspace_bytes, K)
+        act = torch.empty((T, self.n_envs) + self._act_tail, dtype=dtype, device=self.device)
         pr = torch.empty((T, self.n_envs), dtype=torch.float64, device=self.device) if diagnostics else None
         es = torch.empty((T, self.n_envs), dtype=torch.float64, device=self.device) if diagnostics else None
-        L.check(L.lib().emei_mpc_mppi(self._h, T, H, K, int(seed) & (2**64 - 1), _ptr(nominal), sigma, float(discount), float(temperature),
+        L.check(L.lib().emei_mpc_mppi(self._h, T, H, K, _seed64(seed), _ptr(nominal), sigma, float(discount), float(temperature),
                                       float(refill), lo, hi, _ptr(ws), _ptr(act), _ACT_DTYPES[dtype], _ptr(obs), _ptr(rew), _ptr(done),
                                       _ptr(pr), _ptr(es), L.FLAG_AUTO_RESET if auto_reset else 0, _stream()))
         return (act, obs, rew, done) + ((pr, es) if diagnostics else ())
@@ -519,7 +522,7 @@ class Engine:
         if not 1 <= n_elites <= K:
             raise ValueError(f"n_elites={n_elites} is outside [1, n_candidates={K}]")
         st = self._start_rows(start_state)
-        shape = (H, self.n_envs) + ((self.act_dim,) if self.act_dim > 1 else ())
+        shape = (H, self.n_envs) + self._act_tail
         like = shape if nominal is None else tuple(nominal.shape)
         if out is None:
             out = torch.empty(like, dtype=torch.float32, device=self.device)
@@ -532,16 +535,11 @@ class Engine:
             out_sigma = torch.empty(like, dtype=torch.float32, device=self.device)
         else:
             self._check_plan_out("out_sigma", out_sigma, shape, sigma_map, "the sigma tensor")
-        need = int(L.lib().emei_plan_cem_workspace_bytes(self.n_envs, K))
-        if need < 0:
-            L.check(need)
-        ws = getattr(self, "_cem_ws", None)
-        if ws is None or ws.numel() * 8 < need:  # grow-only (float64 elements: 8-byte aligned records)
-            ws = self._cem_ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+        ws = self._workspace("_cem_ws", L.lib().emei_plan_cem_workspace_bytes, K)
         ret = torch.empty(self.n_envs, dtype=torch.float64, device=self.device)
         idx = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
         er = torch.empty(self.n_envs, dtype=torch.float64, device=self.device) if elite_return else None
-        L.check(L.lib().emei_plan_cem(self._h, H, K, n_elites, int(seed) & (2**64 - 1), _ptr(nominal), sigma, _ptr(sigma_map),
+        L.check(L.lib().emei_plan_cem(self._h, H, K, n_elites, _seed64(seed), _ptr(nominal), sigma, _ptr(sigma_map),
                                       float(discount), _ptr(st), _ptr(ws), _ptr(out), _ptr(out_sigma), _ptr(ret), _ptr(idx), _ptr(er),
                                       _stream()))
         return (out, out_sigma, ret, idx) + ((er,) if elite_return else ())

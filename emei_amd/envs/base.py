@@ -266,6 +266,16 @@ class HipEnv(EmeiEnv):
     def get_batch_init_state(self, batch_size):
         return self._host_init_state(batch_size)
 
+    def _as_device(self, x, dtype):
+        """an optional array argument of the plan calls (NumPy, tensor or nested lists) -> None, or a contiguous tensor of `dtype` on
+        the engine's device (the caller's own tensor when it already is one)"""
+        import torch
+
+        if x is None:
+            return None
+        x = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+        return x.to(device=self.engine.device, dtype=dtype).contiguous()
+
     def evaluate_action_sequences(self, actions, discount=1.0, start_state=None, final_obs=False):
         """The query a planner asks of the true dynamics (random shooting, CEM, MPPI; core.py:18-37,190-193 serve model-based
         callers with freeze() and get_batch_next_obs): K candidate action sequences per env scored from the envs' current
@@ -284,10 +294,7 @@ class HipEnv(EmeiEnv):
             a = a.to(torch.int64)
         if eng.act_dim > 0:
             a = a.to(torch.float32)
-        st = None
-        if start_state is not None:
-            st = start_state if isinstance(start_state, torch.Tensor) else torch.as_tensor(np.asarray(start_state))
-            st = st.to(device=eng.device, dtype=torch.float64).contiguous()
+        st = self._as_device(start_state, torch.float64)
         out = eng.evaluate_sequences(a.contiguous(), discount=discount, start_state=st, final_obs=final_obs)
         if isinstance(actions, torch.Tensor):
             return out
@@ -309,13 +316,7 @@ class HipEnv(EmeiEnv):
         assert self.state is not None, "Call reset before using step method."  # base_control.py:67
         eng = self.engine
         as_numpy = isinstance(nominal, np.ndarray) or isinstance(start_state, np.ndarray)
-        nom = st = None
-        if nominal is not None:
-            nom = nominal if isinstance(nominal, torch.Tensor) else torch.as_tensor(np.asarray(nominal))
-            nom = nom.to(device=eng.device, dtype=torch.float32).contiguous()
-        if start_state is not None:
-            st = start_state if isinstance(start_state, torch.Tensor) else torch.as_tensor(np.asarray(start_state))
-            st = st.to(device=eng.device, dtype=torch.float64).contiguous()
+        nom, st = self._as_device(nominal, torch.float32), self._as_device(start_state, torch.float64)
         out = eng.plan_shooting(horizon, n_candidates, seed, discount=discount, nominal=nom, sigma=sigma, start_state=st,
                                 sequence=sequence, length=length, dtype=dtype)
         return tuple(t.cpu().numpy() for t in out) if as_numpy else out
@@ -335,13 +336,7 @@ class HipEnv(EmeiEnv):
         assert self.state is not None, "Call reset before using step method."  # base_control.py:67
         eng = self.engine
         as_numpy = isinstance(nominal, np.ndarray) or isinstance(start_state, np.ndarray)
-        nom = st = None
-        if nominal is not None:
-            nom = nominal if isinstance(nominal, torch.Tensor) else torch.as_tensor(np.asarray(nominal))
-            nom = nom.to(device=eng.device, dtype=torch.float32).contiguous()
-        if start_state is not None:
-            st = start_state if isinstance(start_state, torch.Tensor) else torch.as_tensor(np.asarray(start_state))
-            st = st.to(device=eng.device, dtype=torch.float64).contiguous()
+        nom, st = self._as_device(nominal, torch.float32), self._as_device(start_state, torch.float64)
         res = eng.plan_mppi(horizon, n_candidates, seed, temperature, discount=discount, nominal=nom, sigma=sigma, start_state=st,
                             out=out, ess=ess)
         return tuple(t.cpu().numpy() for t in res) if as_numpy else res
@@ -362,8 +357,7 @@ class HipEnv(EmeiEnv):
         assert self.state is not None, "Call reset before using step method."  # base_control.py:67
         eng = self.engine
         as_numpy = not isinstance(nominal, torch.Tensor)
-        nom = nominal if isinstance(nominal, torch.Tensor) else torch.as_tensor(np.asarray(nominal))
-        nom = nom.to(device=eng.device, dtype=torch.float32).contiguous()
+        nom = self._as_device(nominal, torch.float32)
         res = eng.mpc_mppi(n_steps, horizon, n_candidates, seed, temperature, nom, discount=discount, sigma=sigma, refill=refill,
                            clamp=clamp, auto_reset=self.auto_reset if auto_reset is None else auto_reset, diagnostics=diagnostics)
         act, obs, rew, done = res[:4]
@@ -394,8 +388,7 @@ class HipEnv(EmeiEnv):
         as_numpy = any(isinstance(x, np.ndarray) for x in (nominal, sigma, start_state))
 
         def own(x, dtype):  # a device copy the iterations may write
-            x = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-            return x.to(device=eng.device, dtype=dtype).contiguous().clone()
+            return self._as_device(x, dtype).clone()
 
         mean = None if nominal is None else own(nominal, torch.float32)
         std = own(sigma, torch.float32) if isinstance(sigma, (torch.Tensor, np.ndarray)) else sigma
