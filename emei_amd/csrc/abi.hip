@@ -989,6 +989,68 @@ extern "C" EMEI_API int emei_mpc_mppi(emei_env* h, int32_t n_steps, int32_t hori
     return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
 }
 
+// ---------------------------------------------------------------------------------------------
+// emei_mpc_cem: n_steps control steps of "`iterations` times emei_plan_cem in place, act, emei_step, shift" in one kernel of one wave
+// per env (pendulum_kernels.h:pend_mpc_cem_kernel), then emei_mpc_mppi's done-mask launch.
+extern "C" EMEI_API int64_t emei_mpc_cem_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
+    const int64_t nk = check_plan_shape("emei_mpc_cem_workspace_bytes", n_envs, n_candidates);
+    return nk < 0 ? nk : (int64_t)sizeof(double) * nk;  // every candidate's return, then its membership flag
+}
+
+extern "C" EMEI_API int emei_mpc_cem(emei_env* h, int32_t n_steps, int32_t horizon, int32_t n_candidates, int32_t n_elites,
+                                     int32_t iterations, uint64_t seed, float* nominal, double sigma, double sigma_min, double discount,
+                                     float refill, float nominal_lo, float nominal_hi, void* workspace, void* actions_out,
+                                     int action_dtype, float* obs_out, float* reward_out, uint8_t* done_out, double* plan_return_out,
+                                     double* elite_return_out, uint32_t flags, void* stream) {
+    const char* fn = "emei_mpc_cem";
+    if (n_steps < 1) return fail(EMEI_ERR_INVALID, "%s: n_steps=%d < 1", fn, n_steps);
+    // n_elites is refused after horizon and n_candidates, before discount (as emei_plan_cem)
+    if (horizon >= 1 && n_candidates >= 1 && (n_elites < 1 || n_elites > n_candidates))
+        return fail(EMEI_ERR_INVALID, "%s: n_elites=%d is outside [1, n_candidates=%d]", fn, n_elites, n_candidates);
+    if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
+    if (iterations < 1) return fail(EMEI_ERR_INVALID, "%s: iterations=%d < 1", fn, iterations);
+    if (!std::isfinite(refill)) return fail(EMEI_ERR_INVALID, "%s: refill=%g must be finite", fn, (double)refill);
+    if (!(nominal_lo <= nominal_hi))  // also refuses a NaN bound
+        return fail(EMEI_ERR_INVALID, "%s: nominal_lo=%g, nominal_hi=%g: need nominal_lo <= nominal_hi", fn, (double)nominal_lo,
+                    (double)nominal_hi);
+    if (!(std::isfinite(sigma_min) && sigma_min >= 0.0))
+        return fail(EMEI_ERR_INVALID, "%s: sigma_min=%g must be finite and >= 0", fn, sigma_min);
+    if (horizon > EMEI_MPC_MAX_HORIZON)
+        return fail(EMEI_ERR_INVALID, "%s: horizon=%d exceeds EMEI_MPC_MAX_HORIZON=%d (the mean and the sigma live in LDS)", fn, horizon,
+                    EMEI_MPC_MAX_HORIZON);
+    // every control step starts from the scalar sigma, so it always counts
+    if (int rc = check_candidates(fn, h, horizon, n_candidates, true, sigma)) return rc;
+    if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
+    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "%s: unknown flags 0x%x", fn, flags);
+    if (!nominal) return fail(EMEI_ERR_INVALID, "%s: null nominal", fn);
+    if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
+    if (!actions_out) return fail(EMEI_ERR_INVALID, "%s: null actions_out", fn);
+    EMEI_ON_DEVICE(h, fn);
+    if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    if (steps_as_body(h->cfg))
+        return fail(EMEI_ERR_UNSUPPORTED, "%s: this handle steps on the body kernels (a multi-body env, or an InvertedPendulum with "
+                                          "a non-euler integrator or observation noise); the fused controller serves the 4-state kernels only",
+                    fn);
+    if (h->peers.count > 0)
+        return fail(EMEI_ERR_UNSUPPORTED, "%s: observation peers are set (emei_set_obs_peers), which this kernel does not serve", fn);
+    PendLaunch L = pend_base(h, stream);
+    L.op = PEND_OP_MPC_CEM;
+    L.n_steps = n_steps, L.horizon = horizon, L.n_elites = n_elites, L.iterations = iterations;
+    L.plan.n_candidates = n_candidates, L.plan.discount = discount;
+    L.plan.cand = candidate_spec(h, seed, nullptr, sigma);  // the kernel keeps the mean and the sigma in LDS
+    L.sigma_min = (float)sigma_min;
+    L.mpc_nominal = nominal, L.plan.return_out = (double*)workspace;
+    L.mpc_actions_out = actions_out, L.action_dtype = action_dtype;
+    L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
+    L.plan_return_out = plan_return_out, L.elite_return_out = elite_return_out;
+    L.refill = refill, L.nominal_lo = nominal_lo, L.nominal_hi = nominal_hi;
+    L.flags = flags;
+    L.selected = &h->last_kernel;
+    int rc = pend_launch(L);
+    if (rc == EMEI_OK) rc = launch_mpc_done_pack((const double*)workspace, n_candidates, h->cfg.n_envs, h->done_mask, (hipStream_t)stream);
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+}
+
 extern "C" EMEI_API int emei_compact_done(emei_env* h, int32_t* idx_out, int32_t* count_out, void* stream) {
     if (!h || !idx_out || !count_out) return fail(EMEI_ERR_INVALID, "emei_compact_done: null argument");
     EMEI_ON_DEVICE(h, "emei_compact_done");

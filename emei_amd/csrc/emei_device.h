@@ -678,6 +678,14 @@ __device__ __forceinline__ bool plan_beats(double x, double y) { return x > y ||
 __device__ __forceinline__ bool plan_replaces(double ra, int32_t ka, double rb, int32_t kb) {  // does (rb, kb) replace (ra, ka)?
     return plan_beats(rb, ra) || (!plan_beats(ra, rb) && kb < ka);
 }
+// The planner's order as a 64-bit key (the elite selection of emei_plan_cem / emei_mpc_cem): key(a) > key(b) <=> a comes before b
+// whatever their k, key(a) == key(b) <=> neither beats the other (+0.0 and -0.0 one key, every NaN the key 0 below -inf's 0x000f..f;
+// the usual sign-flip map otherwise).
+__device__ __forceinline__ uint64_t plan_key(double r) {
+    if (r != r) return 0ull;
+    const uint64_t b = (uint64_t)__double_as_longlong(r + 0.0);  // -0.0 + 0.0 = +0.0
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
 // End of a plan kernel: lane l of the wave holds candidate j = wave base + l, k = j % n_cand of env i = j / n_cand (lanes with
 // j >= nk hold nothing and may have left).  Segmented suffix reduction by env over the wave's lanes (log2(64) shuffle steps: at
 // step d lane l takes in lane l + d, which by then covers candidates j + d .. j + 2d - 1 of ITS env), then the first lane of every

@@ -7,7 +7,7 @@
 
 namespace emei {
 
-enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC };
+enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC, PEND_OP_MPC_CEM };
 
 // emei_set_obs_peers: the gathered buffers the staged rollout kernel also writes every observation row to
 struct ObsPeers {
@@ -80,6 +80,12 @@ struct PendLaunch {
     double* ess_out = nullptr;          // [n_steps, n] or null
     double temperature = 1.0;
     float refill = 0.f, nominal_lo = 0.f, nominal_hi = 0.f;
+    // PEND_OP_MPC_CEM (emei_mpc_cem): PEND_OP_MPC's fields with the cross-entropy method as the planner — `iterations` refits to the
+    // n_elites best candidates per control step, plan.cand.sigma the width every control step starts from, sigma_min the floor of the
+    // refitted one; elite_return_out [n_steps, n] or null takes ess_out's place, temperature is unused
+    int32_t n_elites = 1, iterations = 1;
+    float sigma_min = 0.f;
+    double* elite_return_out = nullptr;
 };
 
 // pendulum_kernels.hip
@@ -92,7 +98,7 @@ const void* emei_trig_table(int device);
 int launch_state_unpack(const double* aos, void* soa, int precision, int64_t n, int dim, hipStream_t s);
 int launch_state_pack(const void* soa, double* aos, int precision, int64_t n, int dim, hipStream_t s);
 int launch_compact_done(const unsigned long long* masks, int64_t n, int32_t* idx_out, int32_t* count_out, hipStream_t s);
-// emei_mpc_mppi's follow-up: env i's last done code (word 0 of its workspace row of `stride` doubles) -> one ballot word per 64 envs
+// emei_mpc_mppi's and emei_mpc_cem's follow-up: env i's last done code (word 0 of its workspace row of `stride` doubles) -> one ballot word per 64 envs
 int launch_mpc_done_pack(const double* work, int64_t stride, int64_t n, unsigned long long* done_mask, hipStream_t s);
 // emei_sample_candidates / the second launch of emei_plan_shooting (act_dim 0: a discrete env)
 int launch_sample_candidates(const CandidateSpec& sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim, void* actions_out,

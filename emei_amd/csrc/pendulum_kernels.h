@@ -910,6 +910,295 @@ __global__ void __launch_bounds__(kBlock) pend_mpc_mppi_kernel(const MpcArgs<Env
 }
 
 // ---------------------------------------------------------------------------------------------
+// emei_mpc_cem: receding-horizon CEM control episodes in ONE launch (the normative text: include/emei_hip.h).
+// draw_action's sigma-map Spec with the mean AND the sigma in LDS (the continuous envs; the discrete ones keep CandidateSpecLds: the
+// sigma-map path of draw_action has no coin-flip branch).  Both slices are always "there": see LdsNominal.
+struct CandidateSpecLdsMap {
+    static constexpr bool kSigmaMap = true;
+    uint64_t seed, env_offset;
+    LdsNominal nominal, sigma_map;
+    float lo, hi;
+};
+
+template <class Env>
+struct MpcCemArgs {
+    typename Env::real* state;  // SoA: 4 arrays of n
+    int32_t* steps;
+    uint32_t* episode;
+    const SinCosEntry* trig;
+    float* nominal;  // in/out [horizon, n(, act_dim)]
+    double* work;    // [n, n_cand] returns, then membership flags; word 0 of env i's row ends as its last done code (mpc_done_pack_kernel)
+    void* actions_out;
+    float4* obs_out;
+    float* reward_out;
+    uint8_t* done_out;
+    double* plan_return_out;
+    double* elite_return_out;
+    int64_t n;
+    int32_t n_steps, horizon, n_cand, n_elites, iterations, freq_rate, action_dtype, max_episode_steps;
+    uint32_t flags;
+    uint64_t reset_seed, env_offset, seed;
+    double discount;
+    float sigma, sigma_min, lo, hi, refill, nominal_lo, nominal_hi;
+    typename Env::Params p;
+};
+
+// pend_mpc_mppi_kernel's layout — one WAVE per env for all n_steps control steps, lane l owning the candidates k = l, l + 64, ..., the
+// real state and its carry in registers, the mean in the wave's LDS slice — with the planner replaced.  Per control step, `iterations`
+// times:
+//   (a, b) the lanes clamp the mean and, in the first iteration, set the sigma slice (a second LDS slice per wave) to the scalar;
+//   (c) every lane scores its candidates as pend_mpc_mppi_kernel does (pend_plan_kernel's DRAWN loop, the draws reading mean and sigma
+//       from LDS), keeps the returns in `work` and folds (k*, r*);
+//       the elite set is plan_cem_finish_kernel's: the MSB-first radix select over plan_key (eight passes, 256 LDS counters per wave,
+//       a suffix scan over the lanes), then membership row by row (ballot + prefix popcount, ties to the lower k), the flag written
+//       over the return and read back by the lane that wrote it only;
+//       the moments are that kernel's step 4, copied rather than shared: the members alone redrawn, d = (double)a - m0, S1 / S2 per
+//       lane in ascending k, the butterfly, m0 + S1 / M and sqrt(max(S2 / M - mu^2, 0)); lane 0 writes mean and sigma into LDS behind a
+//       fence, so that every lane's draws of that block have read the old entries (the in-place rule);
+//   (d) the lanes floor the sigma.
+// Then act, step, auto-reset and shift: pend_mpc_mppi_kernel's steps 4 and 5.
+// stage_trig_table's block barrier is taken by every wave, also by those past n; after it the waves of a block run different trip
+// counts, so there is NO block barrier (plan_cem_finish_kernel's __syncthreads() around the counters become wave_lds_fence(): the
+// counters are per wave, and a wave's LDS operations — the ds_add of the histogram included — execute in order).
+template <class Env>
+__global__ void __launch_bounds__(kBlock) pend_mpc_cem_kernel(const MpcCemArgs<Env> a) {
+    using R = typename Env::real;
+    using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
+    using Spec = typename std::conditional<Env::kDiscrete, CandidateSpecLds, CandidateSpecLdsMap>::type;
+    constexpr bool kMap = !Env::kDiscrete;
+    constexpr int kWavesPerBlock = kBlock / kWave;
+    constexpr int na = Env::kActDim;                          // components per step of the mean
+    constexpr int act_dim = Env::kDiscrete ? 0 : Env::kActDim;  // draw_action's: 0 = coin flips
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    __shared__ float nom_s[kWavesPerBlock][EMEI_MPC_MAX_HORIZON * na];
+    __shared__ float sig_s[kWavesPerBlock][kMap ? EMEI_MPC_MAX_HORIZON * na : 1];
+    __shared__ uint32_t hist_s[kWavesPerBlock][256];
+    stage_trig_table(trig_s, a.trig, Env::trig_rot_c(), Env::trig_rot_s());
+    const int lane = (int)(threadIdx.x & (kWave - 1));
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    const int64_t i = (int64_t)blockIdx.x * kWavesPerBlock + wv;  // wave-uniform
+    if (i >= a.n) return;
+    const int64_t n = a.n;
+    const int32_t n_cand = a.n_cand, horizon = a.horizon;
+    const int32_t n_comp = horizon * na;  // <= EMEI_MPC_MAX_HORIZON * na (abi.hip)
+    float* nom = nom_s[wv];
+    float* sig = sig_s[wv];
+    uint32_t* hist = hist_s[wv];
+    for (int32_t c = lane; c < n_comp; c += kWave) nom[c] = a.nominal[((int64_t)(c / na) * n + i) * na + c % na];
+
+    R s[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = a.state[k * n + i];
+    int32_t steps = a.steps[i];
+    uint32_t episode = a.episode[i];
+    typename Env::Carry c;
+    trig_ctx_init(c.trig, trig_s);
+    const bool auto_reset = (a.flags & EMEI_FLAG_AUTO_RESET) != 0;
+    const uint64_t g = a.env_offset + (uint64_t)i;
+    double* wt = a.work + i * n_cand;
+    Spec sp;
+    sp.env_offset = a.env_offset;
+    sp.nominal.p = (const __attribute__((address_space(3))) float*)nom;
+    if constexpr (kMap) sp.sigma_map.p = (const __attribute__((address_space(3))) float*)sig;
+    else sp.sigma = a.sigma;
+    sp.lo = a.lo, sp.hi = a.hi;
+    const double m_el = (double)a.n_elites;
+    uint32_t done = 0;
+
+    for (int32_t t = 0; t < a.n_steps; ++t) {
+        Env::prime(s, c, a.p);
+        for (int32_t it = 0; it < a.iterations; ++it) {
+            // (a), (b)
+            for (int32_t cc = lane; cc < n_comp; cc += kWave) {
+                nom[cc] = fminf(fmaxf(nom[cc], a.nominal_lo), a.nominal_hi);
+                if constexpr (kMap) {
+                    if (it == 0) sig[cc] = a.sigma;
+                }
+            }
+            wave_lds_fence();
+            // (c) the returns and (k*, r*)
+            sp.seed = a.seed + (uint64_t)t * (uint64_t)a.iterations + (uint64_t)it;
+            double rs = __builtin_nan("");  // (NaN, INT32_MAX) loses to every candidate
+            int32_t ks = INT32_MAX;
+            for (int32_t k0 = 0; k0 < n_cand; k0 += kWave) {  // wave-uniform trip count: every lane takes part in the ballot
+                const int32_t k = k0 + lane;
+                R cs[4] = {s[0], s[1], s[2], s[3]};
+                typename Env::Carry cc = c;
+                CandidateWordsT<true> cw(sp.seed, g, (uint32_t)k);
+                double ret = 0.0, gd = 1.0;
+                bool live = k < n_cand;
+                for (int32_t h = 0; h < horizon; ++h) {
+                    R o[4], rew;
+                    bool term;
+                    const DrawT act = (DrawT)draw_action(cw, sp, 1, 0, h, 0, act_dim);
+                    Env::step(cs, cc, Env::decode_t(act), a.p, a.freq_rate, o, rew, term);
+                    if (live) {
+                        ret = ret + gd * (double)(float)rew;
+                        gd = gd * a.discount;
+                        if (term) live = false;
+                    }
+                    if (__ballot(live) == 0ull) break;  // wave-uniform
+                }
+                if (k < n_cand) {
+                    wt[k] = ret;
+                    if (plan_replaces(rs, ks, ret, k)) rs = ret, ks = k;
+                }
+            }
+#pragma unroll
+            for (int d = 1; d < kWave; d <<= 1) {
+                const double r2 = __shfl_xor(rs, d, kWave);
+                const int32_t k2 = __shfl_xor(ks, d, kWave);
+                if (plan_replaces(rs, ks, r2, k2)) rs = r2, ks = k2;
+            }
+            const bool last_it = it == a.iterations - 1;
+            if (lane == 0 && last_it && a.plan_return_out) a.plan_return_out[(int64_t)t * n + i] = rs;
+            // the threshold: `need` = the rank looked for among the candidates whose bytes above `shift` equal `prefix`'s
+            uint64_t prefix = 0ull;
+            int32_t need = a.n_elites;
+            for (int shift = 56; shift >= 0; shift -= 8) {
+#pragma unroll
+                for (int b = 0; b < 4; ++b) hist[4 * lane + b] = 0u;
+                wave_lds_fence();
+                for (int32_t k = lane; k < n_cand; k += kWave) {
+                    const uint64_t key = plan_key(wt[k]);
+                    const uint64_t high = shift == 56 ? 0ull : key >> (shift + 8);
+                    if (high == prefix) atomicAdd(&hist[(uint32_t)(key >> shift) & 255u], 1u);
+                }
+                wave_lds_fence();
+                int32_t cb[4], own = 0;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) cb[b] = (int32_t)hist[4 * lane + b], own += cb[b];
+                int32_t above = own;  // candidates in this lane's bins and in those of the lanes above it
+#pragma unroll
+                for (int d = 1; d < kWave; d <<= 1) {
+                    const int32_t up = __shfl_down(above, d, kWave);
+                    if (lane + d < kWave) above += up;
+                }
+                above -= own;
+                const bool mine = above < need && need <= above + own;  // one lane
+                int32_t digit = 0, rest = need;
+                if (mine) {
+                    int32_t acc = above;
+#pragma unroll
+                    for (int b = 3; b >= 0; --b) {
+                        if (acc < need && need <= acc + cb[b]) digit = 4 * lane + b, rest = need - acc;
+                        acc += cb[b];
+                    }
+                }
+                const unsigned long long owner = __ballot(mine);
+                const int src = owner ? __builtin_ctzll(owner) : 0;
+                digit = __shfl(digit, src, kWave), need = __shfl(rest, src, kWave);
+                prefix = (prefix << 8) | (uint64_t)(uint32_t)digit;
+                wave_lds_fence();  // the counters are read before the next pass clears them
+            }
+            // membership: prefix = T, need = how many of the key == T candidates are members (>= 1)
+            int32_t taken = 0;
+            for (int32_t k0 = 0; k0 < n_cand; k0 += kWave) {  // wave-uniform trip count: every lane takes part in the ballot
+                const int32_t k = k0 + lane;
+                const double r = k < n_cand ? wt[k] : 0.0;
+                const uint64_t key = plan_key(r);
+                const bool tie = k < n_cand && key == prefix;
+                const unsigned long long ties = __ballot(tie);
+                const int32_t rank = taken + (int32_t)__popcll(ties & ((1ull << lane) - 1ull));  // of this lane's tie among all ties, by k
+                const bool in = k < n_cand && (key > prefix || (tie && rank < need));
+                if (k < n_cand) wt[k] = in ? 1.0 : 0.0;
+                if (tie && rank == need - 1 && last_it && a.elite_return_out) a.elite_return_out[(int64_t)t * n + i] = r;
+                taken += (int32_t)__popcll(ties);
+            }
+            // the moments (plan_cem_finish_kernel's step 4)
+            for (int32_t c0 = 0; c0 < n_comp; c0 += 4) {
+                double m0[4], s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int32_t cc = min(c0 + u, n_comp - 1);  // past the end: the last component again, dropped below
+                    m0[u] = Env::kDiscrete ? 0.0 : (double)nom[cc];
+                }
+                for (int32_t k = lane; k < n_cand; k += kWave) {
+                    if (wt[k] == 0.0) continue;  // no draw for a candidate outside the set
+                    CandidateWordsT<true> cw(sp.seed, g, (uint32_t)k);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int32_t cc = min(c0 + u, n_comp - 1);
+                        const double d = (double)draw_action(cw, sp, 1, 0, cc / na, cc % na, act_dim) - m0[u];
+                        s1[u] += d, s2[u] += d * d;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+#pragma unroll
+                    for (int d = 1; d < kWave; d <<= 1) s1[u] += __shfl_xor(s1[u], d, kWave);
+#pragma unroll
+                    for (int d = 1; d < kWave; d <<= 1) s2[u] += __shfl_xor(s2[u], d, kWave);
+                }
+                wave_lds_fence();  // every lane's draws (and m0) of this block have read the entries lane 0 now replaces
+                if (lane == 0) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int32_t cc = c0 + u;
+                        if (cc >= n_comp) continue;
+                        const double mu = s1[u] / m_el;
+                        nom[cc] = (float)(m0[u] + mu);
+                        if constexpr (kMap) sig[cc] = (float)sqrt(fmax(s2[u] / m_el - mu * mu, 0.0));
+                    }
+                }
+            }
+            wave_lds_fence();  // lane 0's mean and sigma are what every lane reads from here on
+            // (d)
+            if constexpr (kMap) {
+                for (int32_t cc = lane; cc < n_comp; cc += kWave) sig[cc] = fmaxf(sig[cc], a.sigma_min);
+                wave_lds_fence();
+            }
+        }
+        // act
+        float av[na];
+#pragma unroll
+        for (int q = 0; q < na; ++q) {
+            av[q] = nom[q];
+            if constexpr (Env::kDiscrete) av[q] = av[q] >= 0.5f ? 1.f : 0.f;
+            if (lane == 0) store_action(a.actions_out, a.action_dtype, ((int64_t)t * n + i) * na + q, av[q]);
+        }
+        // step: the wave-uniform real state, computed redundantly by every lane; lane 0 stores
+        {
+            R o[4], rew;
+            bool term;
+            Env::step(s, c, Env::decode_t((DrawT)av[0]), a.p, a.freq_rate, o, rew, term);
+            ++steps;
+            const bool trunc = (a.max_episode_steps > 0) & (steps >= a.max_episode_steps);
+            done = (term ? EMEI_DONE_TERMINAL : 0u) | (trunc ? EMEI_DONE_TRUNCATED : 0u);
+            if (lane == 0) {
+                const int64_t at = (int64_t)t * n + i;
+                if (a.obs_out) a.obs_out[at] = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
+                if (a.reward_out) a.reward_out[at] = (float)rew;
+                if (a.done_out) a.done_out[at] = (uint8_t)done;
+            }
+        }
+        const bool reset_now = auto_reset && __builtin_amdgcn_readfirstlane(done) != 0u;  // wave-uniform
+        if (reset_now) {
+            ++episode;
+            steps = 0;
+            Env::init(s, a.reset_seed, g, episode, a.p);
+        }
+        // warm start, pass by pass in ascending order: a pass reads [base + na, base + 64 + na) and writes [base, base + 64)
+        for (int32_t base = 0; base < n_comp; base += kWave) {
+            const int32_t cc = base + lane;
+            const float v = (!reset_now && cc + na < n_comp) ? nom[cc + na] : a.refill;
+            wave_lds_fence();
+            if (cc < n_comp) nom[cc] = v;
+            wave_lds_fence();
+        }
+    }
+
+    for (int32_t cc = lane; cc < n_comp; cc += kWave) a.nominal[((int64_t)(cc / na) * n + i) * na + cc % na] = nom[cc];
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a.state[k * n + i] = s[k];
+        a.steps[i] = steps;
+        a.episode[i] = episode;
+        ((unsigned long long*)wt)[0] = (unsigned long long)done;  // lane 0's own slot, after its last use
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 #ifndef EMEI_XCD_CONTIGUOUS
@@ -1127,6 +1416,28 @@ static int launch_env(const PendLaunch& L) {
             const dim3 mgrid((unsigned)((L.n + kWavesPerBlock - 1) / kWavesPerBlock));
             hipLaunchKernelGGL(pend_mpc_mppi_kernel<Env>, mgrid, dim3(kBlock), 0, L.stream, m);
             if (L.selected) *L.selected = EMEI_KERNEL_PEND_MPC_MPPI;
+            break;
+        }
+        case PEND_OP_MPC_CEM: {
+            MpcCemArgs<Env> m;
+            m.state = (R*)L.state, m.steps = L.steps, m.episode = L.episode, m.trig = a.trig;
+            m.nominal = L.mpc_nominal, m.work = L.plan.return_out, m.actions_out = L.mpc_actions_out;
+            m.obs_out = (float4*)L.obs_out, m.reward_out = L.reward_out, m.done_out = L.done_out;
+            m.plan_return_out = L.plan_return_out, m.elite_return_out = L.elite_return_out;
+            m.n = L.n, m.n_steps = L.n_steps, m.horizon = L.horizon, m.n_cand = L.plan.n_candidates, m.n_elites = L.n_elites;
+            m.iterations = L.iterations, m.freq_rate = L.freq_rate;
+            m.action_dtype = L.action_dtype, m.max_episode_steps = L.max_episode_steps, m.flags = L.flags;
+            m.reset_seed = L.seed, m.env_offset = L.env_offset, m.seed = L.plan.cand.seed;
+            m.discount = L.plan.discount;
+            m.sigma = L.plan.cand.sigma, m.sigma_min = L.sigma_min, m.lo = L.plan.cand.lo, m.hi = L.plan.cand.hi;
+            m.refill = L.refill, m.nominal_lo = L.nominal_lo, m.nominal_hi = L.nominal_hi;
+            m.p = a.p;
+            if (L.horizon < 1 || L.horizon > EMEI_MPC_MAX_HORIZON) return EMEI_ERR_INVALID;  // the LDS slices of the mean and the sigma
+            if (L.iterations < 1 || L.n_elites < 1 || L.n_elites > L.plan.n_candidates) return EMEI_ERR_INVALID;
+            constexpr int kWavesPerBlock = kBlock / kWave;  // one wave per env
+            const dim3 mgrid((unsigned)((L.n + kWavesPerBlock - 1) / kWavesPerBlock));
+            hipLaunchKernelGGL(pend_mpc_cem_kernel<Env>, mgrid, dim3(kBlock), 0, L.stream, m);
+            if (L.selected) *L.selected = EMEI_KERNEL_PEND_MPC_CEM;
             break;
         }
         default: return EMEI_ERR_INVALID;

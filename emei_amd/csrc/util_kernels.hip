@@ -251,13 +251,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // ---------------------------------------------------------------------------------------------
-// emei_plan_cem.  The planner's order as a 64-bit key: key(a) > key(b) <=> a comes before b whatever their k, key(a) == key(b) <=>
-// neither beats the other (+0.0 and -0.0 one key, every NaN the key 0 below -inf's 0x000f..f; the usual sign-flip map otherwise).
-__device__ __forceinline__ uint64_t plan_key(double r) {
-    if (r != r) return 0ull;
-    const uint64_t b = (uint64_t)__double_as_longlong(r + 0.0);  // -0.0 + 0.0 = +0.0
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
+// emei_plan_cem (the planner's order as a 64-bit key: emei_device.h:plan_key).
 
 // (k*, r*) of env i from its partials (slots w + i of the waves w its candidates lay on), as plan_finish_kernel finds them: the
 // lanes' strided pass, then the butterfly; every lane of the wave ends with the winner.  (plan_mppi_finish_kernel keeps the same lines

@@ -42,7 +42,9 @@ def collect(env, n_steps, actions=None, seed=0, device_rng=True, policy=None, mp
     actions (`env.action_space.sample()`, zoo/util.py:58) in ONE fused rollout launch.
     mpc: instead of either, dict(horizon=, n_candidates=, temperature=[, seed=, discount=, sigma=, refill=, clamp=, nominal=]) — an
     MPPI controller on the true dynamics acts (Engine.mpc_mppi: ONE launch with auto-reset, the 4-state envs; seed defaults to
-    `seed`, nominal to `refill` everywhere)."""
+    `seed`, nominal to `refill` everywhere).  With planner="cem" in the dict a CEM controller acts instead (Engine.mpc_cem):
+    dict(planner="cem", horizon=, n_candidates=, n_elites=[, iterations=, sigma=, sigma_min=, seed=, discount=, refill=, clamp=,
+    nominal=]); planner defaults to "mppi"."""
     eng = env.engine
     N, T, od = eng.n_envs, int(n_steps), eng.obs_dim
     obs0, _ = env.reset(seed=seed, options={"device_rng": True} if device_rng else None)
@@ -52,7 +54,11 @@ def collect(env, n_steps, actions=None, seed=0, device_rng=True, policy=None, mp
         if actions is not None or policy is not None:
             raise ValueError("collect: mpc= is an action source of its own; give neither actions= nor policy=")
         kw = dict(mpc)
-        H, K, temperature = int(kw.pop("horizon")), int(kw.pop("n_candidates")), float(kw.pop("temperature"))
+        planner = kw.pop("planner", "mppi")
+        if planner not in ("mppi", "cem"):
+            raise ValueError(f"collect: mpc planner {planner!r}: 'mppi' or 'cem'")
+        H, K = int(kw.pop("horizon")), int(kw.pop("n_candidates"))
+        plan_arg = float(kw.pop("temperature")) if planner == "mppi" else int(kw.pop("n_elites"))
         refill = kw.get("refill")
         if refill is None:
             refill = kw["refill"] = 0.5 if eng.act_dim == 0 else 0.0
@@ -60,7 +66,10 @@ def collect(env, n_steps, actions=None, seed=0, device_rng=True, policy=None, mp
         if nominal is None:
             shape = (H, N) + ((eng.act_dim,) if eng.act_dim > 1 else ())
             nominal = torch.full(shape, float(refill), dtype=torch.float32, device=eng.device)
-        actions, next_obs, rew, done = eng.mpc_mppi(T, H, K, kw.pop("seed", seed), temperature, nominal, auto_reset=True, **kw)
+        if planner == "mppi":
+            actions, next_obs, rew, done = eng.mpc_mppi(T, H, K, kw.pop("seed", seed), plan_arg, nominal, auto_reset=True, **kw)
+        else:
+            actions, next_obs, rew, done = eng.mpc_cem(T, H, K, plan_arg, kw.pop("seed", seed), nominal, auto_reset=True, **kw)
     elif actions is None and policy is not None:
         next_obs, rew, done = eng.alloc_outputs(T)
         acts_t, cur, epi = [], obs0, epi0.clone()

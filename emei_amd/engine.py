@@ -491,6 +491,46 @@ class Engine:
                                       _ptr(pr), _ptr(es), L.FLAG_AUTO_RESET if auto_reset else 0, _stream()))
         return (act, obs, rew, done) + ((pr, es) if diagnostics else ())
 
+    @_on_device
+    def mpc_cem(self, T, H, K, n_elites, seed, nominal, iterations=1, sigma=None, sigma_min=0.0, discount=1.0, refill=None, clamp=None,
+                auto_reset=False, out=None, diagnostics=False):
+        """T control steps of receding-horizon CEM in one launch (emei_mpc_cem; the 4-state envs on their own kernels): per step,
+        `iterations` times, the mean is clamped to `clamp` and refitted as plan_cem(H, K, n_elites, seed + t * iterations + j,
+        nominal=mean, sigma=std, out=mean, out_sigma=std) refits it — std a per-entry tensor that starts every control step at
+        `sigma` and is floored at `sigma_min` after every refit (continuous envs; the discrete ones have none) — then the mean's first
+        entry is the action (discrete envs: entry >= 0.5), the envs take step(action, auto_reset), and the mean is shifted by one
+        step with `refill` behind it (an env that was reset: `refill` everywhere) — bit for bit what that loop of plan_cem and step
+        computes, state, counters and compact_done() included.
+        nominal: float32 [H, N(, act_dim)] on the engine's device, the mean, updated IN PLACE (T = a + b steps equal a call with
+        (a, seed) and one with (b, seed + a * iterations)).  Defaults of refill, clamp and out as mpc_mppi's.
+        -> (actions [T, N(, act_dim)] int64 / float32, obs [T, N, obs_dim] f32, reward [T, N] f32, done [T, N] u8
+        [, plan_return float64 [T, N], elite_return float64 [T, N]]: the best candidate return and the admission threshold of every
+        step's last iteration)."""
+        T, n_elites, iterations = int(T), int(n_elites), int(iterations)
+        if T < 1:
+            raise ValueError(f"n_steps={T} must be >= 1")
+        if nominal is None:
+            raise ValueError("mpc_cem needs a nominal tensor (it is updated in place)")
+        H, K, nominal, sigma, dtype = self._candidate_args(H, K, nominal, sigma, None)
+        if not 1 <= n_elites <= K:
+            raise ValueError(f"n_elites={n_elites} is outside [1, n_candidates={K}]")
+        if iterations < 1:
+            raise ValueError(f"iterations={iterations} must be >= 1")
+        if refill is None:
+            refill = 0.5 if self.act_dim == 0 else 0.0
+        if clamp is None:
+            clamp = (0.05, 0.95) if self.act_dim == 0 else _CTRL_RANGE.get(self.env_name, (-1.0, 1.0))
+        lo, hi = float(clamp[0]), float(clamp[1])
+        obs, rew, done = self._check_outputs(out, (T,)) if out is not None else self.alloc_outputs(T)
+        ws = self._workspace("_mpc_cem_ws", L.lib().emei_mpc_cem_workspace_bytes, K)
+        act = torch.empty((T, self.n_envs) + self._act_tail, dtype=dtype, device=self.device)
+        pr = torch.empty((T, self.n_envs), dtype=torch.float64, device=self.device) if diagnostics else None
+        er = torch.empty((T, self.n_envs), dtype=torch.float64, device=self.device) if diagnostics else None
+        L.check(L.lib().emei_mpc_cem(self._h, T, H, K, n_elites, iterations, _seed64(seed), _ptr(nominal), sigma, float(sigma_min),
+                                     float(discount), float(refill), lo, hi, _ptr(ws), _ptr(act), _ACT_DTYPES[dtype], _ptr(obs), _ptr(rew),
+                                     _ptr(done), _ptr(pr), _ptr(er), L.FLAG_AUTO_RESET if auto_reset else 0, _stream()))
+        return (act, obs, rew, done) + ((pr, er) if diagnostics else ())
+
     def _check_plan_out(self, name, out, shape, source, source_name):
         """an output tensor of plan_mppi / plan_cem: float32 [H, N(, act_dim)], `source` itself (in place) or clear of it"""
         if not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous() \

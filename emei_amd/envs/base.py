@@ -368,6 +368,34 @@ class HipEnv(EmeiEnv):
             return out
         return tuple(t.cpu().numpy() for t in out + (nom,))
 
+    def mpc_cem(self, n_steps, horizon, n_candidates, n_elites, seed, nominal, iterations=1, sigma=None, sigma_min=0.0, discount=1.0,
+                refill=None, clamp=None, auto_reset=None, diagnostics=False):
+        """n_steps control steps of receding-horizon CEM in one launch (Engine.mpc_cem, ABI emei_mpc_cem; the 4-state envs): per step
+        `iterations` refits of plan_cem(horizon, n_candidates, n_elites, seed + t * iterations + j, nominal=mean, sigma=std) on the clamped
+        mean — std starting at `sigma` every step and floored at `sigma_min` — the mean's first entry as the action (discrete envs:
+        >= 0.5), step(), and the mean shifted by one step with `refill` behind it — the same bits as that loop —
+        (actions [n_steps, num_envs(, act_dim)], obs float32 [n_steps, num_envs, obs_dim], reward float32, terminal bool, truncated
+        bool [, plan_return float64 [n_steps, num_envs], elite_return float64 [n_steps, num_envs]]).
+        nominal: float32 [horizon, num_envs(, act_dim)], the mean.  A tensor on the env's device is updated in place and tensors come
+        back; a NumPy array is left as it is and NumPy arrays come back, the updated nominal appended as the last element.
+        auto_reset: the env's own setting unless given.  Other arguments as Engine.mpc_cem."""
+        import torch
+
+        assert self.state is not None, "Call reset before using step method."  # base_control.py:67
+        eng = self.engine
+        as_numpy = not isinstance(nominal, torch.Tensor)
+        nom = self._as_device(nominal, torch.float32)
+        res = eng.mpc_cem(n_steps, horizon, n_candidates, n_elites, seed, nom, iterations=iterations, sigma=sigma, sigma_min=sigma_min,
+                          discount=discount, refill=refill, clamp=clamp, auto_reset=self.auto_reset if auto_reset is None else auto_reset,
+                          diagnostics=diagnostics)
+        act, obs, rew, done = res[:4]
+        out = (act, obs, rew, (done & 1).bool(), (done & 2).bool()) + tuple(res[4:])
+        if not as_numpy:
+            if nom.data_ptr() != nominal.data_ptr():
+                nominal.copy_(nom.reshape(nominal.shape))  # a tensor that had to be moved or converted: still updated in place
+            return out
+        return tuple(t.cpu().numpy() for t in out + (nom,))
+
     def plan_cem(self, horizon, n_candidates, n_elites, seed, discount=1.0, nominal=None, sigma=None, start_state=None, iterations=1,
                  elite_return=False):
         """The cross-entropy method's refit of a sampling distribution over action sequences, two launches per iteration

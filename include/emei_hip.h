@@ -43,7 +43,9 @@ extern "C" {
  *    (one cross-entropy-method iteration: exact per-env selection of the n_elites best candidates on the device, their mean and
  *    standard deviation);
  *    emei_mpc_mppi_workspace_bytes, emei_mpc_mppi (receding-horizon MPPI control episodes of the 4-state family in one launch:
- *    plan, act, step, auto-reset and warm start per control step without leaving the device), EMEI_KERNEL_PEND_MPC_MPPI. */
+ *    plan, act, step, auto-reset and warm start per control step without leaving the device), EMEI_KERNEL_PEND_MPC_MPPI;
+ *    emei_mpc_cem_workspace_bytes, emei_mpc_cem (the same control episodes with the cross-entropy method as the planner: `iterations`
+ *    refits of emei_plan_cem per control step, the per-entry sigma kept on the device), EMEI_KERNEL_PEND_MPC_CEM. */
 #define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
@@ -508,6 +510,57 @@ EMEI_API int emei_mpc_mppi(emei_env* h, int32_t n_steps, int32_t horizon, int32_
                            void* workspace, void* actions_out, int action_dtype, float* obs_out, float* reward_out, uint8_t* done_out,
                            double* plan_return_out, double* ess_out, uint32_t flags, void* stream);
 
+/* Receding-horizon control with the cross-entropy method as the planner (PETS / PlaNet-style MPC on the true dynamics), whole episodes
+ * in ONE launch (plus the small one that packs the done mask): what the loop "`iterations` times emei_plan_cem in place, first entry,
+ * emei_step, shift the mean" does in 2 * iterations + 1 launches and a handful of array operations per control step.  The same envs
+ * as emei_mpc_mppi: the 4-state family on its own kernels.
+ *
+ * Semantics (normative).  For every env i and t = 0 .. n_steps - 1, m being env i's column of `nominal` and, on continuous envs, s a
+ * per-entry sigma column of the same shape that lives only inside the call:
+ *   1. Iterate.  For j = 0 .. iterations - 1:
+ *      (a) Clamp.  m[h(, a)] = fminf(fmaxf(m[h(, a)], nominal_lo), nominal_hi); -inf / +inf: no clamp.
+ *      (b) Continuous envs, j = 0 only: s[h, a] = (float)sigma — the distribution's width is reset at every control step, only the
+ *          mean is warm-started.
+ *      (c) Refit.  Exactly emei_plan_cem(h, horizon, n_candidates, n_elites, seed + t*iterations + j (mod 2^64), nominal = m,
+ *          sigma_map = s (continuous) / NULL (discrete), discount, start_state = NULL, mean_out = m, std_out = s / NULL) for env i: the
+ *          same candidates (the sigma_map clause of the candidate specification; g = env_index_offset + i), the same start state (the
+ *          env's current one), returns, planner's order and elite set E_i, shifted moments and summation tree (lane l adds its
+ *          members k = l, l + 64, .. in ascending order, then the butterfly d = 1 .. 32), one rounding to float32.
+ *      (d) Continuous envs: s[h, a] = fmaxf(s[h, a], (float)sigma_min); sigma_min = 0: no floor.
+ *      After the last iteration plan_return_out[t, i] = r* and elite_return_out[t, i] = the admission threshold, as emei_plan_cem's
+ *      best_return_out and elite_return_out (float64 [n_steps, n_envs]; either may be NULL).
+ *   2. Act.  Continuous envs: a_t = m[0, :]; discrete envs: a_t = (m[0] >= 0.5f) ? 1 : 0.  actions_out[t, i(, :)] in action_dtype
+ *      (U8 / I32 / I64 discrete, F32 continuous), [n_steps, n_envs(, act_dim)].  Required.
+ *   3. Step.  Exactly emei_step(a_t, flags) for env i, with emei_rollout's arithmetic: the TimeLimit counter, the EMEI_DONE_* bits
+ *      and EMEI_FLAG_AUTO_RESET with the handle's reset key and episode counter.  obs_out / reward_out / done_out at [t, i] as
+ *      emei_rollout writes them; any of the three may be NULL.
+ *   4. Warm start.  The step was done and auto-reset is on: m[h] = refill for all h (a new episode gets no warm start).  Otherwise
+ *      m[h] = m[h + 1] for h < horizon - 1 and m[horizon - 1] = refill.
+ * After the call `nominal` (float32 [horizon, n_envs(, act_dim)], in/out, required) holds m after the last shift, and the handle is as
+ * after the equivalent loop: state, step and episode counters, the done mask emei_compact_done reads.  Every output is bit-identical
+ * to that loop's.
+ * Consequences.  Chunking: n_steps = a + b in one call equals a call with (a, seed) followed by one with (b, seed + a*iterations).
+ * Sharding: results depend on g, not on n_envs or the shard.  Stream: the call neither allocates nor synchronises (capturable).
+ * Non-finite nominal entries are the caller's error: the results of that env are unspecified (the call does not fault).  Smoothing of
+ * the mean and elites kept across iterations are out of scope: emei_plan_cem's two-launch route serves them.
+ * Work split: one wave per env, as emei_mpc_mppi.
+ * workspace: emei_mpc_cem_workspace_bytes(n_envs, n_candidates) = 8 * n_envs * n_candidates bytes of device memory, 8-byte aligned,
+ * contents irrelevant before and after.
+ * EMEI_ERR_INVALID before any HIP call, scalars first, in this order: n_steps < 1, horizon < 1, n_candidates < 1, n_elites outside
+ * [1, n_candidates], discount outside (0, 1], iterations < 1, refill not finite, nominal_lo > nominal_hi or either NaN, sigma_min not
+ * finite or < 0, horizon > EMEI_MPC_MAX_HORIZON (the mean and the sigma live in LDS); then a NULL handle; emei_plan_shooting's
+ * candidate checks (sigma finite and > 0 on a continuous env, n_envs * n_candidates), a wrong action_dtype, unknown flags; NULL
+ * nominal, workspace or actions_out.  EMEI_ERR_STATE without a state.  EMEI_ERR_UNSUPPORTED exactly where emei_mpc_mppi gives it:
+ * a handle emei_rollout runs on the body kernels, and a handle with observation peers set. */
+/* bytes of device scratch emei_mpc_cem needs for this shape; host only, no handle, no HIP call.
+ * Negative (EMEI_ERR_INVALID) where emei_plan_mppi_workspace_bytes is. */
+EMEI_API int64_t emei_mpc_cem_workspace_bytes(int64_t n_envs, int32_t n_candidates);
+EMEI_API int emei_mpc_cem(emei_env* h, int32_t n_steps, int32_t horizon, int32_t n_candidates, int32_t n_elites, int32_t iterations,
+                          uint64_t seed, float* nominal, double sigma, double sigma_min, double discount, float refill,
+                          float nominal_lo, float nominal_hi, void* workspace, void* actions_out, int action_dtype,
+                          float* obs_out, float* reward_out, uint8_t* done_out, double* plan_return_out, double* elite_return_out,
+                          uint32_t flags, void* stream);
+
 /* Which kernel the LAST emei_step / emei_rollout of this handle launched (enum emei_kernel_id): a debug /
  * test getter, so that a parity test can assert that the path it checked is the path bench.py times. */
 enum emei_kernel_id {
@@ -522,7 +575,8 @@ enum emei_kernel_id {
     EMEI_KERNEL_BODY_RK4_CHUNKED = 8,  /* body_rollout_kernel<Body, true> likewise */
     EMEI_KERNEL_PEND_STAGED_PEERS_FREQ1 = 9, /* pend_rollout_staged_peers_kernel<Env, ActT, true>: with the peer stores of emei_set_obs_peers */
     EMEI_KERNEL_PEND_STAGED_PEERS = 10,      /* pend_rollout_staged_peers_kernel<Env, ActT, false> */
-    EMEI_KERNEL_PEND_MPC_MPPI = 11           /* pend_mpc_mppi_kernel<Env>: emei_mpc_mppi (it steps the handle, so it reports here) */
+    EMEI_KERNEL_PEND_MPC_MPPI = 11,          /* pend_mpc_mppi_kernel<Env>: emei_mpc_mppi (it steps the handle, so it reports here) */
+    EMEI_KERNEL_PEND_MPC_CEM = 12            /* pend_mpc_cem_kernel<Env>: emei_mpc_cem (likewise) */
 };
 EMEI_API int emei_last_rollout_kernel(emei_env* h);
 

@@ -9,8 +9,11 @@ rounds; every round times ONE episode of each route with device events around it
 events bracket everything its T iterations enqueue), the two routes alternating inside the round so that drift hits both alike.
 Reported per shape: the median over the rounds and the spread (min, max) of either route, and the ratio of the medians.
 Shapes: CartPoleSwingUp N = 256 and N = 65 536, ReboundInvertedPendulumSwingUp N = 256; K = 64, H = 30; T = 200 (20 at N = 65 536).
+--planner cem: the same comparison for Engine.mpc_cem (emei_mpc_cem) against the README's CEM loop — per control step a roll, a
+refill, a fresh std, ITERATIONS = 3 times (a clamp of the mean on the discrete envs, plan_cem in place: two launches, a floor of the
+std on the continuous ones), and a step — with N_ELITES = 8, at the same shapes (tests/test_gpu_mpc_cem.py: the same bits).
 One JSON line per shape.  Run on the GPU box:
-    python tools/mpc_timing.py [--warmup 2] [--repeats 7] [--only INDEX]"""
+    python tools/mpc_timing.py [--planner mppi|cem] [--warmup 2] [--repeats 7] [--only INDEX]"""
 import argparse
 import json
 import os
@@ -29,6 +32,7 @@ SHAPES = [
     ("ReboundInvertedPendulumSwingUp", 256, 64, 30, 200, 0.5),
 ]
 TEMPERATURE, DISCOUNT = 0.5, 0.99
+ITERATIONS, N_ELITES, SIGMA_MIN = 3, 8, 0.05  # --planner cem
 
 
 def loop_episode(eng, T, H, K, seed, nominal, sigma, refill, lo, hi):
@@ -42,10 +46,26 @@ def loop_episode(eng, T, H, K, seed, nominal, sigma, refill, lo, hi):
         eng.step((nominal[0] >= 0.5).long() if eng.act_dim == 0 else nominal[0], auto_reset=True)
 
 
+def cem_loop_episode(eng, T, H, K, seed, nominal, sigma, refill, lo, hi):
+    """the README's CEM loop at the Engine level; the discrete envs have no std and clamp the mean as the MPPI loop does"""
+    for t in range(T):
+        nominal = torch.roll(nominal, -1, 0)
+        nominal[-1] = refill
+        std = None if eng.act_dim == 0 else torch.full_like(nominal, sigma)
+        for it in range(ITERATIONS):
+            nominal.clamp_(lo, hi)
+            eng.plan_cem(H, K, N_ELITES, seed + ITERATIONS * t + it, discount=DISCOUNT, nominal=nominal, sigma=std, out=nominal,
+                         out_sigma=std)
+            if std is not None:
+                std.clamp_(min=SIGMA_MIN)
+        eng.step((nominal[0] >= 0.5).long() if eng.act_dim == 0 else nominal[0], auto_reset=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--planner", choices=("mppi", "cem"), default="mppi")
     ap.add_argument("--only", type=int, default=None, help="index of the one shape to run")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -68,11 +88,15 @@ def main():
             torch.cuda.synchronize()
 
         def fused():
-            eng.mpc_mppi(T, H, K, 1, TEMPERATURE, nominal, discount=DISCOUNT, sigma=sigma, refill=refill, clamp=(lo, hi), auto_reset=True,
-                         out=outs)
+            if args.planner == "cem":
+                eng.mpc_cem(T, H, K, N_ELITES, 1, nominal, iterations=ITERATIONS, sigma=sigma, sigma_min=SIGMA_MIN, discount=DISCOUNT,
+                            refill=refill, clamp=(lo, hi), auto_reset=True, out=outs)
+            else:
+                eng.mpc_mppi(T, H, K, 1, TEMPERATURE, nominal, discount=DISCOUNT, sigma=sigma, refill=refill, clamp=(lo, hi),
+                             auto_reset=True, out=outs)
 
         def loop():
-            loop_episode(eng, T, H, K, 1, nominal, sigma, refill, lo, hi)
+            (cem_loop_episode if args.planner == "cem" else loop_episode)(eng, T, H, K, 1, nominal, sigma, refill, lo, hi)
 
         def timed(fn):
             restore()
@@ -91,7 +115,7 @@ def main():
             ms["loop"].append(timed(loop))
         med = {k: statistics.median(v) for k, v in ms.items()}
         print(json.dumps({
-            "env": name, "n_envs": N, "n_candidates": K, "horizon": H, "n_steps": T, "repeats": args.repeats,
+            "planner": args.planner, "env": name, "n_envs": N, "n_candidates": K, "horizon": H, "n_steps": T, "repeats": args.repeats,
             "fused_ms": round(med["fused"], 4), "fused_ms_min_max": [round(min(ms["fused"]), 4), round(max(ms["fused"]), 4)],
             "loop_ms": round(med["loop"], 4), "loop_ms_min_max": [round(min(ms["loop"]), 4), round(max(ms["loop"]), 4)],
             "loop_over_fused": round(med["loop"] / med["fused"], 3),
