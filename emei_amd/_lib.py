@@ -39,12 +39,13 @@ KERNEL_NAMES = {0: "none", 1: "pend_rollout_staged_kernel<freq1>", 2: "pend_roll
                 4: "pend_rollout_kernel", 5: "body_rollout_kernel", 6: "body_rollout_kernel<rk4>",
                 7: "body_rollout_kernel (chunked work items)", 8: "body_rollout_kernel<rk4> (chunked work items)",
                 9: "pend_rollout_staged_peers_kernel<freq1>", 10: "pend_rollout_staged_peers_kernel", 11: "pend_mpc_mppi_kernel",
-                12: "pend_mpc_cem_kernel"}
+                12: "pend_mpc_cem_kernel", 13: "body_mpc_mppi_kernel", 14: "body_mpc_cem_kernel"}
 KERNEL_PEND_STAGED_FREQ1, KERNEL_PEND_STAGED, KERNEL_PEND_GENERIC_FULL, KERNEL_PEND_GENERIC, KERNEL_BODY, KERNEL_BODY_RK4 = 1, 2, 3, 4, 5, 6
 KERNEL_BODY_CHUNKED, KERNEL_BODY_RK4_CHUNKED = 7, 8
 KERNEL_PEND_STAGED_PEERS_FREQ1, KERNEL_PEND_STAGED_PEERS = 9, 10
 KERNEL_PEND_MPC_MPPI = 11
 KERNEL_PEND_MPC_CEM = 12
+KERNEL_BODY_MPC_MPPI, KERNEL_BODY_MPC_CEM = 13, 14  # the InvertedDoublePendulum's fused controllers
 MPC_MAX_HORIZON = 256  # EMEI_MPC_MAX_HORIZON
 MAX_OBS_PEERS = 8  # EMEI_MAX_OBS_PEERS
 # enum emei_ode_method: `method` of ODE_approximation (base_control.py:133-173), classic control only

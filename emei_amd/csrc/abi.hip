@@ -183,6 +183,10 @@ static bool steps_as_body(const emei_config& c) {
     return is_ip(c.env_id) && (c.integrator != EMEI_INTEG_EULER || obs_noise);
 }
 static bool is_body(int env_id) { return env_id >= EMEI_HALFCHEETAH_RUNNING && env_id <= EMEI_HOPPER_RUNNING; }
+static bool is_idp(int env_id) {
+    return env_id == EMEI_IDP_REBOUND_BALANCING || env_id == EMEI_IDP_BOUNDARY_BALANCING || env_id == EMEI_IDP_REBOUND_SWINGUP ||
+           env_id == EMEI_IDP_BOUNDARY_SWINGUP;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Host twin of the InvertedPendulum constants for the launch descriptors: every number comes from pendulum_envs.h:
@@ -934,8 +938,47 @@ extern "C" EMEI_API int emei_plan_cem(emei_env* h, int32_t horizon, int32_t n_ca
 }
 
 // ---------------------------------------------------------------------------------------------
+// The handles the fused controllers refuse (after the state check): the 4-state kernels have pend_mpc_*_kernel, and of the handles
+// that step on the body kernels the InvertedDoublePendulum has body_mpc_*_kernel (body_mpc_kernels.h: Body::kFusedMpc), whose plan
+// steps the model without observation noise.
+static int check_mpc_handle(const char* fn, const emei_env* h) {
+    if (steps_as_body(h->cfg)) {
+        if (!is_idp(h->cfg.env_id))
+            return fail(EMEI_ERR_UNSUPPORTED, "%s: this handle steps on the body kernels (a multi-body env, or an InvertedPendulum with "
+                                              "a non-euler integrator or observation noise); the fused controller serves the 4-state kernels only",
+                        fn);
+        for (int i = 0; i < EMEI_MAX_STATE_DIM; ++i)
+            if (h->cfg.obs_sigma[i] != 0.f)
+                return fail(EMEI_ERR_UNSUPPORTED, "%s: this InvertedDoublePendulum handle has observation noise (obs_sigma[%d]=%g), which the "
+                                                  "fused controller does not serve: its plan steps the model without it",
+                            fn, i, (double)h->cfg.obs_sigma[i]);
+    }
+    if (h->peers.count > 0)
+        return fail(EMEI_ERR_UNSUPPORTED, "%s: observation peers are set (emei_set_obs_peers), which this kernel does not serve", fn);
+    return EMEI_OK;
+}
+
+// the body-kernel route of both controllers (the planner's own fields come in `m`): the kernel, then the done-mask launch
+static int launch_body_mpc(emei_env* h, int op, MpcLaunch m, int32_t n_steps, int32_t n_candidates, uint64_t seed, double sigma,
+                           double discount, void* workspace, float* obs_out, float* reward_out, uint8_t* done_out, uint32_t flags,
+                           void* stream) {
+    BodyLaunch L = body_base(h, stream);
+    L.op = op, L.mpc = m;
+    L.n_steps = n_steps;
+    L.plan.n_candidates = n_candidates, L.plan.discount = discount;
+    L.plan.cand = candidate_spec(h, seed, nullptr, sigma);  // the kernel keeps the nominal in LDS
+    L.plan.return_out = (double*)workspace;
+    L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
+    L.flags = flags;
+    L.selected = &h->last_kernel;
+    const int rc = body_launch(L);
+    return rc != EMEI_OK ? rc : launch_mpc_done_pack((const double*)workspace, n_candidates, h->cfg.n_envs, h->done_mask, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
 // emei_mpc_mppi: n_steps control steps of "emei_plan_mppi, act, emei_step, shift" in one kernel of one wave per env
-// (pendulum_kernels.h:pend_mpc_mppi_kernel), then the done mask packed by a small second launch.
+// (pendulum_kernels.h:pend_mpc_mppi_kernel; the InvertedDoublePendulum: body_mpc_kernels.h:body_mpc_mppi_kernel), then the done mask
+// packed by a small second launch.
 extern "C" EMEI_API int64_t emei_mpc_mppi_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
     const int64_t nk = check_plan_shape("emei_mpc_mppi_workspace_bytes", n_envs, n_candidates);
     return nk < 0 ? nk : (int64_t)sizeof(double) * nk;  // every candidate's return, then its weight
@@ -966,12 +1009,16 @@ extern "C" EMEI_API int emei_mpc_mppi(emei_env* h, int32_t n_steps, int32_t hori
     if (!actions_out) return fail(EMEI_ERR_INVALID, "%s: null actions_out", fn);
     EMEI_ON_DEVICE(h, fn);
     if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    if (steps_as_body(h->cfg))
-        return fail(EMEI_ERR_UNSUPPORTED, "%s: this handle steps on the body kernels (a multi-body env, or an InvertedPendulum with "
-                                          "a non-euler integrator or observation noise); the fused controller serves the 4-state kernels only",
-                    fn);
-    if (h->peers.count > 0)
-        return fail(EMEI_ERR_UNSUPPORTED, "%s: observation peers are set (emei_set_obs_peers), which this kernel does not serve", fn);
+    if (int rc = check_mpc_handle(fn, h)) return rc;
+    if (steps_as_body(h->cfg)) {  // continuous actions: actions_out is float32 (check_action_dtype)
+        MpcLaunch m;
+        m.horizon = horizon, m.nominal = nominal, m.actions_out = (float*)actions_out;
+        m.plan_return_out = plan_return_out, m.ess_out = ess_out, m.temperature = temperature;
+        m.refill = refill, m.nominal_lo = nominal_lo, m.nominal_hi = nominal_hi;
+        const int rc = launch_body_mpc(h, BODY_OP_MPC_MPPI, m, n_steps, n_candidates, seed, sigma, discount, workspace, obs_out, reward_out,
+                                       done_out, flags, stream);
+        return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    }
     PendLaunch L = pend_base(h, stream);
     L.op = PEND_OP_MPC;
     L.n_steps = n_steps, L.horizon = horizon, L.temperature = temperature;
@@ -991,7 +1038,8 @@ extern "C" EMEI_API int emei_mpc_mppi(emei_env* h, int32_t n_steps, int32_t hori
 
 // ---------------------------------------------------------------------------------------------
 // emei_mpc_cem: n_steps control steps of "`iterations` times emei_plan_cem in place, act, emei_step, shift" in one kernel of one wave
-// per env (pendulum_kernels.h:pend_mpc_cem_kernel), then emei_mpc_mppi's done-mask launch.
+// per env (pendulum_kernels.h:pend_mpc_cem_kernel; the InvertedDoublePendulum: body_mpc_kernels.h:body_mpc_cem_kernel), then
+// emei_mpc_mppi's done-mask launch.
 extern "C" EMEI_API int64_t emei_mpc_cem_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
     const int64_t nk = check_plan_shape("emei_mpc_cem_workspace_bytes", n_envs, n_candidates);
     return nk < 0 ? nk : (int64_t)sizeof(double) * nk;  // every candidate's return, then its membership flag
@@ -1027,12 +1075,17 @@ extern "C" EMEI_API int emei_mpc_cem(emei_env* h, int32_t n_steps, int32_t horiz
     if (!actions_out) return fail(EMEI_ERR_INVALID, "%s: null actions_out", fn);
     EMEI_ON_DEVICE(h, fn);
     if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    if (steps_as_body(h->cfg))
-        return fail(EMEI_ERR_UNSUPPORTED, "%s: this handle steps on the body kernels (a multi-body env, or an InvertedPendulum with "
-                                          "a non-euler integrator or observation noise); the fused controller serves the 4-state kernels only",
-                    fn);
-    if (h->peers.count > 0)
-        return fail(EMEI_ERR_UNSUPPORTED, "%s: observation peers are set (emei_set_obs_peers), which this kernel does not serve", fn);
+    if (int rc = check_mpc_handle(fn, h)) return rc;
+    if (steps_as_body(h->cfg)) {  // continuous actions: actions_out is float32 (check_action_dtype)
+        MpcLaunch m;
+        m.horizon = horizon, m.nominal = nominal, m.actions_out = (float*)actions_out;
+        m.plan_return_out = plan_return_out, m.elite_return_out = elite_return_out;
+        m.n_elites = n_elites, m.iterations = iterations, m.sigma_min = (float)sigma_min;
+        m.refill = refill, m.nominal_lo = nominal_lo, m.nominal_hi = nominal_hi;
+        const int rc = launch_body_mpc(h, BODY_OP_MPC_CEM, m, n_steps, n_candidates, seed, sigma, discount, workspace, obs_out, reward_out,
+                                       done_out, flags, stream);
+        return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    }
     PendLaunch L = pend_base(h, stream);
     L.op = PEND_OP_MPC_CEM;
     L.n_steps = n_steps, L.horizon = horizon, L.n_elites = n_elites, L.iterations = iterations;

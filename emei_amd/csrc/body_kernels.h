@@ -22,6 +22,8 @@
 //   kObsIsState                                     // the observation determines the state (get_batch_next_obs)
 //   kUnrollRK4                                      // RK4 stages as straight-line code (see body_substep)
 //   kScratchPerLane                                 // elements of `real` of block LDS per lane that accel() may use (0: none)
+//   kFusedMpc                                       // emei_mpc_mppi / emei_mpc_cem serve this body (body_mpc_kernels.h): a cheap step, no
+//                                                   // lane reads another lane's data; false: no such kernel is instantiated
 //
 // Layout: one thread per env, state SoA in HBM ([NS][n] Reals), registers across a rollout.  An env's
 // observation (NO floats) and action (NA floats) are wider than one lane access, so each wave stages
@@ -163,7 +165,28 @@ __device__ __forceinline__ void body_substep(typename Body::real (&s)[Body::NS],
 
 enum BodyOp { BODY_OP_ROLLOUT = 0, BODY_OP_RESET, BODY_OP_GET_OBS, BODY_OP_INIT_OBS, BODY_OP_REWARD, BODY_OP_TERMINAL, BODY_OP_NEXT_OBS,
               BODY_OP_OCCUPANCY /* host only: *selected = waves of the rollout kernel (of L.integrator) the current device holds at once */,
-              BODY_OP_PLAN /* emei_evaluate_sequences: body_plan_kernel */ };
+              BODY_OP_PLAN /* emei_evaluate_sequences: body_plan_kernel */,
+              BODY_OP_MPC_MPPI /* emei_mpc_mppi: body_mpc_mppi_kernel (Body::kFusedMpc) */,
+              BODY_OP_MPC_CEM /* emei_mpc_cem: body_mpc_cem_kernel (Body::kFusedMpc) */ };
+
+// What BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM take beyond the base descriptor: n_steps control steps of the planner with plan.n_candidates
+// candidates over `horizon` steps under plan.discount; plan.cand carries the call's seed, sigma and the ctrlrange (its nominal is
+// unused: the kernel keeps the nominal in LDS), `seed` the handle's reset key; plan.return_out = the workspace [n * K]; obs_out /
+// reward_out / done_out as BODY_OP_ROLLOUT's outputs
+struct MpcLaunch {
+    int32_t horizon = 1;
+    float* nominal = nullptr;  // in/out [horizon, n, act_dim]
+    float* actions_out = nullptr;
+    double* plan_return_out = nullptr;  // [n_steps, n] or null
+    double* ess_out = nullptr;          // MPPI: [n_steps, n] or null
+    double temperature = 1.0;           // MPPI
+    float refill = 0.f, nominal_lo = 0.f, nominal_hi = 0.f;
+    // CEM: `iterations` refits to the n_elites best candidates per control step, plan.cand.sigma the width every control step starts
+    // from, sigma_min the floor of the refitted one
+    int32_t n_elites = 1, iterations = 1;
+    float sigma_min = 0.f;
+    double* elite_return_out = nullptr;  // [n_steps, n] or null
+};
 
 // host-side launch descriptor (abi.hip -> body_dispatch.hip -> body_tu.hip)
 struct BodyLaunch {
@@ -201,6 +224,7 @@ struct BodyLaunch {
     hipStream_t stream = nullptr;
     int* selected = nullptr;  // out: enum emei_kernel_id of the rollout kernel launched
     PlanLaunch plan;  // BODY_OP_PLAN; n_steps = the horizon, obs_out = final_obs [n * K, NO] or null
+    MpcLaunch mpc;    // BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM
 };
 int body_launch(const BodyLaunch& L);  // body_dispatch.hip
 
@@ -786,6 +810,10 @@ static void launch_body_plan(const BodyLaunch& L, const typename Body::Model& m,
                        DRAWN ? (PlanPartial*)P.partials : nullptr);
 }
 
+}  // namespace emei
+#include "body_mpc_kernels.h"  // body_mpc_mppi_kernel / body_mpc_cem_kernel and launch_body_mpc
+namespace emei {
+
 // every launch of one Body type (one translation unit instantiates exactly one Body: body_tu.hip)
 template <class Body>
 static int launch_body(const BodyLaunch& L) {
@@ -945,6 +973,14 @@ static int launch_body(const BodyLaunch& L) {
             }
             break;
         }
+        case BODY_OP_MPC_MPPI:
+        case BODY_OP_MPC_CEM:
+            if constexpr (Body::kFusedMpc) {
+                if (int rc = launch_body_mpc<Body>(L, m)) return rc;
+                break;
+            } else {
+                return EMEI_ERR_UNSUPPORTED;  // abi.hip refuses these handles with a message of its own
+            }
         default: return EMEI_ERR_INVALID;
     }
     return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;

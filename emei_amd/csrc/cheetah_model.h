@@ -1334,6 +1334,7 @@ struct CheetahBody {
 #endif
     static constexpr bool kUnrollRK4 = EMEI_CHEETAH_UNROLL_RK4 != 0;
     static constexpr int kScratchPerLane = SOLVER == EMEI_SOLVER_NEWTON ? cheetah::kDualSlots * cheetah::kSlotFields : 0;
+    static constexpr bool kFusedMpc = false;  // ~10^4 instructions per step and lanes that lend each other constraint slots (`donor`)
     static constexpr bool kHasCtrlCost = true;
     static constexpr bool kObsIsState = true;
     static constexpr bool kSpareReset = false;

@@ -91,6 +91,7 @@ struct DPendBody {
     static constexpr int kMinWavesPerEU = 1;
     static constexpr bool kUnrollRK4 = false;
     static constexpr int kScratchPerLane = 0;
+    static constexpr bool kFusedMpc = true;   // body_mpc_kernels.h: a 3x3 LDL^T and one limit row per evaluation, lanes independent
     static constexpr bool kHasCtrlCost = false;
     static constexpr bool kObsIsState = false;
     static constexpr bool kSpareReset = true;

@@ -620,6 +620,29 @@ struct CandidateSpecMap {  // kernel argument
     CandidateSpecMap(const CandidateSpec& sp, const float* map)
         : seed(sp.seed), env_offset(sp.env_offset), nominal(sp.nominal), sigma_map(map), lo(sp.lo), hi(sp.hi) {}
 };
+// The specs of the fused controllers (emei_mpc_mppi / emei_mpc_cem: pendulum_kernels.h, body_mpc_kernels.h), whose nominal lives in
+// LDS: the wave's own slice [horizon(, act_dim)], indexed as a one-env nominal (draw_action is called with n_envs = 1, i = 0).  Types
+// of their own: the CandidateSpec / CandidateSpecMap instantiations are the code they were.
+// The slice may sit at LDS address 0, which IS the null pointer of that address space: draw_action's "is there a nominal" tests must not
+// look at the address (the first wave of a block would draw as if it had no nominal), hence a type that is always "there".
+struct LdsNominal {
+    const __attribute__((address_space(3))) float* p;
+    __device__ __forceinline__ explicit operator bool() const { return true; }
+    __device__ __forceinline__ float operator[](int64_t idx) const { return p[idx]; }
+};
+struct CandidateSpecLds {
+    static constexpr bool kSigmaMap = false;
+    uint64_t seed, env_offset;
+    LdsNominal nominal;
+    float sigma, lo, hi;
+};
+// the sigma-map Spec with the mean AND the sigma in LDS (continuous envs); both slices are always "there"
+struct CandidateSpecLdsMap {
+    static constexpr bool kSigmaMap = true;
+    uint64_t seed, env_offset;
+    LdsNominal nominal, sigma_map;
+    float lo, hi;
+};
 // (KEYS_IN_PLACE: as philox4x32_10's — for the 4-state plan kernels, whose float64 InvertedPendulum instantiations have no scalar
 // registers left for twenty precomputed round keys; the seed is a kernel argument there)
 template <bool KEYS_IN_PLACE = false>

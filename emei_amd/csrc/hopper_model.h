@@ -951,6 +951,7 @@ struct HopperBody {
     static constexpr int kMinWavesPerEU = SOLVER == EMEI_SOLVER_SWEEP1 ? 2 : 1;
     static constexpr bool kUnrollRK4 = false;  // unrolled: the same time with the Newton solver (25.76 vs 25.73 ms), 4x the code
     static constexpr int kScratchPerLane = 0;
+    static constexpr bool kFusedMpc = false;  // ~10^4 instructions per step: a control loop on it is bound by compute, not by launches
     static constexpr bool kHasCtrlCost = true;
     static constexpr bool kObsIsState = true;
     static constexpr bool kSpareReset = false;

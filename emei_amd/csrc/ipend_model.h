@@ -62,6 +62,7 @@ struct InvPendBody {
     static constexpr int kMinWavesPerEU = 1;
     static constexpr bool kUnrollRK4 = true;
     static constexpr int kScratchPerLane = 0;
+    static constexpr bool kFusedMpc = false;  // the default InvertedPendulum is served by the 4-state kernels
     static constexpr bool kHasCtrlCost = false;
     static constexpr bool kObsIsState = true;
     static constexpr bool kSpareReset = true;

@@ -685,22 +685,7 @@ __global__ void __launch_bounds__(kBlock)
 
 // ---------------------------------------------------------------------------------------------
 // emei_mpc_mppi: receding-horizon MPPI control episodes in ONE launch (the normative text: include/emei_hip.h).
-// draw_action's Spec with the nominal in LDS: the wave's own slice [horizon(, act_dim)], indexed as a one-env nominal
-// (draw_action is called with n_envs = 1, i = 0).  A type of its own: the CandidateSpec / CandidateSpecMap instantiations are
-// the code they were.
-// The slice may sit at LDS address 0, which IS the null pointer of that address space: draw_action's "is there a nominal" tests must not
-// look at the address (the first wave of a block would draw as if it had no nominal), hence a type that is always "there".
-struct LdsNominal {
-    const __attribute__((address_space(3))) float* p;
-    __device__ __forceinline__ explicit operator bool() const { return true; }
-    __device__ __forceinline__ float operator[](int64_t idx) const { return p[idx]; }
-};
-struct CandidateSpecLds {
-    static constexpr bool kSigmaMap = false;
-    uint64_t seed, env_offset;
-    LdsNominal nominal;
-    float sigma, lo, hi;
-};
+// The draws read the nominal from the wave's LDS slice: CandidateSpecLds (emei_device.h, shared with the body kernels' controllers).
 
 template <class Env>
 struct MpcArgs {
@@ -911,14 +896,8 @@ __global__ void __launch_bounds__(kBlock) pend_mpc_mppi_kernel(const MpcArgs<Env
 
 // ---------------------------------------------------------------------------------------------
 // emei_mpc_cem: receding-horizon CEM control episodes in ONE launch (the normative text: include/emei_hip.h).
-// draw_action's sigma-map Spec with the mean AND the sigma in LDS (the continuous envs; the discrete ones keep CandidateSpecLds: the
-// sigma-map path of draw_action has no coin-flip branch).  Both slices are always "there": see LdsNominal.
-struct CandidateSpecLdsMap {
-    static constexpr bool kSigmaMap = true;
-    uint64_t seed, env_offset;
-    LdsNominal nominal, sigma_map;
-    float lo, hi;
-};
+// The draws of the continuous envs read the mean AND the sigma from LDS: CandidateSpecLdsMap (emei_device.h); the discrete ones keep
+// CandidateSpecLds: the sigma-map path of draw_action has no coin-flip branch.
 
 template <class Env>
 struct MpcCemArgs {

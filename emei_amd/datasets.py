@@ -41,8 +41,9 @@ def collect(env, n_steps, actions=None, seed=0, device_rng=True, policy=None, mp
     emei_step launch per step, observations after a device reset rebuilt the same way); else uniform random
     actions (`env.action_space.sample()`, zoo/util.py:58) in ONE fused rollout launch.
     mpc: instead of either, dict(horizon=, n_candidates=, temperature=[, seed=, discount=, sigma=, refill=, clamp=, nominal=]) — an
-    MPPI controller on the true dynamics acts (Engine.mpc_mppi: ONE launch with auto-reset, the 4-state envs; seed defaults to
-    `seed`, nominal to `refill` everywhere).  With planner="cem" in the dict a CEM controller acts instead (Engine.mpc_cem):
+    MPPI controller on the true dynamics acts (Engine.mpc_mppi: ONE launch with auto-reset, the 4-state envs and the
+    InvertedDoublePendulum — a continuous env needs sigma=; seed defaults to `seed`, nominal to `refill` everywhere).  With
+    planner="cem" in the dict a CEM controller acts instead (Engine.mpc_cem):
     dict(planner="cem", horizon=, n_candidates=, n_elites=[, iterations=, sigma=, sigma_min=, seed=, discount=, refill=, clamp=,
     nominal=]); planner defaults to "mppi"."""
     eng = env.engine

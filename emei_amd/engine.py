@@ -460,14 +460,15 @@ class Engine:
     @_on_device
     def mpc_mppi(self, T, H, K, seed, temperature, nominal, discount=1.0, sigma=None, refill=None, clamp=None, auto_reset=False,
                  out=None, diagnostics=False):
-        """T control steps of receding-horizon MPPI in one launch (emei_mpc_mppi; the 4-state envs on their own kernels): per
-        step the nominal is clamped to `clamp`, updated as plan_mppi(H, K, seed + t, temperature, nominal=nominal, out=nominal)
-        updates it, its first entry is the action (discrete envs: entry >= 0.5), the envs take step(action, auto_reset), and the
+        """T control steps of receding-horizon MPPI in one launch (emei_mpc_mppi; the 4-state envs and the InvertedDoublePendulum
+        without observation noise, each on kernels of its own): per step the nominal is clamped to `clamp`, updated as
+        plan_mppi(H, K, seed + t, temperature, nominal=nominal, out=nominal) updates it, its first entry is the action (discrete envs: entry >= 0.5), the envs take step(action, auto_reset), and the
         nominal is shifted by one step with `refill` behind it (an env that was reset: `refill` everywhere) — bit for bit what
         that loop of plan_mppi and step computes, state, counters and compact_done() included.
         nominal: float32 [H, N(, act_dim)] on the engine's device, updated IN PLACE (ready for the next call: T = a + b steps equal
         a call with (a, seed) and one with (b, seed + a)).  refill: default 0.5 (discrete) / 0.0 (continuous).  clamp: (lo, hi),
-        default (0.05, 0.95) on the discrete envs and the ctrlrange on the continuous ones.  out: (obs, reward, done) as rollout's.
+        default (0.05, 0.95) on the discrete envs and the ctrlrange on the continuous ones (InvertedPendulum +-3,
+        InvertedDoublePendulum +-1).  out: (obs, reward, done) as rollout's.
         -> (actions [T, N(, act_dim)] int64 / float32, obs [T, N, obs_dim] f32, reward [T, N] f32, done [T, N] u8
         [, plan_return float64 [T, N], ess float64 [T, N]]: every step's best candidate return and effective sample size)."""
         T = int(T)
@@ -494,7 +495,7 @@ class Engine:
     @_on_device
     def mpc_cem(self, T, H, K, n_elites, seed, nominal, iterations=1, sigma=None, sigma_min=0.0, discount=1.0, refill=None, clamp=None,
                 auto_reset=False, out=None, diagnostics=False):
-        """T control steps of receding-horizon CEM in one launch (emei_mpc_cem; the 4-state envs on their own kernels): per step,
+        """T control steps of receding-horizon CEM in one launch (emei_mpc_cem; the envs mpc_mppi serves): per step,
         `iterations` times, the mean is clamped to `clamp` and refitted as plan_cem(H, K, n_elites, seed + t * iterations + j,
         nominal=mean, sigma=std, out=mean, out_sigma=std) refits it — std a per-entry tensor that starts every control step at
         `sigma` and is floored at `sigma_min` after every refit (continuous envs; the discrete ones have none) — then the mean's first

@@ -343,7 +343,8 @@ class HipEnv(EmeiEnv):
 
     def mpc_mppi(self, n_steps, horizon, n_candidates, seed, temperature, nominal, discount=1.0, sigma=None, refill=None, clamp=None,
                  auto_reset=None, diagnostics=False):
-        """n_steps control steps of receding-horizon MPPI in one launch (Engine.mpc_mppi, ABI emei_mpc_mppi; the 4-state envs):
+        """n_steps control steps of receding-horizon MPPI in one launch (Engine.mpc_mppi, ABI emei_mpc_mppi; the 4-state envs and the
+        InvertedDoublePendulum):
         per step plan_mppi(horizon, n_candidates, seed + t, temperature, nominal=nominal, out=nominal) on the clamped nominal, its first
         entry as the action (discrete envs: >= 0.5), step(), and the nominal shifted by one step with `refill` behind it — the same
         bits as that loop —
@@ -370,7 +371,8 @@ class HipEnv(EmeiEnv):
 
     def mpc_cem(self, n_steps, horizon, n_candidates, n_elites, seed, nominal, iterations=1, sigma=None, sigma_min=0.0, discount=1.0,
                 refill=None, clamp=None, auto_reset=None, diagnostics=False):
-        """n_steps control steps of receding-horizon CEM in one launch (Engine.mpc_cem, ABI emei_mpc_cem; the 4-state envs): per step
+        """n_steps control steps of receding-horizon CEM in one launch (Engine.mpc_cem, ABI emei_mpc_cem; the 4-state envs and the
+        InvertedDoublePendulum): per step
         `iterations` refits of plan_cem(horizon, n_candidates, n_elites, seed + t * iterations + j, nominal=mean, sigma=std) on the clamped
         mean — std starting at `sigma` every step and floored at `sigma_min` — the mean's first entry as the action (discrete envs:
         >= 0.5), step(), and the mean shifted by one step with `refill` behind it — the same bits as that loop —

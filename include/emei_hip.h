@@ -45,7 +45,9 @@ extern "C" {
  *    emei_mpc_mppi_workspace_bytes, emei_mpc_mppi (receding-horizon MPPI control episodes of the 4-state family in one launch:
  *    plan, act, step, auto-reset and warm start per control step without leaving the device), EMEI_KERNEL_PEND_MPC_MPPI;
  *    emei_mpc_cem_workspace_bytes, emei_mpc_cem (the same control episodes with the cross-entropy method as the planner: `iterations`
- *    refits of emei_plan_cem per control step, the per-entry sigma kept on the device), EMEI_KERNEL_PEND_MPC_CEM. */
+ *    refits of emei_plan_cem per control step, the per-entry sigma kept on the device), EMEI_KERNEL_PEND_MPC_CEM;
+ *    emei_mpc_mppi and emei_mpc_cem also serve the four InvertedDoublePendulum envs (any integrator, either precision, no
+ *    observation noise) on kernels of the body family, EMEI_KERNEL_BODY_MPC_MPPI / EMEI_KERNEL_BODY_MPC_CEM. */
 #define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
@@ -467,7 +469,9 @@ EMEI_API int emei_plan_cem(emei_env* h, int32_t horizon, int32_t n_candidates, i
 /* Receding-horizon MPPI control on the true dynamics, whole episodes in ONE launch (plus a small one that packs the done mask): what
  * the loop "emei_plan_mppi, threshold / first entry, emei_step, shift the nominal" does in three launches and a handful of array
  * operations per control step.  For the 4-state family on its own kernels (CartPole, CartPoleRK4, InvertedPendulum with the euler
- * integrator and no observation noise), where a plan is microseconds of arithmetic and the loop is bound by launches.
+ * integrator and no observation noise) and for the InvertedDoublePendulum (all four envs, any integrator, either precision, init noise
+ * in either layout, no observation noise; its observation row is six floats: obs_out is [n_steps, n_envs, 6]), where a plan is
+ * microseconds of arithmetic and the loop is bound by launches.
  *
  * Semantics (normative).  For every env i and t = 0 .. n_steps - 1, m being env i's column of `nominal`:
  *   1. Clamp.  m[h(, a)] = fminf(fmaxf(m[h(, a)], nominal_lo), nominal_hi); -inf / +inf: no clamp.  Non-finite nominal entries are the
@@ -498,9 +502,9 @@ EMEI_API int emei_plan_cem(emei_env* h, int32_t horizon, int32_t n_candidates, i
  * (0, 1]; temperature not finite or <= 0; refill not finite, nominal_lo > nominal_hi or either NaN; horizon > EMEI_MPC_MAX_HORIZON
  * (the nominal lives in LDS); then a NULL handle; emei_plan_shooting's candidate checks (sigma finite and > 0 on a continuous env,
  * n_envs * n_candidates, a wrong action_dtype), unknown flags; NULL nominal, workspace or actions_out.  EMEI_ERR_STATE without a
- * state.  EMEI_ERR_UNSUPPORTED, the message naming the reason, for a handle emei_rollout runs on the body kernels (HalfCheetah,
- * Hopper, InvertedDoublePendulum; InvertedPendulum with another integrator or observation noise) and for a handle with observation
- * peers set (emei_set_obs_peers). */
+ * state.  EMEI_ERR_UNSUPPORTED, the message naming the reason, for the other handles emei_rollout runs on the body kernels
+ * (HalfCheetah, Hopper; InvertedPendulum with another integrator or observation noise), for an InvertedDoublePendulum handle with
+ * observation noise (the plan steps the model without it) and for a handle with observation peers set (emei_set_obs_peers). */
 #define EMEI_MPC_MAX_HORIZON 256
 /* bytes of device scratch emei_mpc_mppi needs for this shape; host only, no handle, no HIP call.
  * Negative (EMEI_ERR_INVALID) where emei_plan_mppi_workspace_bytes is. */
@@ -513,7 +517,8 @@ EMEI_API int emei_mpc_mppi(emei_env* h, int32_t n_steps, int32_t horizon, int32_
 /* Receding-horizon control with the cross-entropy method as the planner (PETS / PlaNet-style MPC on the true dynamics), whole episodes
  * in ONE launch (plus the small one that packs the done mask): what the loop "`iterations` times emei_plan_cem in place, first entry,
  * emei_step, shift the mean" does in 2 * iterations + 1 launches and a handful of array operations per control step.  The same envs
- * as emei_mpc_mppi: the 4-state family on its own kernels.
+ * as emei_mpc_mppi: the 4-state family on its own kernels, and the InvertedDoublePendulum without observation noise (obs_out
+ * [n_steps, n_envs, 6]: its observation row is six floats).
  *
  * Semantics (normative).  For every env i and t = 0 .. n_steps - 1, m being env i's column of `nominal` and, on continuous envs, s a
  * per-entry sigma column of the same shape that lives only inside the call:
@@ -551,7 +556,8 @@ EMEI_API int emei_mpc_mppi(emei_env* h, int32_t n_steps, int32_t horizon, int32_
  * finite or < 0, horizon > EMEI_MPC_MAX_HORIZON (the mean and the sigma live in LDS); then a NULL handle; emei_plan_shooting's
  * candidate checks (sigma finite and > 0 on a continuous env, n_envs * n_candidates), a wrong action_dtype, unknown flags; NULL
  * nominal, workspace or actions_out.  EMEI_ERR_STATE without a state.  EMEI_ERR_UNSUPPORTED exactly where emei_mpc_mppi gives it:
- * a handle emei_rollout runs on the body kernels, and a handle with observation peers set. */
+ * a handle emei_rollout runs on the body kernels other than an InvertedDoublePendulum without observation noise, and a handle with
+ * observation peers set. */
 /* bytes of device scratch emei_mpc_cem needs for this shape; host only, no handle, no HIP call.
  * Negative (EMEI_ERR_INVALID) where emei_plan_mppi_workspace_bytes is. */
 EMEI_API int64_t emei_mpc_cem_workspace_bytes(int64_t n_envs, int32_t n_candidates);
@@ -576,7 +582,9 @@ enum emei_kernel_id {
     EMEI_KERNEL_PEND_STAGED_PEERS_FREQ1 = 9, /* pend_rollout_staged_peers_kernel<Env, ActT, true>: with the peer stores of emei_set_obs_peers */
     EMEI_KERNEL_PEND_STAGED_PEERS = 10,      /* pend_rollout_staged_peers_kernel<Env, ActT, false> */
     EMEI_KERNEL_PEND_MPC_MPPI = 11,          /* pend_mpc_mppi_kernel<Env>: emei_mpc_mppi (it steps the handle, so it reports here) */
-    EMEI_KERNEL_PEND_MPC_CEM = 12            /* pend_mpc_cem_kernel<Env>: emei_mpc_cem (likewise) */
+    EMEI_KERNEL_PEND_MPC_CEM = 12,           /* pend_mpc_cem_kernel<Env>: emei_mpc_cem (likewise) */
+    EMEI_KERNEL_BODY_MPC_MPPI = 13,          /* body_mpc_mppi_kernel<Body, RK4>: emei_mpc_mppi on an InvertedDoublePendulum handle */
+    EMEI_KERNEL_BODY_MPC_CEM = 14            /* body_mpc_cem_kernel<Body, RK4>: emei_mpc_cem on an InvertedDoublePendulum handle */
 };
 EMEI_API int emei_last_rollout_kernel(emei_env* h);
 

@@ -8,7 +8,9 @@ Method: after `--warmup` untimed episodes of each route (code objects loaded, wo
 rounds; every round times ONE episode of each route with device events around it (the loop's host overhead is inside its window: the
 events bracket everything its T iterations enqueue), the two routes alternating inside the round so that drift hits both alike.
 Reported per shape: the median over the rounds and the spread (min, max) of either route, and the ratio of the medians.
-Shapes: CartPoleSwingUp N = 256 and N = 65 536, ReboundInvertedPendulumSwingUp N = 256; K = 64, H = 30; T = 200 (20 at N = 65 536).
+Shapes: CartPoleSwingUp N = 256 and N = 65 536, ReboundInvertedPendulumSwingUp N = 256, ReboundInvertedDoublePendulumSwingUp (the
+fused call on the body kernels' controllers, body_mpc_kernels.h) N = 256 and N = 16 384; K = 64, H = 30; T = 200 (20 at the large N;
+the InvertedDoublePendulum 400 and 40, so that its MPPI windows exceed 10 ms).
 --planner cem: the same comparison for Engine.mpc_cem (emei_mpc_cem) against the README's CEM loop — per control step a roll, a
 refill, a fresh std, ITERATIONS = 3 times (a clamp of the mean on the discrete envs, plan_cem in place: two launches, a floor of the
 std on the continuous ones), and a step — with N_ELITES = 8, at the same shapes (tests/test_gpu_mpc_cem.py: the same bits).
@@ -23,13 +25,16 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from emei_amd.engine import Engine  # noqa: E402
+from emei_amd.engine import _CTRL_RANGE, Engine  # noqa: E402
 
 # (env, N, K, H, T, sigma)
 SHAPES = [
     ("CartPoleSwingUp", 256, 64, 30, 200, None),
     ("CartPoleSwingUp", 65536, 64, 30, 20, None),
     ("ReboundInvertedPendulumSwingUp", 256, 64, 30, 200, 0.5),
+    # (T doubled against the shapes above: at T = 200 / 20 the fused MPPI episodes are 8.2 / 6.6 ms, short of a ~10 ms window)
+    ("ReboundInvertedDoublePendulumSwingUp", 256, 64, 30, 400, 0.5),
+    ("ReboundInvertedDoublePendulumSwingUp", 16384, 64, 30, 40, 0.5),
 ]
 TEMPERATURE, DISCOUNT = 0.5, 0.99
 ITERATIONS, N_ELITES, SIGMA_MIN = 3, 8, 0.05  # --planner cem
@@ -77,7 +82,7 @@ def main():
         eng.reset(seed=0)
         state0 = eng.get_state().clone()
         refill = 0.5 if eng.act_dim == 0 else 0.0
-        lo, hi = (0.05, 0.95) if eng.act_dim == 0 else (-3.0, 3.0)
+        lo, hi = (0.05, 0.95) if eng.act_dim == 0 else _CTRL_RANGE.get(name, (-1.0, 1.0))  # Engine.mpc_*'s default clamp
         nominal = torch.empty((H, N), dtype=torch.float32, device=eng.device)
         outs = eng.alloc_outputs(T)
 
