@@ -25,3 +25,11 @@ from .envs import (  # noqa: F401
     make,
     spec,
 )
+
+
+def __getattr__(name):  # MLPPolicy needs torch: imported on first use, like the engine
+    if name == "MLPPolicy":
+        from .policy import MLPPolicy
+
+        return MLPPolicy
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -40,12 +40,25 @@ KERNEL_NAMES = {0: "none", 1: "pend_rollout_staged_kernel<freq1>", 2: "pend_roll
                 7: "body_rollout_kernel (chunked work items)", 8: "body_rollout_kernel<rk4> (chunked work items)",
                 9: "pend_rollout_staged_peers_kernel<freq1>", 10: "pend_rollout_staged_peers_kernel", 11: "pend_mpc_mppi_kernel",
                 12: "pend_mpc_cem_kernel", 13: "body_mpc_mppi_kernel", 14: "body_mpc_cem_kernel"}
+# ... and the ids of emei_rollout_policy's kernels, a table of their own (KERNEL_NAMES stays the 15 ids of emei_rollout and the fused
+# controllers); kernel_name() looks an id up in both
+POLICY_KERNEL_NAMES = {15: "pend_policy_rollout_kernel", 16: "body_policy_rollout_kernel", 17: "body_policy_rollout_kernel<rk4>"}
+
+
+def kernel_name(kernel_id):
+    """name of an enum emei_kernel_id value (emei_last_rollout_kernel)"""
+    return KERNEL_NAMES[kernel_id] if kernel_id in KERNEL_NAMES else POLICY_KERNEL_NAMES[kernel_id]
+
+
 KERNEL_PEND_STAGED_FREQ1, KERNEL_PEND_STAGED, KERNEL_PEND_GENERIC_FULL, KERNEL_PEND_GENERIC, KERNEL_BODY, KERNEL_BODY_RK4 = 1, 2, 3, 4, 5, 6
 KERNEL_BODY_CHUNKED, KERNEL_BODY_RK4_CHUNKED = 7, 8
 KERNEL_PEND_STAGED_PEERS_FREQ1, KERNEL_PEND_STAGED_PEERS = 9, 10
 KERNEL_PEND_MPC_MPPI = 11
 KERNEL_PEND_MPC_CEM = 12
 KERNEL_BODY_MPC_MPPI, KERNEL_BODY_MPC_CEM = 13, 14  # the InvertedDoublePendulum's fused controllers
+KERNEL_PEND_POLICY, KERNEL_BODY_POLICY, KERNEL_BODY_POLICY_RK4 = 15, 16, 17  # emei_rollout_policy
+POLICY_OUT_CLIP, POLICY_OUT_TANH = 0, 1  # enum emei_policy_out
+POLICY_MAX_HIDDEN = 1024  # EMEI_POLICY_MAX_HIDDEN
 MPC_MAX_HORIZON = 256  # EMEI_MPC_MAX_HORIZON
 MAX_OBS_PEERS = 8  # EMEI_MAX_OBS_PEERS
 # enum emei_ode_method: `method` of ODE_approximation (base_control.py:133-173), classic control only
@@ -94,6 +107,21 @@ class EmeiConfig(C.Structure):
     ]
 
 
+class EmeiPolicy(C.Structure):
+    """struct emei_policy (include/emei_hip.h): the weights are device pointers."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("hidden", C.c_int32),
+        ("out_mode", C.c_int32),
+        ("reserved", C.c_int32),
+        ("w1", C.c_void_p),
+        ("b1", C.c_void_p),
+        ("w2", C.c_void_p),
+        ("b2", C.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/emei_hip.h declares
 _vp, _i32, _i64, _u32, _u64, _dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 SYMBOLS = {
@@ -137,6 +165,7 @@ SYMBOLS = {
     "emei_mpc_cem_workspace_bytes": (_i64, [_i64, _i32]),
     "emei_mpc_cem": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _u64, _vp, _dbl, _dbl, _dbl, C.c_float, C.c_float, C.c_float, _vp, _vp,
                                C.c_int, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "emei_rollout_policy": (C.c_int, [_vp, _i32, C.POINTER(EmeiPolicy), _vp, C.c_int, _vp, _vp, _vp, _u32, _vp]),
     "emei_compact_done": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emei_get_counters": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emei_episode_init_obs": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),

@@ -1104,6 +1104,61 @@ extern "C" EMEI_API int emei_mpc_cem(emei_env* h, int32_t n_steps, int32_t horiz
     return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
 }
 
+// ---------------------------------------------------------------------------------------------
+// emei_rollout_policy: n_steps of "observe, evaluate the policy, emei_step" in one launch of the family's policy rollout kernel
+// (pendulum_kernels.h:pend_policy_rollout_kernel, body_kernels.h:body_policy_rollout_kernel); the kernel leaves the done mask itself.
+extern "C" EMEI_API int emei_rollout_policy(emei_env* h, int32_t n_steps, const emei_policy* policy, void* actions_out, int action_dtype,
+                                            float* obs_out, float* reward_out, uint8_t* done_out, uint32_t flags, void* stream) {
+    const char* fn = "emei_rollout_policy";
+    if (n_steps < 1) return fail(EMEI_ERR_INVALID, "%s: n_steps=%d < 1", fn, n_steps);
+    if (!policy) return fail(EMEI_ERR_INVALID, "%s: null policy", fn);
+    if (policy->struct_size != sizeof(emei_policy))
+        return fail(EMEI_ERR_INVALID, "%s: policy.struct_size=%u != sizeof(emei_policy)=%zu", fn, policy->struct_size, sizeof(emei_policy));
+    if (policy->hidden < 0 || policy->hidden > EMEI_POLICY_MAX_HIDDEN)
+        return fail(EMEI_ERR_INVALID, "%s: policy.hidden=%d is outside [0, EMEI_POLICY_MAX_HIDDEN=%d]", fn, policy->hidden, EMEI_POLICY_MAX_HIDDEN);
+    if (policy->out_mode != EMEI_POLICY_OUT_CLIP && policy->out_mode != EMEI_POLICY_OUT_TANH)
+        return fail(EMEI_ERR_INVALID, "%s: unknown policy.out_mode=%d", fn, policy->out_mode);
+    if (policy->reserved != 0) return fail(EMEI_ERR_INVALID, "%s: policy.reserved=%d must be 0", fn, policy->reserved);
+    if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
+    if (!policy->w2 || !policy->b2) return fail(EMEI_ERR_INVALID, "%s: null policy.%s", fn, !policy->w2 ? "w2" : "b2");
+    if (policy->hidden > 0 && (!policy->w1 || !policy->b1))
+        return fail(EMEI_ERR_INVALID, "%s: null policy.%s with hidden=%d", fn, !policy->w1 ? "w1" : "b1", policy->hidden);
+    if (action_dtype < EMEI_ACT_U8 || action_dtype > EMEI_ACT_F32 || (h->act_dim > 0) != (action_dtype == EMEI_ACT_F32))
+        return fail(EMEI_ERR_INVALID, "%s: action_dtype=%d: actions_out is uint8 / int32 / int64 for the discrete envs, float32 for the "
+                                      "continuous ones", fn, action_dtype);
+    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "%s: unknown flags 0x%x", fn, flags);
+    EMEI_ON_DEVICE(h, fn);
+    if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    if (h->peers.count > 0)
+        return fail(EMEI_ERR_UNSUPPORTED, "%s: observation peers are set (emei_set_obs_peers), which this kernel does not serve", fn);
+    PolicyArgs pa{};
+    pa.w1 = policy->w1, pa.b1 = policy->b1, pa.w2 = policy->w2, pa.b2 = policy->b2;
+    pa.actions_out = actions_out, pa.hidden = policy->hidden, pa.out_mode = policy->out_mode, pa.action_dtype = action_dtype;
+    ctrl_range(h->cfg.env_id, pa.lo, pa.hi);
+    int rc;
+    if (!steps_as_body(h->cfg)) {
+        PendLaunch L = pend_base(h, stream);
+        L.op = PEND_OP_POLICY;
+        L.action_dtype = action_dtype;
+        L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
+        L.n_steps = n_steps;
+        L.flags = flags;
+        L.policy = pa;
+        L.selected = &h->last_kernel;
+        rc = pend_launch(L);
+    } else {
+        BodyLaunch L = body_base(h, stream);
+        L.op = BODY_OP_POLICY;
+        L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
+        L.n_steps = n_steps;
+        L.flags = flags;
+        L.policy = pa;
+        L.selected = &h->last_kernel;
+        rc = body_launch(L);
+    }
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+}
+
 extern "C" EMEI_API int emei_compact_done(emei_env* h, int32_t* idx_out, int32_t* count_out, void* stream) {
     if (!h || !idx_out || !count_out) return fail(EMEI_ERR_INVALID, "emei_compact_done: null argument");
     EMEI_ON_DEVICE(h, "emei_compact_done");

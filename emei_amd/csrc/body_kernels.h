@@ -167,7 +167,8 @@ enum BodyOp { BODY_OP_ROLLOUT = 0, BODY_OP_RESET, BODY_OP_GET_OBS, BODY_OP_INIT_
               BODY_OP_OCCUPANCY /* host only: *selected = waves of the rollout kernel (of L.integrator) the current device holds at once */,
               BODY_OP_PLAN /* emei_evaluate_sequences: body_plan_kernel */,
               BODY_OP_MPC_MPPI /* emei_mpc_mppi: body_mpc_mppi_kernel (Body::kFusedMpc) */,
-              BODY_OP_MPC_CEM /* emei_mpc_cem: body_mpc_cem_kernel (Body::kFusedMpc) */ };
+              BODY_OP_MPC_CEM /* emei_mpc_cem: body_mpc_cem_kernel (Body::kFusedMpc) */,
+              BODY_OP_POLICY /* emei_rollout_policy: body_policy_rollout_kernel */ };
 
 // What BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM take beyond the base descriptor: n_steps control steps of the planner with plan.n_candidates
 // candidates over `horizon` steps under plan.discount; plan.cand carries the call's seed, sigma and the ctrlrange (its nominal is
@@ -225,6 +226,7 @@ struct BodyLaunch {
     int* selected = nullptr;  // out: enum emei_kernel_id of the rollout kernel launched
     PlanLaunch plan;  // BODY_OP_PLAN; n_steps = the horizon, obs_out = final_obs [n * K, NO] or null
     MpcLaunch mpc;    // BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM
+    PolicyArgs policy = {};  // BODY_OP_POLICY: BODY_OP_ROLLOUT's fields without `actions`; weights, ctrlrange and actions_out (float32)
 };
 int body_launch(const BodyLaunch& L);  // body_dispatch.hip
 
@@ -577,6 +579,153 @@ __global__ void __launch_bounds__(rollout_block<Body>()) __attribute__((amdgpu_w
     EMEI_PROFILE_END();
 }
 
+// emei_rollout_policy (the normative text: include/emei_hip.h): the one-piece loop of body_rollout_kernel — spare / per-lane resets,
+// observation noise, padding lanes parked, LDS-staged observation stores — with the action staging replaced by the lane's own
+// evaluation of the policy (emei_device.h:policy_eval; the weights arrive as scalar loads).  The action of step t + 1 is computed at
+// the END of step t, from the float32 row the step emitted while it is still in registers (after an auto-reset: from the new episode's
+// first observation, body_init_obs_kernel's arithmetic), so NA floats cross the step instead of NO; the action of the first step comes
+// from the state as emei_get_obs shows it.  Padding lanes step with zero controls, as the rollout's staging gives them.
+// Always one piece: block b = env block b for all n_steps (no WorkQueue).
+template <class Body, bool RK4>
+__global__ void __launch_bounds__(rollout_block<Body>()) __attribute__((amdgpu_waves_per_eu(Body::kMinWavesPerEU)))
+    body_policy_rollout_kernel(const BodyArgs<Body> a, const PolicyArgs pol) {
+    using R = typename Body::real;
+    constexpr int NS = Body::NS, NO = Body::NO, NA = Body::NA;
+    constexpr int kBlock = rollout_block<Body>();  // shadows the library-wide 256 inside this kernel
+    constexpr int kWaves = kBlock / kWave;
+    constexpr int kObsVec = (kWave * NO + 3) / 4;  // 16-byte vectors per wave block
+    constexpr int kObsIt = (kObsVec + kWave - 1) / kWave;
+    __shared__ __attribute__((aligned(16))) float obs_s[kWaves][kObsIt * kWave * 4];
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table<kBlock>(trig_s, a.trig);  // every thread reaches the barrier: inactive lanes stay in the kernel
+    TrigCtx trig;
+    trig.tab = trig_s;
+    __shared__ R scratch_s[(Body::kScratchPerLane > 0 ? Body::kScratchPerLane : 1) * (Body::kScratchPerLane > 0 ? kBlock : 1)];
+    if constexpr (Body::kScratchPerLane > 0) trig.scratch = scratch_s;
+    trig.scratch_stride = kBlock;
+    trig.cap_hits = a.cap_hits;
+    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t n = a.n;
+    const int64_t i0 = i - lane;                             // first env of this wave
+    const int wave_envs = (int)min((int64_t)kWave, n - i0);  // ragged last wave
+    const bool active = i < n;
+
+    R s[NS];
+    int32_t steps = 0;
+    uint32_t episode = 0;
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = a.state[(int64_t)k * n + i];
+        steps = a.steps[i];
+        episode = a.episode[i];
+    } else {
+        Body::park(s);  // see body_rollout_kernel
+    }
+    const bool auto_reset = (a.flags & EMEI_FLAG_AUTO_RESET) != 0;
+    const bool obs_noise = a.noise.obs_on != 0;
+    uint32_t done = 0;
+    R spare[Body::kSpareReset ? NS : 1];
+    bool have_spare = false;
+
+    // the float32 observation of the state, as emei_get_obs / emei_episode_init_obs round it
+    auto observe = [&](float (&x)[NO]) __attribute__((always_inline)) {
+        double od[NO];
+        Body::obs_of(s, od, a.m);
+#pragma unroll
+        for (int k = 0; k < NO; ++k) x[k] = (float)od[k];
+    };
+    float act[NA];
+    {
+        float x[NO];
+        observe(x);
+        policy_eval<NO, NA, false>(pol, x, act);
+    }
+    for (int t = 0; t < a.n_steps; ++t) {
+        R ctrl[NA];
+#pragma unroll
+        for (int k = 0; k < NA; ++k) ctrl[k] = active ? (R)act[k] : R(0);
+        if (pol.actions_out && active) {
+            float* dst = (float*)pol.actions_out + ((int64_t)t * n + i) * NA;
+#pragma unroll
+            for (int k = 0; k < NA; ++k) dst[k] = act[k];
+        }
+
+        R pre[NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) pre[k] = s[k];
+        typename Body::Warm warm{};  // per env-step, as body_rollout_kernel
+        for (int k = 0; k < a.freq_rate; ++k) {  // mujoco_env.py:91-104
+            body_substep<Body, RK4>(s, ctrl, a.m, a.semi != 0, trig, warm);
+            if (obs_noise)
+                gauss_state<R, NS, false>(s, a.seed ^ kObsNoiseKey, a.env_offset + (uint64_t)i, episode,
+                                          ((uint32_t)steps * (uint32_t)a.freq_rate + (uint32_t)k) * (uint32_t)((NS + 3) / 4),
+                                          a.noise.obs, a.noise.shared != 0);
+        }
+        float o[NO];
+        R rew;
+        bool term;
+        Body::outputs(s, pre, ctrl, a.m, a.freq_rate, o, rew, term, trig);
+        ++steps;
+        const bool trunc = (a.max_episode_steps > 0) & (steps >= a.max_episode_steps);
+        done = active ? ((term ? EMEI_DONE_TERMINAL : 0u) | (trunc ? EMEI_DONE_TRUNCATED : 0u)) : 0u;
+
+        if (a.obs_out) {  // lane-wise into LDS, linear out
+            float* mine = &obs_s[wv][lane * NO];
+#pragma unroll
+            for (int k = 0; k < NO; ++k) mine[k] = o[k];
+            wave_lds_fence();
+            float* dst = a.obs_out + ((int64_t)t * n + i0) * NO;
+            if (wave_envs == kWave && (((uintptr_t)dst) & 15u) == 0) {
+#pragma unroll
+                for (int c = 0; c < kObsIt; ++c) {
+                    const int vec = c * kWave + lane;
+                    if (vec < kObsVec) store_body_out<Body::kStreamOutputs>((float4*)dst + vec, ((const float4*)obs_s[wv])[vec]);
+                }
+            } else {
+                for (int e = lane; e < wave_envs * NO; e += kWave) dst[e] = obs_s[wv][e];
+            }
+            wave_lds_fence();
+        }
+        if (active) {
+            if (a.reward_out) store_body_out<Body::kStreamOutputs>(a.reward_out + (int64_t)t * n + i, (float)rew);
+            if (a.done_out) store_body_out<Body::kStreamOutputs>(a.done_out + (int64_t)t * n + i, (uint8_t)done);
+        }
+        if (__builtin_expect(auto_reset && __ballot(done != 0) != 0ull, 0)) {
+            if constexpr (Body::kSpareReset) {
+                if (__ballot((done != 0) & !have_spare) != 0ull) {
+                    if (!have_spare) {
+                        body_init<Body>(spare, a.seed, a.env_offset + (uint64_t)i, episode + 1u, a.noise);
+                        have_spare = true;
+                    }
+                }
+                if (done != 0) {
+                    ++episode;
+                    steps = 0;
+#pragma unroll
+                    for (int k = 0; k < NS; ++k) s[k] = spare[k];
+                    have_spare = false;
+                    observe(o);
+                }
+            } else if (done != 0) {  // episodes only end by TimeLimit, for all lanes at once
+                ++episode;
+                steps = 0;
+                body_init<Body>(s, a.seed, a.env_offset + (uint64_t)i, episode, a.noise);
+                observe(o);
+            }
+        }
+        if (t + 1 < a.n_steps) policy_eval<NO, NA, false>(pol, o, act);  // wave-uniform: the next step's action
+    }
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) a.state[(int64_t)k * n + i] = s[k];
+        a.steps[i] = steps;
+        a.episode[i] = episode;
+    }
+    unsigned long long mk = __ballot(done != 0);
+    if (lane == 0 && active) a.done_mask[i / kWave] = mk;
+}
+
 template <class Body>
 __global__ void __launch_bounds__(kBlock)
     body_reset_kernel(typename Body::real* state, int32_t* steps, uint32_t* episode, int64_t n, uint64_t seed,
@@ -868,6 +1017,23 @@ static int launch_body(const BodyLaunch& L) {
             if (L.selected)
                 *L.selected = a.work ? (L.integrator == EMEI_INTEG_RK4 ? EMEI_KERNEL_BODY_RK4_CHUNKED : EMEI_KERNEL_BODY_CHUNKED)
                                      : (L.integrator == EMEI_INTEG_RK4 ? EMEI_KERNEL_BODY_RK4 : EMEI_KERNEL_BODY);
+            break;
+        }
+        case BODY_OP_POLICY: {  // always one piece: block b = env block b (the work queue is body_rollout_kernel's)
+            BodyArgs<Body> a;
+            a.state = (R*)L.state, a.steps = L.steps, a.episode = L.episode, a.done_mask = L.done_mask;
+            a.actions = nullptr, a.obs_out = L.obs_out, a.reward_out = L.reward_out, a.done_out = L.done_out;
+            a.n = L.n, a.n_steps = L.n_steps, a.freq_rate = L.freq_rate, a.max_episode_steps = L.max_episode_steps;
+            a.flags = L.flags, a.seed = L.seed, a.env_offset = L.env_offset, a.m = m;
+            a.semi = L.integrator == EMEI_INTEG_SEMI_IMPLICIT, a.noise = NoiseArgs<Body::NS>(L.noise);
+            a.trig = (const SinCosEntry*)L.trig;
+            a.cap_hits = L.cap_hits;
+            a.work = nullptr, a.chunk_steps = 0, a.n_waves = rgrid.x, a.n_items = 0;
+            if (L.integrator == EMEI_INTEG_RK4)
+                hipLaunchKernelGGL((body_policy_rollout_kernel<Body, true>), rgrid, dim3(rollout_block<Body>()), 0, L.stream, a, L.policy);
+            else
+                hipLaunchKernelGGL((body_policy_rollout_kernel<Body, false>), rgrid, dim3(rollout_block<Body>()), 0, L.stream, a, L.policy);
+            if (L.selected) *L.selected = L.integrator == EMEI_INTEG_RK4 ? EMEI_KERNEL_BODY_POLICY_RK4 : EMEI_KERNEL_BODY_POLICY;
             break;
         }
         case BODY_OP_OCCUPANCY: {

@@ -729,6 +729,64 @@ __device__ __forceinline__ void plan_reduce_wave(int64_t j, int64_t nk, int64_t 
 }
 
 // ---------------------------------------------------------------------------------------------
+// emei_rollout_policy: the feedback policy of the two policy rollout kernels (the normative text: include/emei_hip.h).
+// Kernel-argument form of struct emei_policy plus what the kernels need with it.
+struct PolicyArgs {
+    const float* w1;  // [hidden, NO]
+    const float* b1;  // [hidden]
+    const float* w2;  // [n_out, hidden] (hidden == 0: [n_out, NO])
+    const float* b2;  // [n_out]
+    void* actions_out;  // [n_steps, n(, NA)] in action_dtype, or null
+    int32_t hidden, out_mode, action_dtype;
+    float lo, hi;  // the env's ctrlrange (continuous envs)
+};
+// The weights are the same for every lane and never written during the launch: they are read through the CONSTANT address space
+// with wave-uniform indices (kernel-argument pointers, loop counters), which hipcc selects as scalar loads (s_load_dword*) into
+// SGPRs — one fetch per wave through the scalar cache, no VGPR and no LDS per weight; a v_fma_f64 takes the converted weight
+// next to the lane's own x / h.  (An LDS copy read by broadcast would need (NO + n_out + 1) * hidden floats per block — 100 KiB
+// for the cheetah at EMEI_POLICY_MAX_HIDDEN, on top of its solver's slots — and a fill phase per launch.)
+typedef const __attribute__((address_space(4))) float* PolicyWeights;
+
+// One evaluation for one lane: x[NO] -> act[NA] (discrete envs: act[0] is 0.f or 1.f).  One hidden unit at a time: z over the
+// NO inputs, h_j, then its contribution to the NA accumulators — nothing of size `hidden` is ever live.  fma() on float64: the
+// products of two widened float32 values are exact, so this is the ascending-order sum of the specification, bit for bit.
+template <int NO, int NA, bool DISCRETE>
+__device__ __forceinline__ void policy_eval(const PolicyArgs& pa, const float (&x)[NO], float (&act)[NA]) {
+    const PolicyWeights w1 = (PolicyWeights)pa.w1, b1 = (PolicyWeights)pa.b1, w2 = (PolicyWeights)pa.w2, b2 = (PolicyWeights)pa.b2;
+    const int hidden = pa.hidden;  // wave-uniform, as every index below
+    double y[NA];
+#pragma unroll
+    for (int q = 0; q < NA; ++q) y[q] = (double)b2[q];
+    if (hidden > 0) {
+        for (int j = 0; j < hidden; ++j) {
+            double z = (double)b1[j];
+#pragma unroll
+            for (int k = 0; k < NO; ++k) z = fma((double)w1[j * NO + k], (double)x[k], z);
+            float hj = (float)z;
+            hj = hj > 0.f ? hj : 0.f;  // NaN -> 0
+#pragma unroll
+            for (int q = 0; q < NA; ++q) y[q] = fma((double)w2[q * hidden + j], (double)hj, y[q]);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NO; ++k) {
+#pragma unroll
+            for (int q = 0; q < NA; ++q) y[q] = fma((double)w2[q * NO + k], (double)x[k], y[q]);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NA; ++q) {
+        if constexpr (DISCRETE) {
+            act[q] = y[q] >= 0.0 ? 1.f : 0.f;  // NaN -> 0
+        } else if (pa.out_mode == EMEI_POLICY_OUT_TANH) {  // wave-uniform
+            act[q] = (float)(0.5 * ((double)pa.hi + (double)pa.lo) + 0.5 * ((double)pa.hi - (double)pa.lo) * tanh(y[q]));
+        } else {
+            act[q] = fminf(fmaxf((float)y[q], pa.lo), pa.hi);  // NaN -> lo
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // action loads: dtype is wave-uniform, so the switch is a scalar branch
 __device__ __forceinline__ int load_discrete_action(const void* p, int dtype, int64_t idx) {
     switch (dtype) {

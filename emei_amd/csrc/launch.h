@@ -7,7 +7,7 @@
 
 namespace emei {
 
-enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC, PEND_OP_MPC_CEM };
+enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC, PEND_OP_MPC_CEM, PEND_OP_POLICY };
 
 // emei_set_obs_peers: the gathered buffers the staged rollout kernel also writes every observation row to
 struct ObsPeers {
@@ -86,6 +86,9 @@ struct PendLaunch {
     int32_t n_elites = 1, iterations = 1;
     float sigma_min = 0.f;
     double* elite_return_out = nullptr;
+    // PEND_OP_POLICY (emei_rollout_policy): PEND_OP_ROLLOUT's fields without `actions`; the weights, the ctrlrange and actions_out (in
+    // policy.action_dtype) travel in `policy`
+    PolicyArgs policy = {};
 };
 
 // pendulum_kernels.hip

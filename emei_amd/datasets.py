@@ -14,6 +14,8 @@ import json
 import numpy as np
 import torch
 
+from .policy import MLPPolicy
+
 DATASET_KEYS = ("observations", "next_observations", "actions", "rewards", "dones", "timeouts")
 
 
@@ -40,6 +42,8 @@ def collect(env, n_steps, actions=None, seed=0, device_rng=True, policy=None, mp
     actions [N(, act_dim)]` evaluated between steps (the agent.predict loop of zoo/util.py:54-59: one
     emei_step launch per step, observations after a device reset rebuilt the same way); else uniform random
     actions (`env.action_space.sample()`, zoo/util.py:58) in ONE fused rollout launch.
+    A policy that is an emei_amd.MLPPolicy is evaluated inside the rollout kernel (Engine.rollout_policy: ONE launch, the same
+    actions as the loop gives with that object as the callable); any other callable takes the per-step loop.
     mpc: instead of either, dict(horizon=, n_candidates=, temperature=[, seed=, discount=, sigma=, refill=, clamp=, nominal=]) — an
     MPPI controller on the true dynamics acts (Engine.mpc_mppi: ONE launch with auto-reset, the 4-state envs and the
     InvertedDoublePendulum — a continuous env needs sigma=; seed defaults to `seed`, nominal to `refill` everywhere).  With
@@ -71,6 +75,8 @@ def collect(env, n_steps, actions=None, seed=0, device_rng=True, policy=None, mp
             actions, next_obs, rew, done = eng.mpc_mppi(T, H, K, kw.pop("seed", seed), plan_arg, nominal, auto_reset=True, **kw)
         else:
             actions, next_obs, rew, done = eng.mpc_cem(T, H, K, plan_arg, kw.pop("seed", seed), nominal, auto_reset=True, **kw)
+    elif actions is None and isinstance(policy, MLPPolicy):  # the policy is evaluated inside the rollout kernel: ONE launch
+        actions, next_obs, rew, done = eng.rollout_policy(T, policy, auto_reset=True)
     elif actions is None and policy is not None:
         next_obs, rew, done = eng.alloc_outputs(T)
         acts_t, cur, epi = [], obs0, epi0.clone()

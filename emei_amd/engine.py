@@ -184,7 +184,7 @@ class Engine:
         self._peer_refs = [p for p in peers if torch.is_tensor(p)]  # keep local targets alive while they are written to
 
     def last_kernel(self):
-        """enum emei_kernel_id of the kernel the last step / rollout launched (_lib.KERNEL_NAMES)."""
+        """enum emei_kernel_id of the kernel the last step / rollout launched (_lib.kernel_name)."""
         self._live()
         return int(L.lib().emei_last_rollout_kernel(self._h))
 
@@ -323,6 +323,31 @@ class Engine:
         L.check(L.lib().emei_rollout(self._h, T, _ptr(actions), dt, _ptr(obs), _ptr(rew), _ptr(done),
                                      L.FLAG_AUTO_RESET if auto_reset else 0, _stream()))
         return obs, rew, done
+
+    @_on_device
+    def rollout_policy(self, T, policy, auto_reset=False, out=None):
+        """T closed-loop steps under a feedback policy in one launch (emei_rollout_policy): per step the policy (policy.MLPPolicy)
+        is evaluated inside the kernel on the observation the env holds — get_obs() rounded to float32 at first, then the row each
+        step emits, or episode_init_obs of the new episode after an auto-reset — and the envs take step(action, auto_reset): bit for
+        bit what that loop computes with policy(obs) as the callable (out="clip" and the discrete envs; out="tanh" up to the
+        device's tanh), state, counters and compact_done() included.
+        -> (actions [T, N(, act_dim)] int64 / float32, obs [T, N, obs_dim] f32, reward [T, N] f32, done [T, N] u8).
+        out: (obs, reward, done) as rollout's."""
+        T = int(T)
+        if T < 1:
+            raise ValueError(f"n_steps={T} must be >= 1")
+        from .policy import MLPPolicy
+
+        if not isinstance(policy, MLPPolicy):
+            raise TypeError("rollout_policy takes an emei_amd.MLPPolicy (any other callable acts through the per-step loop: step())")
+        policy.bind(self)
+        obs, rew, done = self._check_outputs(out, (T,)) if out is not None else self.alloc_outputs(T)
+        dtype = torch.int64 if self.act_dim == 0 else torch.float32
+        act = torch.empty((T, self.n_envs) + self._act_tail, dtype=dtype, device=self.device)
+        ps = policy.struct()
+        L.check(L.lib().emei_rollout_policy(self._h, T, C.byref(ps), _ptr(act), _ACT_DTYPES[dtype], _ptr(obs), _ptr(rew), _ptr(done),
+                                            L.FLAG_AUTO_RESET if auto_reset else 0, _stream()))
+        return act, obs, rew, done
 
     @_on_device
     def evaluate_sequences(self, actions, discount=1.0, start_state=None, final_obs=False):

@@ -1,0 +1,119 @@
+"""Feedback policies the engine evaluates INSIDE a rollout launch (emei_rollout_policy, include/emei_hip.h).
+
+MLPPolicy holds the weights of a small network — one ReLU hidden layer, or affine — as contiguous float32 device tensors.
+Engine.rollout_policy hands their pointers to the kernel; calling the object, `policy(obs)`, evaluates the same normative
+arithmetic (float64 sums in ascending index order) with torch operations, so the one object also serves the per-step path
+(`datasets.collect(env, n, policy=lambda o: policy(o))`) and gives the same actions there.
+"""
+import ctypes as C
+
+import torch
+
+from . import _lib as L
+from .engine import _CTRL_RANGE
+
+_OUT_MODES = {"clip": L.POLICY_OUT_CLIP, "tanh": L.POLICY_OUT_TANH}
+
+
+class MLPPolicy:
+    """a = pi(obs): h = relu(w1 @ obs + b1) (or h = obs without a hidden layer), y = w2 @ h + b2, then
+    out="clip": a = clip(float32(y), lo, hi);  out="tanh": a = mid + half * tanh(y) onto [lo, hi], the env's ctrlrange;
+    discrete envs (one output): a = 1 if y >= 0 else 0, whatever `out` says.
+    w2 [n_out, hidden] (or [n_out, obs_dim] without a hidden layer), b2 [n_out], w1 [hidden, obs_dim], b1 [hidden]: anything
+    torch.as_tensor takes; kept as contiguous float32 tensors and moved to the engine's device on first use there."""
+
+    def __init__(self, w2, b2, w1=None, b1=None, out="clip"):
+        if out not in _OUT_MODES:
+            raise ValueError(f"out {out!r}: 'clip' or 'tanh'")
+        if (w1 is None) != (b1 is None):
+            raise ValueError("w1 and b1 come together (both None: an affine policy)")
+        f = lambda t: None if t is None else torch.as_tensor(t).detach().to(torch.float32).contiguous()
+        self.w1, self.b1, self.w2, self.b2 = f(w1), f(b1), f(w2), f(b2)
+        self.out = out
+        if self.w2.dim() != 2 or self.b2.dim() != 1 or self.b2.shape[0] != self.w2.shape[0]:
+            raise ValueError(f"w2 {tuple(self.w2.shape)} must be [n_out, n_in] and b2 {tuple(self.b2.shape)} [n_out]")
+        self.hidden = 0
+        if self.w1 is not None:
+            if self.w1.dim() != 2 or self.b1.dim() != 1 or self.b1.shape[0] != self.w1.shape[0] or self.w2.shape[1] != self.w1.shape[0]:
+                raise ValueError(f"w1 {tuple(self.w1.shape)} must be [hidden, obs_dim], b1 {tuple(self.b1.shape)} [hidden] and "
+                                 f"w2 {tuple(self.w2.shape)} [n_out, hidden]")
+            self.hidden = int(self.w1.shape[0])
+            if not 1 <= self.hidden <= L.POLICY_MAX_HIDDEN:
+                raise ValueError(f"hidden={self.hidden} is outside [1, {L.POLICY_MAX_HIDDEN}]")
+        self.obs_dim = int(self.w1.shape[1] if self.w1 is not None else self.w2.shape[1])
+        self.n_out = int(self.w2.shape[0])
+        self.lo = self.hi = None  # the ctrlrange of the env the policy was last bound to (what __call__ maps onto)
+        self.discrete = None
+
+    @classmethod
+    def from_module(cls, seq):
+        """torch.nn.Sequential(Linear[, ReLU, Linear][, Tanh]) -> MLPPolicy; a trailing Tanh selects out="tanh"."""
+        mods = list(seq)
+        out = "clip"
+        if mods and isinstance(mods[-1], torch.nn.Tanh):
+            out, mods = "tanh", mods[:-1]
+        kinds = [type(m) for m in mods]
+        lin, relu = torch.nn.Linear, torch.nn.ReLU
+        if kinds == [lin]:
+            first, last = None, mods[0]
+        elif kinds == [lin, relu, lin]:
+            first, last = mods[0], mods[2]
+        else:
+            raise ValueError("from_module takes Linear[, ReLU, Linear][, Tanh]; got " + ", ".join(k.__name__ for k in map(type, seq)))
+        for m in (first, last):
+            if m is not None and m.bias is None:
+                raise ValueError("from_module: every Linear needs a bias")
+        return cls(last.weight, last.bias, None if first is None else first.weight, None if first is None else first.bias, out=out)
+
+    def to(self, device):
+        for k in ("w1", "b1", "w2", "b2"):
+            t = getattr(self, k)
+            if t is not None and t.device != torch.device(device):
+                setattr(self, k, t.to(device).contiguous())
+        return self
+
+    def bind(self, engine):
+        """check the shapes against `engine`'s env, move the weights to its device, remember its ctrlrange"""
+        n_out = engine.act_dim if engine.act_dim > 0 else 1
+        if self.obs_dim != engine.obs_dim or self.n_out != n_out:
+            raise ValueError(f"policy maps {self.obs_dim} -> {self.n_out} but {engine.env_name} has obs_dim={engine.obs_dim} and "
+                             f"{n_out} policy output(s)")
+        self.to(engine.device)
+        self.discrete = engine.act_dim == 0
+        self.lo, self.hi = _CTRL_RANGE.get(engine.env_name, (-1.0, 1.0))  # the ctrlrange of the kernels' model constants
+        return self
+
+    def struct(self):
+        """struct emei_policy over the weights (which the caller keeps alive for the launch)"""
+        p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        return L.EmeiPolicy(C.sizeof(L.EmeiPolicy), self.hidden, _OUT_MODES[self.out], 0, p(self.w1), p(self.b1), p(self.w2), p(self.b2))
+
+    def __call__(self, obs):
+        """obs [N, obs_dim] -> actions [N] int64 (discrete), [N] float32 (one control) or [N, act_dim] float32: the normative
+        arithmetic of emei_rollout_policy in torch float64 (products of float32 values are exact there; the sums run in ascending
+        index order, one elementwise operation per term).  Needs bind(engine) first (Engine.rollout_policy does it)."""
+        if self.discrete is None:
+            raise ValueError("MLPPolicy: bind(engine) first (which env's action space is this for?)")
+        x = torch.as_tensor(obs, device=self.w2.device).to(torch.float32).to(torch.float64)
+        if self.hidden:
+            z = self.b1.to(torch.float64)[None, :].repeat(x.shape[0], 1)
+            w1 = self.w1.to(torch.float64)
+            for k in range(self.obs_dim):
+                z = z + w1[None, :, k] * x[:, k:k + 1]
+            h = z.to(torch.float32)
+            h = torch.where(h > 0, h, torch.zeros_like(h)).to(torch.float64)
+        else:
+            h = x
+        y = self.b2.to(torch.float64)[None, :].repeat(x.shape[0], 1)
+        w2 = self.w2.to(torch.float64)
+        for j in range(h.shape[1]):
+            y = y + w2[None, :, j] * h[:, j:j + 1]
+        if self.discrete:
+            return (y[:, 0] >= 0).to(torch.int64)
+        if self.out == "tanh":
+            a = (0.5 * (self.hi + self.lo) + 0.5 * (self.hi - self.lo) * torch.tanh(y)).to(torch.float32)
+        else:
+            a = y.to(torch.float32)
+            a = torch.where(a >= self.lo, a, torch.full_like(a, self.lo))  # fmaxf(a, lo): NaN -> lo
+            a = torch.where(a <= self.hi, a, torch.full_like(a, self.hi))
+        return a[:, 0].contiguous() if self.n_out == 1 else a.contiguous()

@@ -432,7 +432,7 @@ class ShardedRollout:
         """the rollout kernel the last launch selected (emei_last_rollout_kernel)"""
         from . import _lib as L
 
-        return L.KERNEL_NAMES[self.engine.last_kernel()]
+        return L.kernel_name(self.engine.last_kernel())
 
     @property
     def action_bytes(self):

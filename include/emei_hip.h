@@ -47,7 +47,10 @@ extern "C" {
  *    emei_mpc_cem_workspace_bytes, emei_mpc_cem (the same control episodes with the cross-entropy method as the planner: `iterations`
  *    refits of emei_plan_cem per control step, the per-entry sigma kept on the device), EMEI_KERNEL_PEND_MPC_CEM;
  *    emei_mpc_mppi and emei_mpc_cem also serve the four InvertedDoublePendulum envs (any integrator, either precision, no
- *    observation noise) on kernels of the body family, EMEI_KERNEL_BODY_MPC_MPPI / EMEI_KERNEL_BODY_MPC_CEM. */
+ *    observation noise) on kernels of the body family, EMEI_KERNEL_BODY_MPC_MPPI / EMEI_KERNEL_BODY_MPC_CEM;
+ *    emei_rollout_policy with struct emei_policy (closed-loop rollouts under a small feedback policy a_t = pi(obs_t), one ReLU hidden
+ *    layer or affine, evaluated per lane inside the rollout launch: every env on its family's kernel), EMEI_KERNEL_PEND_POLICY /
+ *    EMEI_KERNEL_BODY_POLICY / EMEI_KERNEL_BODY_POLICY_RK4. */
 #define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
@@ -567,6 +570,60 @@ EMEI_API int emei_mpc_cem(emei_env* h, int32_t n_steps, int32_t horizon, int32_t
                           float* obs_out, float* reward_out, uint8_t* done_out, double* plan_return_out, double* elite_return_out,
                           uint32_t flags, void* stream);
 
+/* Closed-loop rollouts under a feedback policy a_t = pi(obs_t), n_steps env-steps in ONE launch: what the agent.predict loop of
+ * zoo/util.py:54-73 does with one emei_get_obs / emei_episode_init_obs, the policy's own launches and one emei_step per step.  The policy
+ * is a small network — one ReLU hidden layer, or affine — evaluated per lane inside the rollout kernel; the weights are the same for
+ * every env and are read through wave-uniform addresses (scalar loads).  They are DEVICE pointers, read during the launch and not
+ * retained; they must not overlap any output of the call.
+ *
+ * Semantics (normative).  For every env i and t = 0 .. n_steps - 1:
+ *   1. Observe.  x_0 is row i of emei_get_obs, rounded to float32.  For t > 0, x_t is the observation row of step t - 1 as
+ *      emei_rollout writes it; if that step was done under EMEI_FLAG_AUTO_RESET, x_t is instead what emei_episode_init_obs gives for
+ *      (i, the new episode).  Observation noise, where the handle has it, is in the row as the rollout emits it.
+ *   2. Policy.  All sums run in ascending index order, in float64 (a product of two float32 values is exact in float64, so fused and
+ *      unfused multiply-add give the same bits).
+ *        hidden > 0: for j ascending, z = (double)b1[j]; for k ascending, z = z + (double)w1[j,k] * (double)x[k]; h_j = (float)z;
+ *                    h_j = h_j > 0.f ? h_j : 0.f (NaN gives 0).
+ *        hidden == 0: h = x.
+ *        y_q = (double)b2[q]; for j ascending, y_q = y_q + (double)w2[q,j] * (double)h_j.
+ *        continuous envs, EMEI_POLICY_OUT_CLIP: a_q = fminf(fmaxf((float)y_q, lo), hi), [lo, hi] the ctrlrange of the candidate
+ *                    specification above (+-3 for the InvertedPendulum family, +-1 otherwise); NaN gives lo.
+ *        continuous envs, EMEI_POLICY_OUT_TANH: a_q = (float)(0.5*(hi+lo) + 0.5*(hi-lo) * tanh(y_q)) in float64, the device's float64
+ *                    tanh: this mode is NOT pinned bit for bit (within one float32 spacing at max(|lo|, |hi|) of a correctly rounded tanh).
+ *        discrete envs: a = y_0 >= 0 ? 1 : 0 (NaN gives 0); out_mode is ignored.
+ *      actions_out[t, i(, :)] in action_dtype (U8 / I32 / I64 for the discrete envs, F32 for the continuous ones),
+ *      [n_steps, n_envs(, act_dim)].
+ *   3. Step.  Exactly emei_step(a_t, flags) for env i, with emei_rollout's arithmetic: the TimeLimit counter, the EMEI_DONE_* bits,
+ *      EMEI_FLAG_AUTO_RESET with the handle's reset key and episode counter, the observation-noise counters; obs_out / reward_out /
+ *      done_out at [t, i] as emei_rollout writes them.
+ * Each of the four outputs may be NULL.  After the call the handle is as after the equivalent loop: state, step and episode counters,
+ * the done mask emei_compact_done reads.
+ * Consequences.  Replay: feeding actions_out to emei_rollout from the same start reproduces the other three outputs bit for bit.
+ * Chunking: n_steps = a + b in one call equals two calls wherever (float)emei_get_obs equals the row the last step emitted (the second
+ * call observes the state, the single call the emitted row).  Sharding: results depend on the global env index, not on the shard.
+ * Stream: the call neither allocates nor synchronises (capturable).
+ * Kernels: pend_policy_rollout_kernel for every handle emei_rollout runs on the 4-state family's kernels (the loop of the generic
+ * pend_rollout_kernel, any n, any n_steps); body_policy_rollout_kernel for every handle on the body kernels, always as a one-piece
+ * launch: the chunked work-queue launch (emei_config.rollout_chunk_steps) is NOT used by this call.
+ * EMEI_ERR_INVALID before any HIP call, each message naming the argument, in this order: n_steps < 1; NULL policy; struct_size wrong;
+ * hidden < 0 or > EMEI_POLICY_MAX_HIDDEN; unknown out_mode; reserved != 0; a NULL handle; NULL w2 or b2; hidden > 0 with NULL w1 or
+ * b1; a wrong action_dtype; unknown flags.  EMEI_ERR_STATE without a state.  EMEI_ERR_UNSUPPORTED for a handle with observation peers
+ * set (emei_set_obs_peers). */
+enum emei_policy_out { EMEI_POLICY_OUT_CLIP = 0, EMEI_POLICY_OUT_TANH = 1 };
+#define EMEI_POLICY_MAX_HIDDEN 1024
+typedef struct emei_policy {
+    uint32_t struct_size;   /* = sizeof(emei_policy) */
+    int32_t hidden;         /* width of the one hidden layer (ReLU); 0 = an affine policy */
+    int32_t out_mode;       /* enum emei_policy_out; ignored by the discrete envs */
+    int32_t reserved;       /* must be 0 */
+    const float* w1;        /* [hidden, obs_dim] row-major; NULL when hidden == 0 */
+    const float* b1;        /* [hidden];                    NULL when hidden == 0 */
+    const float* w2;        /* [n_out, hidden], or [n_out, obs_dim] when hidden == 0 */
+    const float* b2;        /* [n_out];  n_out = act_dim, or 1 for the discrete envs */
+} emei_policy;
+EMEI_API int emei_rollout_policy(emei_env* h, int32_t n_steps, const emei_policy* policy, void* actions_out, int action_dtype,
+                                 float* obs_out, float* reward_out, uint8_t* done_out, uint32_t flags, void* stream);
+
 /* Which kernel the LAST emei_step / emei_rollout of this handle launched (enum emei_kernel_id): a debug /
  * test getter, so that a parity test can assert that the path it checked is the path bench.py times. */
 enum emei_kernel_id {
@@ -584,7 +641,10 @@ enum emei_kernel_id {
     EMEI_KERNEL_PEND_MPC_MPPI = 11,          /* pend_mpc_mppi_kernel<Env>: emei_mpc_mppi (it steps the handle, so it reports here) */
     EMEI_KERNEL_PEND_MPC_CEM = 12,           /* pend_mpc_cem_kernel<Env>: emei_mpc_cem (likewise) */
     EMEI_KERNEL_BODY_MPC_MPPI = 13,          /* body_mpc_mppi_kernel<Body, RK4>: emei_mpc_mppi on an InvertedDoublePendulum handle */
-    EMEI_KERNEL_BODY_MPC_CEM = 14            /* body_mpc_cem_kernel<Body, RK4>: emei_mpc_cem on an InvertedDoublePendulum handle */
+    EMEI_KERNEL_BODY_MPC_CEM = 14,           /* body_mpc_cem_kernel<Body, RK4>: emei_mpc_cem on an InvertedDoublePendulum handle */
+    EMEI_KERNEL_PEND_POLICY = 15,            /* pend_policy_rollout_kernel<Env>: emei_rollout_policy (it steps the handle, so it reports here) */
+    EMEI_KERNEL_BODY_POLICY = 16,            /* body_policy_rollout_kernel<Body, false>: emei_rollout_policy on the body kernels */
+    EMEI_KERNEL_BODY_POLICY_RK4 = 17         /* body_policy_rollout_kernel<Body, true> */
 };
 EMEI_API int emei_last_rollout_kernel(emei_env* h);
 

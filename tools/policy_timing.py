@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""Closed-loop policy rollouts, two ways, in the same run: Engine.rollout_policy (emei_rollout_policy: the policy is evaluated per lane
+inside the rollout kernel, T steps with auto-reset in ONE launch) against the loop it replaces, the per-step route of
+datasets.collect(policy=callable) — per step the callable (the SAME MLPPolicy object, evaluated in torch float64), one emei_step
+launch, the host round trip `bool(done.any())` and, when an env finished, an episode_init_obs launch.  The loop is the comparator; the
+fused call is never its own yardstick.  Both start every timed episode from the same state (restored outside the timed window) and
+compute the same bits (tests/test_gpu_policy.py).
+Method: the step count of a shape is doubled from its starting value until one fused episode exceeds 12 ms (so that every timed
+window is above 10 ms); then, after `--warmup` untimed episodes of each route, `--repeats` rounds; every round times ONE episode of
+each route with device events around it (the loop's host overhead is inside its window: the events bracket everything its T
+iterations enqueue), the two routes alternating inside the round so that drift hits both alike.  Reported per shape: the median over
+the rounds and the spread (min, max) of either route, and the ratio of the medians.
+A third figure per shape, `replay_ms`: emei_rollout on the actions the fused call took, from the same start (the same trajectory, the
+actions loaded instead of computed; at aligned shapes on the staged kernels) — what the in-kernel policy costs on top of the env step.
+Shapes: CartPoleSwingUp N = 256 and N = 65 536, HalfCheetahRunning N = 256 and N = 16 384; one hidden layer of 64 units.
+One JSON line per shape.  Run on the GPU box:
+    python tools/policy_timing.py [--warmup 2] [--repeats 7] [--only INDEX]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from emei_amd.engine import Engine  # noqa: E402
+from emei_amd.policy import MLPPolicy  # noqa: E402
+
+# (env, N, starting T, engine kwargs)
+SHAPES = [
+    ("CartPoleSwingUp", 256, 1024, {}),
+    ("CartPoleSwingUp", 65536, 256, {}),
+    ("HalfCheetahRunning", 256, 128, dict(freq_rate=4, real_time_scale=0.002, max_episode_steps=1000, init_noise=0.1)),
+    ("HalfCheetahRunning", 16384, 128, dict(freq_rate=4, real_time_scale=0.002, max_episode_steps=1000, init_noise=0.1)),
+]
+HIDDEN, MIN_WINDOW_MS, MAX_T = 64, 12.0, 8192
+
+
+def make_policy(eng):
+    g = torch.Generator().manual_seed(1)
+    n_out = max(eng.act_dim, 1)
+    r = lambda *s: torch.randn(*s, generator=g) / s[-1] ** 0.5
+    return MLPPolicy(r(n_out, HIDDEN), r(n_out), r(HIDDEN, eng.obs_dim), r(HIDDEN)).bind(eng)
+
+
+def loop_episode(eng, T, policy, outs):
+    """datasets.collect's per-step route, statement for statement, at the Engine level"""
+    next_obs, rew, done = outs
+    cur = eng.get_obs().float()
+    _, epi = eng.get_counters()
+    for t in range(T):
+        a = policy(cur)
+        a = (a.to(torch.float32) if eng.act_dim else a.to(torch.int64)).contiguous()
+        eng.step(a, auto_reset=True, out=(next_obs[t], rew[t], done[t]))
+        cur = next_obs[t]
+        d = done[t] != 0
+        if bool(d.any()):
+            epi = epi + d.to(torch.int64)
+            idx = torch.nonzero(d).reshape(-1)
+            cur = cur.clone()
+            cur[idx] = eng.episode_init_obs(idx, epi[idx])
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--only", type=int, default=None, help="index of the one shape to run")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("policy_timing.py needs a GPU")
+    for idx, (name, N, T, kw) in enumerate(SHAPES):
+        if args.only is not None and args.only != idx:
+            continue
+        eng = Engine(name, N, **kw)
+        eng.reset(seed=0)
+        state0 = eng.get_state().clone()
+        policy = make_policy(eng)
+
+        def restore():
+            eng.reset(seed=0)
+            eng.set_state(state0)
+            torch.cuda.synchronize()
+
+        def timed(fn):
+            restore()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1)
+
+        outs = eng.alloc_outputs(T)
+        fused = lambda: eng.rollout_policy(T, policy, auto_reset=True, out=outs)
+        loop = lambda: loop_episode(eng, T, policy, outs)
+        replay = lambda: eng.rollout(actions, auto_reset=True, out=outs)
+        timed(fused)  # code objects loaded
+        while timed(fused) < MIN_WINDOW_MS and 2 * T <= MAX_T:
+            T *= 2
+            outs = eng.alloc_outputs(T)
+        kernel = eng.last_kernel()  # of the fused route (_lib.kernel_name)
+        restore()
+        actions = eng.rollout_policy(T, policy, auto_reset=True, out=outs)[0]
+        for _ in range(args.warmup):
+            timed(fused), timed(loop), timed(replay)
+        ms = {"fused": [], "loop": [], "replay": []}
+        for _ in range(args.repeats):
+            ms["fused"].append(timed(fused))
+            ms["loop"].append(timed(loop))
+            ms["replay"].append(timed(replay))
+        replay_kernel = eng.last_kernel()
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        print(json.dumps({
+            "env": name, "n_envs": N, "hidden": HIDDEN, "n_steps": T, "repeats": args.repeats,
+            "fused_ms": round(med["fused"], 4), "fused_ms_min_max": [round(min(ms["fused"]), 4), round(max(ms["fused"]), 4)],
+            "loop_ms": round(med["loop"], 4), "loop_ms_min_max": [round(min(ms["loop"]), 4), round(max(ms["loop"]), 4)],
+            "loop_over_fused": round(med["loop"] / med["fused"], 3),
+            "replay_ms": round(med["replay"], 4), "replay_ms_min_max": [round(min(ms["replay"]), 4), round(max(ms["replay"]), 4)],
+            "replay_kernel": replay_kernel,
+            "fused_us_per_step": round(1e3 * med["fused"] / T, 3), "loop_us_per_step": round(1e3 * med["loop"] / T, 3),
+            "kernel": kernel,
+        }), flush=True)
+        eng.close()
+
+
+if __name__ == "__main__":
+    main()
