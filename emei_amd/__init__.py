@@ -27,9 +27,9 @@ from .envs import (  # noqa: F401
 )
 
 
-def __getattr__(name):  # MLPPolicy needs torch: imported on first use, like the engine
-    if name == "MLPPolicy":
-        from .policy import MLPPolicy
+def __getattr__(name):  # the policy classes need torch: imported on first use, like the engine
+    if name in ("MLPPolicy", "PolicyPopulation"):
+        from . import policy
 
-        return MLPPolicy
+        return getattr(policy, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -166,6 +166,7 @@ SYMBOLS = {
     "emei_mpc_cem": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _u64, _vp, _dbl, _dbl, _dbl, C.c_float, C.c_float, C.c_float, _vp, _vp,
                                C.c_int, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "emei_rollout_policy": (C.c_int, [_vp, _i32, C.POINTER(EmeiPolicy), _vp, C.c_int, _vp, _vp, _vp, _u32, _vp]),
+    "emei_evaluate_policies": (C.c_int, [_vp, _i32, _i32, C.POINTER(EmeiPolicy), _dbl, _vp, _vp, _vp, _vp, _vp]),
     "emei_compact_done": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emei_get_counters": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emei_episode_init_obs": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),

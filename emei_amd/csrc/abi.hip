@@ -710,9 +710,10 @@ extern "C" EMEI_API int emei_step(emei_env* h, const void* actions, int action_d
 // ---------------------------------------------------------------------------------------------
 // The planner entry points refuse in one order: the scalars (without a handle and before any HIP call), the handle, what needs the
 // handle, the call's own pointers, the device, the state.  The refusals more than one of them makes:
-static int check_plan_scalars(const char* fn, int32_t horizon, int32_t n_candidates, double discount) {
+// (`count`: what the call names its lanes-per-env argument)
+static int check_plan_scalars(const char* fn, int32_t horizon, int32_t n_candidates, double discount, const char* count = "n_candidates") {
     if (horizon < 1) return fail(EMEI_ERR_INVALID, "%s: horizon=%d < 1", fn, horizon);
-    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "%s: n_candidates=%d < 1", fn, n_candidates);
+    if (n_candidates < 1) return fail(EMEI_ERR_INVALID, "%s: %s=%d < 1", fn, count, n_candidates);
     if (!(discount > 0.0 && discount <= 1.0)) return fail(EMEI_ERR_INVALID, "%s: discount=%g is outside (0, 1]", fn, discount);
     return EMEI_OK;
 }
@@ -1105,24 +1106,36 @@ extern "C" EMEI_API int emei_mpc_cem(emei_env* h, int32_t n_steps, int32_t horiz
 }
 
 // ---------------------------------------------------------------------------------------------
+// What emei_rollout_policy and emei_evaluate_policies refuse alike about their struct emei_policy argument `arg`: the struct's own
+// fields before the handle is looked at, the weight pointers after it.
+static int check_policy_struct(const char* fn, const char* arg, const emei_policy* policy) {
+    if (!policy) return fail(EMEI_ERR_INVALID, "%s: null %s", fn, arg);
+    if (policy->struct_size != sizeof(emei_policy))
+        return fail(EMEI_ERR_INVALID, "%s: %s.struct_size=%u != sizeof(emei_policy)=%zu", fn, arg, policy->struct_size, sizeof(emei_policy));
+    if (policy->hidden < 0 || policy->hidden > EMEI_POLICY_MAX_HIDDEN)
+        return fail(EMEI_ERR_INVALID, "%s: %s.hidden=%d is outside [0, EMEI_POLICY_MAX_HIDDEN=%d]", fn, arg, policy->hidden, EMEI_POLICY_MAX_HIDDEN);
+    if (policy->out_mode != EMEI_POLICY_OUT_CLIP && policy->out_mode != EMEI_POLICY_OUT_TANH)
+        return fail(EMEI_ERR_INVALID, "%s: unknown %s.out_mode=%d", fn, arg, policy->out_mode);
+    if (policy->reserved != 0) return fail(EMEI_ERR_INVALID, "%s: %s.reserved=%d must be 0", fn, arg, policy->reserved);
+    return EMEI_OK;
+}
+static int check_policy_weights(const char* fn, const char* arg, const emei_policy* policy) {
+    if (!policy->w2 || !policy->b2) return fail(EMEI_ERR_INVALID, "%s: null %s.%s", fn, arg, !policy->w2 ? "w2" : "b2");
+    if (policy->hidden > 0 && (!policy->w1 || !policy->b1))
+        return fail(EMEI_ERR_INVALID, "%s: null %s.%s with hidden=%d", fn, arg, !policy->w1 ? "w1" : "b1", policy->hidden);
+    return EMEI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // emei_rollout_policy: n_steps of "observe, evaluate the policy, emei_step" in one launch of the family's policy rollout kernel
 // (pendulum_kernels.h:pend_policy_rollout_kernel, body_kernels.h:body_policy_rollout_kernel); the kernel leaves the done mask itself.
 extern "C" EMEI_API int emei_rollout_policy(emei_env* h, int32_t n_steps, const emei_policy* policy, void* actions_out, int action_dtype,
                                             float* obs_out, float* reward_out, uint8_t* done_out, uint32_t flags, void* stream) {
     const char* fn = "emei_rollout_policy";
     if (n_steps < 1) return fail(EMEI_ERR_INVALID, "%s: n_steps=%d < 1", fn, n_steps);
-    if (!policy) return fail(EMEI_ERR_INVALID, "%s: null policy", fn);
-    if (policy->struct_size != sizeof(emei_policy))
-        return fail(EMEI_ERR_INVALID, "%s: policy.struct_size=%u != sizeof(emei_policy)=%zu", fn, policy->struct_size, sizeof(emei_policy));
-    if (policy->hidden < 0 || policy->hidden > EMEI_POLICY_MAX_HIDDEN)
-        return fail(EMEI_ERR_INVALID, "%s: policy.hidden=%d is outside [0, EMEI_POLICY_MAX_HIDDEN=%d]", fn, policy->hidden, EMEI_POLICY_MAX_HIDDEN);
-    if (policy->out_mode != EMEI_POLICY_OUT_CLIP && policy->out_mode != EMEI_POLICY_OUT_TANH)
-        return fail(EMEI_ERR_INVALID, "%s: unknown policy.out_mode=%d", fn, policy->out_mode);
-    if (policy->reserved != 0) return fail(EMEI_ERR_INVALID, "%s: policy.reserved=%d must be 0", fn, policy->reserved);
+    if (int rc = check_policy_struct(fn, "policy", policy)) return rc;
     if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
-    if (!policy->w2 || !policy->b2) return fail(EMEI_ERR_INVALID, "%s: null policy.%s", fn, !policy->w2 ? "w2" : "b2");
-    if (policy->hidden > 0 && (!policy->w1 || !policy->b1))
-        return fail(EMEI_ERR_INVALID, "%s: null policy.%s with hidden=%d", fn, !policy->w1 ? "w1" : "b1", policy->hidden);
+    if (int rc = check_policy_weights(fn, "policy", policy)) return rc;
     if (action_dtype < EMEI_ACT_U8 || action_dtype > EMEI_ACT_F32 || (h->act_dim > 0) != (action_dtype == EMEI_ACT_F32))
         return fail(EMEI_ERR_INVALID, "%s: action_dtype=%d: actions_out is uint8 / int32 / int64 for the discrete envs, float32 for the "
                                       "continuous ones", fn, action_dtype);
@@ -1154,6 +1167,48 @@ extern "C" EMEI_API int emei_rollout_policy(emei_env* h, int32_t n_steps, const 
         L.flags = flags;
         L.policy = pa;
         L.selected = &h->last_kernel;
+        rc = body_launch(L);
+    }
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+}
+
+// ---------------------------------------------------------------------------------------------
+// emei_evaluate_policies: emei_evaluate_sequences' query with the candidates replaced by a population of feedback policies, one
+// launch of the family's policy evaluation kernel (pendulum_kernels.h:pend_policy_eval_kernel, body_kernels.h:body_policy_eval_kernel)
+// through the plan-launch descriptor; nothing of the handle is written (h->last_kernel included).
+extern "C" EMEI_API int emei_evaluate_policies(emei_env* h, int32_t horizon, int32_t n_policies, const emei_policy* stacked, double discount,
+                                               const double* start_state, double* return_out, int32_t* length_out, float* final_obs_out,
+                                               void* stream) {
+    const char* fn = "emei_evaluate_policies";
+    if (int rc = check_plan_scalars(fn, horizon, n_policies, discount, "n_policies")) return rc;
+    if (int rc = check_policy_struct(fn, "stacked", stacked)) return rc;
+    if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = check_policy_weights(fn, "stacked", stacked)) return rc;
+    if (!return_out) return fail(EMEI_ERR_INVALID, "%s: null return_out", fn);
+    // one lane per (policy, env) pair with 32-bit indices, one grid dimension of ceil(n_envs / 256) blocks per policy
+    const int64_t np = h->cfg.n_envs * (int64_t)n_policies;
+    if (np > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs * n_policies = %lld exceeds 2^31 - 1", fn, (long long)np);
+    const int64_t blocks = (h->cfg.n_envs + kBlock - 1) / kBlock * (int64_t)n_policies;
+    if (blocks > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_policies=%d needs %lld blocks, more than 2^31 - 1", fn, n_policies, (long long)blocks);
+    EMEI_ON_DEVICE(h, fn);
+    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    PolicyArgs pa{};
+    pa.w1 = stacked->w1, pa.b1 = stacked->b1, pa.w2 = stacked->w2, pa.b2 = stacked->b2;
+    pa.hidden = stacked->hidden, pa.out_mode = stacked->out_mode;
+    ctrl_range(h->cfg.env_id, pa.lo, pa.hi);
+    PlanLaunch p;
+    p.mode = PLAN_GIVEN, p.start_rows = start_state, p.n_candidates = n_policies, p.discount = discount;
+    p.return_out = return_out, p.length_out = length_out;
+    int rc;
+    if (!steps_as_body(h->cfg)) {
+        PendLaunch L = pend_base(h, stream);
+        L.op = PEND_OP_POLICY_EVAL, L.plan = p, L.policy = pa;
+        L.n_steps = horizon, L.obs_out = final_obs_out;
+        rc = pend_launch(L);
+    } else {
+        BodyLaunch L = body_base(h, stream);
+        L.op = BODY_OP_POLICY_EVAL, L.plan = p, L.policy = pa;
+        L.n_steps = horizon, L.obs_out = final_obs_out;
         rc = body_launch(L);
     }
     return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));

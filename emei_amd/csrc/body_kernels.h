@@ -168,7 +168,8 @@ enum BodyOp { BODY_OP_ROLLOUT = 0, BODY_OP_RESET, BODY_OP_GET_OBS, BODY_OP_INIT_
               BODY_OP_PLAN /* emei_evaluate_sequences: body_plan_kernel */,
               BODY_OP_MPC_MPPI /* emei_mpc_mppi: body_mpc_mppi_kernel (Body::kFusedMpc) */,
               BODY_OP_MPC_CEM /* emei_mpc_cem: body_mpc_cem_kernel (Body::kFusedMpc) */,
-              BODY_OP_POLICY /* emei_rollout_policy: body_policy_rollout_kernel */ };
+              BODY_OP_POLICY /* emei_rollout_policy: body_policy_rollout_kernel */,
+              BODY_OP_POLICY_EVAL /* emei_evaluate_policies: body_policy_eval_kernel */ };
 
 // What BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM take beyond the base descriptor: n_steps control steps of the planner with plan.n_candidates
 // candidates over `horizon` steps under plan.discount; plan.cand carries the call's seed, sigma and the ctrlrange (its nominal is
@@ -227,6 +228,8 @@ struct BodyLaunch {
     PlanLaunch plan;  // BODY_OP_PLAN; n_steps = the horizon, obs_out = final_obs [n * K, NO] or null
     MpcLaunch mpc;    // BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM
     PolicyArgs policy = {};  // BODY_OP_POLICY: BODY_OP_ROLLOUT's fields without `actions`; weights, ctrlrange and actions_out (float32)
+                             // BODY_OP_POLICY_EVAL: the STACKED weights (member p at p * its size), with `plan` as PLAN_GIVEN takes it:
+                             // n_candidates = the number of policies, return_out / length_out [P, n]; obs_out = final_obs [P, n, NO] or null
 };
 int body_launch(const BodyLaunch& L);  // body_dispatch.hip
 
@@ -945,6 +948,93 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
+// emei_evaluate_policies (the normative text: include/emei_hip.h) for the bodies: body_plan_kernel's non-DRAWN loop with the action
+// load replaced by the lane's own evaluation of ITS policy (emei_device.h:policy_eval, unchanged) on the float32 row it holds; as
+// in body_policy_rollout_kernel the action of step t + 1 is computed at the end of step t, so NA floats cross the step, not NO.
+// One lane per (policy, env) pair and a block never mixes policies: with env_blocks = ceil(n_envs / kBlock), block b serves policy
+// p = b / env_blocks and env block b % env_blocks (env blocks fastest: neighbouring blocks read the same weights).  p comes from
+// blockIdx alone, so the offset weight bases stay wave-uniform and the weights stay scalar loads.  Wave w of a policy's blocks
+// holds envs 64 w .. 64 w + 63, as in the policy rollout: the cheetah's constraint-slot lending sees that rollout's wave-mates.
+// Padding lanes are loaded from env 0's row and parked with a select, with zero controls, as body_plan_kernel's.  Nothing is read
+// or written per step; a lane's results leave at its last counted step, at [p * n_envs + i].
+template <class Body, bool RK4>
+__global__ void __launch_bounds__(kBlock)
+    body_policy_eval_kernel(const typename Body::real* state, const double* start_rows, int64_t n_envs, uint32_t env_blocks,
+                            int32_t horizon, double discount, int freq_rate, int semi, typename Body::Model m,
+                            const SinCosEntry* trig_tab, unsigned long long* cap_hits, const PolicyArgs stacked, double* ret_out,
+                            int32_t* len_out, float* final_obs) {
+    using R = typename Body::real;
+    constexpr int NS = Body::NS, NO = Body::NO, NA = Body::NA;
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table(trig_s, trig_tab);  // every thread reaches the barrier
+    TrigCtx trig;
+    trig.tab = trig_s;
+    __shared__ R scratch_s[(Body::kScratchPerLane > 0 ? Body::kScratchPerLane : 1) * (Body::kScratchPerLane > 0 ? kBlock : 1)];
+    if constexpr (Body::kScratchPerLane > 0) trig.scratch = scratch_s;
+    trig.scratch_stride = kBlock;
+    trig.cap_hits = cap_hits;
+    const uint32_t pi = blockIdx.x / env_blocks;  // the block's policy: scalar
+    const int64_t i_raw = (int64_t)(blockIdx.x - pi * env_blocks) * kBlock + threadIdx.x;
+    const bool active = i_raw < n_envs;
+    const int64_t i = active ? i_raw : 0;  // no divergent branch around the loads: see body_plan_kernel
+    const int64_t j = (int64_t)pi * n_envs + i;
+    PolicyArgs pol = stacked;  // member pi of the population: n_out = NA, fan-in of the output layer = hidden, or NO without one
+    pol.w1 += (int64_t)pi * pol.hidden * NO, pol.b1 += (int64_t)pi * pol.hidden;
+    pol.w2 += (int64_t)pi * NA * (pol.hidden > 0 ? pol.hidden : NO), pol.b2 += (int64_t)pi * NA;
+
+    R s[NS], parked[NS];
+    if (start_rows) {  // wave-uniform; the caller's float64 rows are narrowed as emei_set_state narrows them (util_kernels.hip)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = (R)start_rows[i * NS + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = state[(int64_t)k * n_envs + i];
+    }
+    Body::park(parked);  // as body_rollout_kernel's padding lanes
+#pragma unroll
+    for (int k = 0; k < NS; ++k) s[k] = active ? s[k] : parked[k];
+    float act[NA];
+    {  // x_0: the float32 observation of the state, as emei_get_obs rounds it
+        double od[NO];
+        Body::obs_of(s, od, m);
+        float x[NO];
+#pragma unroll
+        for (int k = 0; k < NO; ++k) x[k] = (float)od[k];
+        policy_eval<NO, NA, false>(pol, x, act);
+    }
+    double ret = 0.0, g = 1.0;
+    bool live = active;
+    for (int t = 0; t < horizon; ++t) {
+        R ctrl[NA];  // padding lanes: zero, as the rollout's staging gives them
+#pragma unroll
+        for (int k = 0; k < NA; ++k) ctrl[k] = active ? (R)act[k] : R(0);
+        R pre[NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) pre[k] = s[k];
+        typename Body::Warm warm{};
+        for (int k = 0; k < freq_rate; ++k) body_substep<Body, RK4>(s, ctrl, m, semi != 0, trig, warm);
+        float o[NO];
+        R rew;
+        bool term;
+        Body::outputs(s, pre, ctrl, m, freq_rate, o, rew, term, trig);
+        if (live) {
+            ret = ret + g * (double)(float)rew;
+            g = g * discount;
+            if (term || t == horizon - 1) {  // the lane's last counted step
+                live = false;
+                ret_out[j] = ret;
+                if (len_out) len_out[j] = t + 1;
+                if (final_obs) {
+#pragma unroll
+                    for (int k = 0; k < NO; ++k) final_obs[j * NO + k] = o[k];
+                }
+            }
+        }
+        if (__ballot(live) == 0ull) break;  // wave-uniform
+        policy_eval<NO, NA, false>(pol, o, act);  // wave-uniform: the next step's action
+    }
+}
+
 // the one launch of body_plan_kernel: DRAWN kernels read no actions and write no lengths or final observations, and only KEEP
 // gives them a return_out; one lane per candidate, n * n_candidates < 2^31 (checked in abi.hip)
 template <class Body, bool RK4, bool DRAWN, bool KEEP, class Spec>
@@ -1034,6 +1124,20 @@ static int launch_body(const BodyLaunch& L) {
             else
                 hipLaunchKernelGGL((body_policy_rollout_kernel<Body, false>), rgrid, dim3(rollout_block<Body>()), 0, L.stream, a, L.policy);
             if (L.selected) *L.selected = L.integrator == EMEI_INTEG_RK4 ? EMEI_KERNEL_BODY_POLICY_RK4 : EMEI_KERNEL_BODY_POLICY;
+            break;
+        }
+        case BODY_OP_POLICY_EVAL: {  // emei_evaluate_policies: block b = (policy b / grid.x, env block b % grid.x); abi.hip bounds the grid
+            const PlanLaunch& P = L.plan;
+            const dim3 egrid(grid.x * (unsigned)P.n_candidates);
+            const int semi = (int)(L.integrator == EMEI_INTEG_SEMI_IMPLICIT);
+            if (L.integrator == EMEI_INTEG_RK4)
+                hipLaunchKernelGGL((body_policy_eval_kernel<Body, true>), egrid, dim3(kBlock), 0, L.stream, (const R*)L.state, P.start_rows,
+                                   L.n, grid.x, L.n_steps, P.discount, L.freq_rate, 0, m, (const SinCosEntry*)L.trig, L.cap_hits, L.policy,
+                                   P.return_out, P.length_out, L.obs_out);
+            else
+                hipLaunchKernelGGL((body_policy_eval_kernel<Body, false>), egrid, dim3(kBlock), 0, L.stream, (const R*)L.state, P.start_rows,
+                                   L.n, grid.x, L.n_steps, P.discount, L.freq_rate, semi, m, (const SinCosEntry*)L.trig, L.cap_hits, L.policy,
+                                   P.return_out, P.length_out, L.obs_out);
             break;
         }
         case BODY_OP_OCCUPANCY: {

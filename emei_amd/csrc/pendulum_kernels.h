@@ -756,6 +756,67 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
+// emei_evaluate_policies (the normative text: include/emei_hip.h): pend_plan_kernel's non-DRAWN loop with the action load replaced
+// by the lane's own evaluation of ITS policy on the float32 row it holds, as pend_policy_rollout_kernel evaluates the one policy.
+// One lane per (policy, env) pair and a block never mixes policies: with env_blocks = ceil(n_envs / kBlock), block b serves policy
+// p = b / env_blocks and env block b % env_blocks (env blocks fastest: neighbouring blocks read the same weights).  p comes from
+// blockIdx alone, so the offset weight bases stay wave-uniform and policy_eval (unchanged) keeps reading them as scalar loads.
+// Nothing is read or written per step; a lane's 12 B (28 with final_obs) leave at its last counted step, at [p * n_envs + i].
+template <class Env>
+__global__ void __launch_bounds__(kBlock)
+    pend_policy_eval_kernel(const typename Env::real* state, const double* start_rows, int64_t n_envs, uint32_t env_blocks,
+                            int32_t horizon, double discount, int freq_rate, typename Env::Params p, const SinCosEntry* trig,
+                            const PolicyArgs stacked, double* ret_out, int32_t* len_out, float4* final_obs) {
+    using R = typename Env::real;
+    using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table(trig_s, trig, Env::trig_rot_c(), Env::trig_rot_s());
+    const uint32_t pi = blockIdx.x / env_blocks;  // the block's policy: scalar
+    const int64_t i = (int64_t)(blockIdx.x - pi * env_blocks) * kBlock + threadIdx.x;
+    if (i >= n_envs) return;
+    const int64_t j = (int64_t)pi * n_envs + i;
+    PolicyArgs pol = stacked;  // member pi of the population: n_out = 1, fan-in of the output layer = hidden, or 4 without one
+    pol.w1 += (int64_t)pi * pol.hidden * 4, pol.b1 += (int64_t)pi * pol.hidden;
+    pol.w2 += (int64_t)pi * (pol.hidden > 0 ? pol.hidden : 4), pol.b2 += pi;
+
+    R s[4];
+    // start state: the handle's SoA, or the caller's float64 rows narrowed as emei_set_state narrows them (util_kernels.hip)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = start_rows ? (R)start_rows[i * 4 + k] : state[k * n_envs + i];
+    typename Env::Carry c;
+    trig_ctx_init(c.trig, trig_s);
+    Env::prime(s, c, p);
+    float x[4];
+    {
+        R o[4];
+        Env::obs_of(s, o);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = (float)o[k];
+    }
+    double ret = 0.0, g = 1.0;
+    bool live = true;
+    for (int t = 0; t < horizon; ++t) {
+        float av[1];
+        policy_eval<4, 1, Env::kDiscrete>(pol, x, av);
+        R o[4], rew;
+        bool term;
+        Env::step(s, c, Env::decode_t((DrawT)av[0]), p, freq_rate, o, rew, term);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = (float)o[k];
+        if (live) {
+            ret = ret + g * (double)(float)rew;
+            g = g * discount;
+            if (term || t == horizon - 1) {  // the lane's last counted step
+                live = false;
+                ret_out[j] = ret;
+                if (len_out) len_out[j] = t + 1;
+                if (final_obs) final_obs[j] = make_float4(x[0], x[1], x[2], x[3]);
+            }
+        }
+        if (__ballot(live) == 0ull) break;  // wave-uniform
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // emei_mpc_mppi: receding-horizon MPPI control episodes in ONE launch (the normative text: include/emei_hip.h).
 // The draws read the nominal from the wave's LDS slice: CandidateSpecLds (emei_device.h, shared with the body kernels' controllers).
@@ -1497,6 +1558,13 @@ static int launch_env(const PendLaunch& L) {
             hipLaunchKernelGGL(pend_policy_rollout_kernel<Env>, grid, dim3(kBlock), 0, L.stream, a, L.policy);
             if (L.selected) *L.selected = EMEI_KERNEL_PEND_POLICY;
             break;
+        case PEND_OP_POLICY_EVAL: {  // emei_evaluate_policies: block b = (policy b / grid.x, env block b % grid.x); abi.hip bounds the grid
+            const PlanLaunch& P = L.plan;
+            hipLaunchKernelGGL(pend_policy_eval_kernel<Env>, dim3(grid.x * (unsigned)P.n_candidates), dim3(kBlock), 0, L.stream,
+                               (const R*)L.state, P.start_rows, L.n, grid.x, L.n_steps, P.discount, L.freq_rate, a.p, a.trig, L.policy,
+                               P.return_out, P.length_out, (float4*)L.obs_out);
+            break;
+        }
         default: return EMEI_ERR_INVALID;
     }
     return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;

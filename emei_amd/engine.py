@@ -374,6 +374,33 @@ class Engine:
                                                 _ptr(fo), _stream()))
         return (ret, length, fo) if final_obs else (ret, length)
 
+    @_on_device
+    def evaluate_policies(self, pop, H, discount=1.0, start_state=None, final_obs=False):
+        """Score a population of P feedback policies, each on every env, from the current state (or `start_state`) in one launch, for
+        policy search (emei_evaluate_policies): pair (p, i) runs policy p closed-loop for H steps from env i's start state, as
+        rollout_policy(H, pop[p], auto_reset=False) would, and is scored as evaluate_sequences scores.  The handle's state, counters
+        and snapshot are left as they are.  pop: a policy.PolicyPopulation, or one MLPPolicy as a population of one.
+        -> (returns float64 [P, N], lengths int32 [P, N][, final_obs float32 [P, N, obs_dim]: the observation of the last counted step])"""
+        from .policy import MLPPolicy, PolicyPopulation
+
+        if isinstance(pop, MLPPolicy):
+            pop = PolicyPopulation.from_policies([pop])
+        if not isinstance(pop, PolicyPopulation):
+            raise TypeError("evaluate_policies takes an emei_amd.PolicyPopulation or an emei_amd.MLPPolicy")
+        H = int(H)
+        if H < 1:
+            raise ValueError(f"horizon={H} must be >= 1")
+        pop.bind(self)
+        P = len(pop)
+        st = self._start_rows(start_state)
+        ret = torch.empty((P, self.n_envs), dtype=torch.float64, device=self.device)
+        length = torch.empty((P, self.n_envs), dtype=torch.int32, device=self.device)
+        fo = torch.empty((P, self.n_envs, self.obs_dim), dtype=torch.float32, device=self.device) if final_obs else None
+        ps = pop.struct()
+        L.check(L.lib().emei_evaluate_policies(self._h, H, P, C.byref(ps), float(discount), _ptr(st), _ptr(ret), _ptr(length), _ptr(fo),
+                                               _stream()))
+        return (ret, length, fo) if final_obs else (ret, length)
+
     def _start_rows(self, start_state):
         """validated start_state of the plan calls: None, or contiguous float64 rows [N, state_dim] on the engine's device"""
         if start_state is None:

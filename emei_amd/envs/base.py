@@ -308,6 +308,19 @@ class HipEnv(EmeiEnv):
             return out
         return tuple(t.cpu().numpy() for t in out)
 
+    def evaluate_policies(self, policies, horizon, discount=1.0, start_state=None, final_obs=False):
+        """The query policy search asks of the true dynamics (evolution strategies, ARS, CEM over weights, population-based
+        training): a population of P feedback policies (emei_amd.PolicyPopulation, or one MLPPolicy), each run closed-loop for
+        `horizon` steps on every env from the envs' current states, or from `start_state` rows [num_envs, state_dim] float64, in one
+        launch (Engine.evaluate_policies, ABI emei_evaluate_policies).
+        -> tensors (returns float64 [P, num_envs], lengths int32 [P, num_envs][, final_obs float32 [P, num_envs, obs_dim]]), scored as
+        evaluate_action_sequences scores.  No observation noise, TimeLimit or auto-reset; the env's state is left as it is."""
+        import torch
+
+        assert self.state is not None, "Call reset before using step method."  # base_control.py:67
+        st = self._as_device(start_state, torch.float64)
+        return self.engine.evaluate_policies(policies, horizon, discount=discount, start_state=st, final_obs=final_obs)
+
     def plan_random_shooting(self, horizon, n_candidates, seed, discount=1.0, nominal=None, sigma=None, start_state=None,
                              sequence=False, length=False, dtype=None):
         """Random-shooting MPC's planning half in two launches (Engine.plan_shooting, ABI emei_plan_shooting): per env,

@@ -117,3 +117,92 @@ class MLPPolicy:
             a = torch.where(a >= self.lo, a, torch.full_like(a, self.lo))  # fmaxf(a, lo): NaN -> lo
             a = torch.where(a <= self.hi, a, torch.full_like(a, self.hi))
         return a[:, 0].contiguous() if self.n_out == 1 else a.contiguous()
+
+
+class PolicyPopulation:
+    """P policies of one architecture stacked along a leading axis, for Engine.evaluate_policies (emei_evaluate_policies):
+    w2 [P, n_out, hidden] (or [P, n_out, obs_dim] without a hidden layer), b2 [P, n_out], w1 [P, hidden, obs_dim], b1 [P, hidden];
+    `out` is shared.  Kept as contiguous float32 tensors: member p's weights sit at p * (the member's size) behind each base
+    pointer, which is the layout the kernels offset into.  len(pop) is P; pop[p] is an MLPPolicy viewing member p."""
+
+    def __init__(self, w2, b2, w1=None, b1=None, out="clip"):
+        if out not in _OUT_MODES:
+            raise ValueError(f"out {out!r}: 'clip' or 'tanh'")
+        if (w1 is None) != (b1 is None):
+            raise ValueError("w1 and b1 come together (both None: affine policies)")
+        f = lambda t: None if t is None else torch.as_tensor(t).detach().to(torch.float32).contiguous()
+        self.w1, self.b1, self.w2, self.b2 = f(w1), f(b1), f(w2), f(b2)
+        self.out = out
+        if self.w2.dim() != 3 or self.w2.shape[0] < 1:
+            raise ValueError(f"w2 {tuple(self.w2.shape)} must be [P, n_out, n_in] with P >= 1")
+        P = int(self.w2.shape[0])
+        if self.b2.dim() != 2 or tuple(self.b2.shape) != (P, self.w2.shape[1]):
+            raise ValueError(f"b2 {tuple(self.b2.shape)} must be [P, n_out] = {(P, int(self.w2.shape[1]))}")
+        self.hidden = 0
+        if self.w1 is not None:
+            if self.w1.dim() != 3 or self.w1.shape[0] != P:
+                raise ValueError(f"w1 {tuple(self.w1.shape)} must be [P, hidden, obs_dim] with P = {P}")
+            if tuple(self.b1.shape) != (P, self.w1.shape[1]):
+                raise ValueError(f"b1 {tuple(self.b1.shape)} must be [P, hidden] = {(P, int(self.w1.shape[1]))}")
+            if self.w2.shape[2] != self.w1.shape[1]:
+                raise ValueError(f"w2 {tuple(self.w2.shape)} must be [P, n_out, hidden] with hidden = {int(self.w1.shape[1])}")
+            self.hidden = int(self.w1.shape[1])
+            if not 1 <= self.hidden <= L.POLICY_MAX_HIDDEN:
+                raise ValueError(f"hidden={self.hidden} of w1 is outside [1, {L.POLICY_MAX_HIDDEN}]")
+        self.n_policies = P
+        self.obs_dim = int(self.w1.shape[2] if self.w1 is not None else self.w2.shape[2])
+        self.n_out = int(self.w2.shape[1])
+        self._engine = None
+
+    @classmethod
+    def from_policies(cls, policies):
+        """[MLPPolicy, ...] of the same shapes and the same `out` -> the population holding copies of their weights"""
+        policies = list(policies)
+        if not policies or not all(isinstance(p, MLPPolicy) for p in policies):
+            raise ValueError("from_policies takes a non-empty list of MLPPolicy")
+        first = policies[0]
+        for n, p in enumerate(policies):
+            if p.out != first.out:
+                raise ValueError(f"policy {n}: out={p.out!r} differs from policy 0's {first.out!r}")
+            for k in ("w1", "b1", "w2", "b2"):
+                a, b = getattr(first, k), getattr(p, k)
+                if (a is None) != (b is None) or (a is not None and a.shape != b.shape):
+                    raise ValueError(f"policy {n}: {k} {None if b is None else tuple(b.shape)} differs from policy 0's "
+                                     f"{None if a is None else tuple(a.shape)}")
+        dev = first.w2.device
+        st = lambda k: None if getattr(first, k) is None else torch.stack([getattr(p, k).to(dev) for p in policies])
+        return cls(st("w2"), st("b2"), st("w1"), st("b1"), out=first.out)
+
+    def __len__(self):
+        return self.n_policies
+
+    def __getitem__(self, p):
+        """member p as an MLPPolicy over VIEWS of the stacked weights (bound as the population is)"""
+        p = int(p)
+        if not -self.n_policies <= p < self.n_policies:
+            raise IndexError(f"policy {p} of a population of {self.n_policies}")
+        v = lambda t: None if t is None else t[p]
+        m = MLPPolicy(v(self.w2), v(self.b2), v(self.w1), v(self.b1), out=self.out)
+        return m.bind(self._engine) if self._engine is not None else m
+
+    def to(self, device):
+        for k in ("w1", "b1", "w2", "b2"):
+            t = getattr(self, k)
+            if t is not None and t.device != torch.device(device):
+                setattr(self, k, t.to(device).contiguous())
+        return self
+
+    def bind(self, engine):
+        """check the shapes against `engine`'s env and move the weights to its device, as MLPPolicy.bind"""
+        n_out = engine.act_dim if engine.act_dim > 0 else 1
+        if self.obs_dim != engine.obs_dim or self.n_out != n_out:
+            raise ValueError(f"the policies map {self.obs_dim} -> {self.n_out} but {engine.env_name} has obs_dim={engine.obs_dim} and "
+                             f"{n_out} policy output(s)")
+        self.to(engine.device)
+        self._engine = engine
+        return self
+
+    def struct(self):
+        """the stacked struct emei_policy over the weights (which the caller keeps alive for the launch)"""
+        p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        return L.EmeiPolicy(C.sizeof(L.EmeiPolicy), self.hidden, _OUT_MODES[self.out], 0, p(self.w1), p(self.b1), p(self.w2), p(self.b2))

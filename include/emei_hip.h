@@ -50,7 +50,9 @@ extern "C" {
  *    observation noise) on kernels of the body family, EMEI_KERNEL_BODY_MPC_MPPI / EMEI_KERNEL_BODY_MPC_CEM;
  *    emei_rollout_policy with struct emei_policy (closed-loop rollouts under a small feedback policy a_t = pi(obs_t), one ReLU hidden
  *    layer or affine, evaluated per lane inside the rollout launch: every env on its family's kernel), EMEI_KERNEL_PEND_POLICY /
- *    EMEI_KERNEL_BODY_POLICY / EMEI_KERNEL_BODY_POLICY_RK4. */
+ *    EMEI_KERNEL_BODY_POLICY / EMEI_KERNEL_BODY_POLICY_RK4;
+ *    emei_evaluate_policies (the policy-side counterpart of emei_evaluate_sequences: n_policies stacked struct emei_policy networks,
+ *    each scored on every env from the envs' current or given states in one launch; the handle is untouched, no kernel id). */
 #define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
@@ -623,6 +625,48 @@ typedef struct emei_policy {
 } emei_policy;
 EMEI_API int emei_rollout_policy(emei_env* h, int32_t n_steps, const emei_policy* policy, void* actions_out, int action_dtype,
                                  float* obs_out, float* reward_out, uint8_t* done_out, uint32_t flags, void* stream);
+
+/* A population of feedback policies scored from the envs' current states in ONE launch, for policy search (evolution strategies and
+ * ARS over perturbed policies, CEM over policy weights, population-based training, choosing among checkpoints): the policy-side
+ * counterpart of emei_evaluate_sequences.  `stacked` is a struct emei_policy whose pointers each name P = n_policies networks laid end
+ * to end — w1 [P, hidden, obs_dim], b1 [P, hidden], w2 [P, n_out, hidden] ([P, n_out, obs_dim] when hidden == 0), b2 [P, n_out] —
+ * with hidden and out_mode shared by the population.  DEVICE pointers, read during the launch and not retained; they must not overlap
+ * any output of the call.
+ *
+ * Semantics (normative).  For every pair (p, i), p < n_policies, i < n_envs, and t = 0 .. horizon - 1:
+ *   1. Start.  The pair starts from env i's start state, emei_evaluate_sequences' rule: the handle's current state (start_state NULL)
+ *      or row i of start_state [n_envs, state_dim] float64 in emei_set_state's layout, narrowed as emei_set_state narrows it.
+ *   2. Observe.  x_0 is the observation of that state as emei_get_obs gives it, rounded to float32.  For t > 0, x_t is the float32
+ *      observation row that step t - 1 emits.
+ *   3. Policy.  a_t = pi_p(x_t): exactly clause 2 ("Policy") of emei_rollout_policy with member p's weights — float64 sums in
+ *      ascending index order, the hidden unit rounded to float32 before the ReLU, the clip / tanh / threshold output and its NaN handling.
+ *   4. Step and score.  The per-step arithmetic emei_rollout runs for this handle, scored as emei_evaluate_sequences scores:
+ *      ret = sum over t < L of discount^t * (double)(float)r_t, accumulated in float64 in step order, discount^t a float64 running
+ *      product from 1.0; L = index of the first step whose terminal bit is set + 1, or horizon (the terminal step's reward counts).
+ *      A pair past its terminal step keeps stepping without accumulating; its wave leaves once none of its pairs is live.
+ * Not consulted: observation noise, the TimeLimit counters, truncation and auto-reset.  The handle is untouched: state, counters,
+ * reset key, frozen snapshot, the done mask emei_compact_done reads and emei_last_rollout_kernel.  Newton solves that end at the
+ * iteration cap count into emei_get_solver_cap_hits, as for the other queries.
+ * Outputs, policy-major:
+ *   return_out    [n_policies, n_envs] float64: ret.  Required.
+ *   length_out    [n_policies, n_envs] int32: L.  May be NULL.
+ *   final_obs_out [n_policies, n_envs, obs_dim] float32: the observation row of step L - 1.  May be NULL.
+ * Consequences.  Replay: candidate k = p of emei_evaluate_sequences, fed the actions_out of an emei_rollout_policy run with policy p
+ * from the same start and without EMEI_FLAG_AUTO_RESET, has the same return, length and final observation — bit for bit under
+ * EMEI_POLICY_OUT_CLIP and on the discrete envs, up to the HalfCheetah's lane lending (its wave-mates differ between the two calls).
+ * Sharding: results depend on the global env index, not on the shard.  Stream: the call neither allocates nor synchronises
+ * (capturable).
+ * Kernels: pend_policy_eval_kernel for every handle emei_rollout runs on the 4-state family's kernels, body_policy_eval_kernel for
+ * every handle on the body kernels.  One lane per pair; a block serves one policy (block b: policy b / nb, env block b % nb with
+ * nb = ceil(n_envs / 256)), so the weights are read through wave-uniform addresses (scalar loads), and wave w of a policy holds envs
+ * 64 w .. 64 w + 63 as in emei_rollout_policy.
+ * EMEI_ERR_INVALID before any HIP call, each message naming the argument, in this order: horizon < 1; n_policies < 1; discount outside
+ * (0, 1]; NULL stacked; struct_size wrong; hidden < 0 or > EMEI_POLICY_MAX_HIDDEN; unknown out_mode; reserved != 0; a NULL handle;
+ * NULL w2 or b2; hidden > 0 with NULL w1 or b1; NULL return_out; n_envs * n_policies > 2^31 - 1, or more than 2^31 - 1 blocks.
+ * EMEI_ERR_STATE without a state and without start_state. */
+EMEI_API int emei_evaluate_policies(emei_env* h, int32_t horizon, int32_t n_policies, const emei_policy* stacked, double discount,
+                                    const double* start_state, double* return_out, int32_t* length_out, float* final_obs_out,
+                                    void* stream);
 
 /* Which kernel the LAST emei_step / emei_rollout of this handle launched (enum emei_kernel_id): a debug /
  * test getter, so that a parity test can assert that the path it checked is the path bench.py times. */
