@@ -43,11 +43,17 @@ KERNEL_NAMES = {0: "none", 1: "pend_rollout_staged_kernel<freq1>", 2: "pend_roll
 # ... and the ids of emei_rollout_policy's kernels, a table of their own (KERNEL_NAMES stays the 15 ids of emei_rollout and the fused
 # controllers); kernel_name() looks an id up in both
 POLICY_KERNEL_NAMES = {15: "pend_policy_rollout_kernel", 16: "body_policy_rollout_kernel", 17: "body_policy_rollout_kernel<rk4>"}
+# ... and those of emei_rollout_policy_noisy, likewise a table of their own
+POLICY_NOISY_KERNEL_NAMES = {18: "pend_policy_rollout_noisy_kernel", 19: "body_policy_rollout_noisy_kernel",
+                             20: "body_policy_rollout_noisy_kernel<rk4>"}
 
 
 def kernel_name(kernel_id):
     """name of an enum emei_kernel_id value (emei_last_rollout_kernel)"""
-    return KERNEL_NAMES[kernel_id] if kernel_id in KERNEL_NAMES else POLICY_KERNEL_NAMES[kernel_id]
+    for table in (KERNEL_NAMES, POLICY_KERNEL_NAMES, POLICY_NOISY_KERNEL_NAMES):
+        if kernel_id in table:
+            return table[kernel_id]
+    raise KeyError(kernel_id)
 
 
 KERNEL_PEND_STAGED_FREQ1, KERNEL_PEND_STAGED, KERNEL_PEND_GENERIC_FULL, KERNEL_PEND_GENERIC, KERNEL_BODY, KERNEL_BODY_RK4 = 1, 2, 3, 4, 5, 6
@@ -58,6 +64,8 @@ KERNEL_PEND_MPC_CEM = 12
 KERNEL_BODY_MPC_MPPI, KERNEL_BODY_MPC_CEM = 13, 14  # the InvertedDoublePendulum's fused controllers
 KERNEL_PEND_POLICY, KERNEL_BODY_POLICY, KERNEL_BODY_POLICY_RK4 = 15, 16, 17  # emei_rollout_policy
 POLICY_OUT_CLIP, POLICY_OUT_TANH = 0, 1  # enum emei_policy_out
+KERNEL_PEND_POLICY_NOISY, KERNEL_BODY_POLICY_NOISY, KERNEL_BODY_POLICY_NOISY_RK4 = 18, 19, 20  # emei_rollout_policy_noisy
+POLICY_NOISE_GAUSS, POLICY_NOISE_GAUSS_HEAD, POLICY_NOISE_EPS_GREEDY = 0, 1, 2  # enum emei_policy_noise_mode
 POLICY_MAX_HIDDEN = 1024  # EMEI_POLICY_MAX_HIDDEN
 MPC_MAX_HORIZON = 256  # EMEI_MPC_MAX_HORIZON
 MAX_OBS_PEERS = 8  # EMEI_MAX_OBS_PEERS
@@ -122,6 +130,23 @@ class EmeiPolicy(C.Structure):
     ]
 
 
+class EmeiPolicyNoise(C.Structure):
+    """struct emei_policy_noise (include/emei_hip.h): std / ws / bs are device pointers."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("mode", C.c_int32),
+        ("seed", C.c_uint64),
+        ("sigma", C.c_double),
+        ("std", C.c_void_p),
+        ("ws", C.c_void_p),
+        ("bs", C.c_void_p),
+        ("log_std_min", C.c_float),
+        ("log_std_max", C.c_float),
+        ("reserved", C.c_int32),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/emei_hip.h declares
 _vp, _i32, _i64, _u32, _u64, _dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 SYMBOLS = {
@@ -166,6 +191,8 @@ SYMBOLS = {
     "emei_mpc_cem": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _u64, _vp, _dbl, _dbl, _dbl, C.c_float, C.c_float, C.c_float, _vp, _vp,
                                C.c_int, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "emei_rollout_policy": (C.c_int, [_vp, _i32, C.POINTER(EmeiPolicy), _vp, C.c_int, _vp, _vp, _vp, _u32, _vp]),
+    "emei_rollout_policy_noisy": (C.c_int, [_vp, _i32, C.POINTER(EmeiPolicy), C.POINTER(EmeiPolicyNoise), _vp, C.c_int, _vp, _vp, _vp, _u32,
+                                            _vp]),
     "emei_evaluate_policies": (C.c_int, [_vp, _i32, _i32, C.POINTER(EmeiPolicy), _dbl, _vp, _vp, _vp, _vp, _vp]),
     "emei_compact_done": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emei_get_counters": (C.c_int, [_vp, _vp, _vp, _vp]),

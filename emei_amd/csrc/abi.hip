@@ -1127,19 +1127,47 @@ static int check_policy_weights(const char* fn, const char* arg, const emei_poli
 }
 
 // ---------------------------------------------------------------------------------------------
-// emei_rollout_policy: n_steps of "observe, evaluate the policy, emei_step" in one launch of the family's policy rollout kernel
-// (pendulum_kernels.h:pend_policy_rollout_kernel, body_kernels.h:body_policy_rollout_kernel); the kernel leaves the done mask itself.
-extern "C" EMEI_API int emei_rollout_policy(emei_env* h, int32_t n_steps, const emei_policy* policy, void* actions_out, int action_dtype,
-                                            float* obs_out, float* reward_out, uint8_t* done_out, uint32_t flags, void* stream) {
-    const char* fn = "emei_rollout_policy";
+// What emei_rollout_policy_noisy refuses about its struct emei_policy_noise before the handle is looked at.
+static int check_policy_noise(const char* fn, const emei_policy_noise* nz) {
+    if (!nz) return fail(EMEI_ERR_INVALID, "%s: null noise", fn);
+    if (nz->struct_size != sizeof(emei_policy_noise))
+        return fail(EMEI_ERR_INVALID, "%s: noise.struct_size=%u != sizeof(emei_policy_noise)=%zu", fn, nz->struct_size, sizeof(emei_policy_noise));
+    if (nz->mode < EMEI_POLICY_NOISE_GAUSS || nz->mode > EMEI_POLICY_NOISE_EPS_GREEDY)
+        return fail(EMEI_ERR_INVALID, "%s: unknown noise.mode=%d", fn, nz->mode);
+    if (nz->reserved != 0) return fail(EMEI_ERR_INVALID, "%s: noise.reserved=%d must be 0", fn, nz->reserved);
+    if (nz->mode == EMEI_POLICY_NOISE_GAUSS && !nz->std && !(std::isfinite(nz->sigma) && nz->sigma >= 0.0))
+        return fail(EMEI_ERR_INVALID, "%s: noise.sigma=%g must be finite and >= 0 (noise.std is null)", fn, nz->sigma);
+    if (nz->mode == EMEI_POLICY_NOISE_EPS_GREEDY && !(nz->sigma >= 0.0 && nz->sigma <= 1.0))
+        return fail(EMEI_ERR_INVALID, "%s: noise.sigma=%g (epsilon) is outside [0, 1]", fn, nz->sigma);
+    if (nz->mode == EMEI_POLICY_NOISE_GAUSS_HEAD) {
+        if (!(nz->log_std_min <= nz->log_std_max))
+            return fail(EMEI_ERR_INVALID, "%s: noise.log_std_min=%g > noise.log_std_max=%g (or a NaN)", fn, (double)nz->log_std_min,
+                        (double)nz->log_std_max);
+        if (!nz->ws || !nz->bs) return fail(EMEI_ERR_INVALID, "%s: null noise.%s", fn, !nz->ws ? "ws" : "bs");
+    }
+    return EMEI_OK;
+}
+
+// emei_rollout_policy / emei_rollout_policy_noisy (`noisy`: the latter, with `noise` checked in its place of the header's order):
+// n_steps of "observe, evaluate the policy, emei_step" in one launch of the family's policy rollout kernel
+// (pendulum_kernels.h:pend_policy_rollout_kernel, body_kernels.h:body_policy_rollout_kernel, or their noisy twins); the kernel leaves
+// the done mask itself.
+static int rollout_policy(const char* fn, bool noisy, emei_env* h, int32_t n_steps, const emei_policy* policy, const emei_policy_noise* noise,
+                          void* actions_out, int action_dtype, float* obs_out, float* reward_out, uint8_t* done_out, uint32_t flags,
+                          void* stream) {
     if (n_steps < 1) return fail(EMEI_ERR_INVALID, "%s: n_steps=%d < 1", fn, n_steps);
     if (int rc = check_policy_struct(fn, "policy", policy)) return rc;
+    if (noisy)
+        if (int rc = check_policy_noise(fn, noise)) return rc;
     if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
     if (int rc = check_policy_weights(fn, "policy", policy)) return rc;
     if (action_dtype < EMEI_ACT_U8 || action_dtype > EMEI_ACT_F32 || (h->act_dim > 0) != (action_dtype == EMEI_ACT_F32))
         return fail(EMEI_ERR_INVALID, "%s: action_dtype=%d: actions_out is uint8 / int32 / int64 for the discrete envs, float32 for the "
                                       "continuous ones", fn, action_dtype);
     if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "%s: unknown flags 0x%x", fn, flags);
+    if (noisy && (h->act_dim > 0) == (noise->mode == EMEI_POLICY_NOISE_EPS_GREEDY))
+        return fail(EMEI_ERR_INVALID, "%s: noise.mode=%d: the Gaussian modes are for the continuous envs, EMEI_POLICY_NOISE_EPS_GREEDY for "
+                                      "the discrete ones", fn, noise->mode);
     EMEI_ON_DEVICE(h, fn);
     if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
     if (h->peers.count > 0)
@@ -1148,28 +1176,46 @@ extern "C" EMEI_API int emei_rollout_policy(emei_env* h, int32_t n_steps, const 
     pa.w1 = policy->w1, pa.b1 = policy->b1, pa.w2 = policy->w2, pa.b2 = policy->b2;
     pa.actions_out = actions_out, pa.hidden = policy->hidden, pa.out_mode = policy->out_mode, pa.action_dtype = action_dtype;
     ctrl_range(h->cfg.env_id, pa.lo, pa.hi);
+    PolicyNoiseArgs na{};
+    if (noisy) {
+        na.seed = noise->seed, na.mode = noise->mode, na.sigma = (float)noise->sigma;
+        if (noise->mode == EMEI_POLICY_NOISE_GAUSS) na.std = noise->std;
+        if (noise->mode == EMEI_POLICY_NOISE_GAUSS_HEAD)
+            na.ws = noise->ws, na.bs = noise->bs, na.log_std_min = noise->log_std_min, na.log_std_max = noise->log_std_max;
+    }
     int rc;
     if (!steps_as_body(h->cfg)) {
         PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_POLICY;
+        L.op = noisy ? PEND_OP_POLICY_NOISY : PEND_OP_POLICY;
         L.action_dtype = action_dtype;
         L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
         L.n_steps = n_steps;
         L.flags = flags;
-        L.policy = pa;
+        L.policy = pa, L.policy_noise = na;
         L.selected = &h->last_kernel;
         rc = pend_launch(L);
     } else {
         BodyLaunch L = body_base(h, stream);
-        L.op = BODY_OP_POLICY;
+        L.op = noisy ? BODY_OP_POLICY_NOISY : BODY_OP_POLICY;
         L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
         L.n_steps = n_steps;
         L.flags = flags;
-        L.policy = pa;
+        L.policy = pa, L.policy_noise = na;
         L.selected = &h->last_kernel;
         rc = body_launch(L);
     }
     return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+}
+extern "C" EMEI_API int emei_rollout_policy(emei_env* h, int32_t n_steps, const emei_policy* policy, void* actions_out, int action_dtype,
+                                            float* obs_out, float* reward_out, uint8_t* done_out, uint32_t flags, void* stream) {
+    return rollout_policy("emei_rollout_policy", false, h, n_steps, policy, nullptr, actions_out, action_dtype, obs_out, reward_out, done_out,
+                          flags, stream);
+}
+extern "C" EMEI_API int emei_rollout_policy_noisy(emei_env* h, int32_t n_steps, const emei_policy* policy, const emei_policy_noise* noise,
+                                                  void* actions_out, int action_dtype, float* obs_out, float* reward_out, uint8_t* done_out,
+                                                  uint32_t flags, void* stream) {
+    return rollout_policy("emei_rollout_policy_noisy", true, h, n_steps, policy, noise, actions_out, action_dtype, obs_out, reward_out,
+                          done_out, flags, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

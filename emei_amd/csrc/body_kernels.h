@@ -169,7 +169,8 @@ enum BodyOp { BODY_OP_ROLLOUT = 0, BODY_OP_RESET, BODY_OP_GET_OBS, BODY_OP_INIT_
               BODY_OP_MPC_MPPI /* emei_mpc_mppi: body_mpc_mppi_kernel (Body::kFusedMpc) */,
               BODY_OP_MPC_CEM /* emei_mpc_cem: body_mpc_cem_kernel (Body::kFusedMpc) */,
               BODY_OP_POLICY /* emei_rollout_policy: body_policy_rollout_kernel */,
-              BODY_OP_POLICY_EVAL /* emei_evaluate_policies: body_policy_eval_kernel */ };
+              BODY_OP_POLICY_EVAL /* emei_evaluate_policies: body_policy_eval_kernel */,
+              BODY_OP_POLICY_NOISY /* emei_rollout_policy_noisy: body_policy_rollout_noisy_kernel */ };
 
 // What BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM take beyond the base descriptor: n_steps control steps of the planner with plan.n_candidates
 // candidates over `horizon` steps under plan.discount; plan.cand carries the call's seed, sigma and the ctrlrange (its nominal is
@@ -227,6 +228,7 @@ struct BodyLaunch {
     int* selected = nullptr;  // out: enum emei_kernel_id of the rollout kernel launched
     PlanLaunch plan;  // BODY_OP_PLAN; n_steps = the horizon, obs_out = final_obs [n * K, NO] or null
     MpcLaunch mpc;    // BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM
+    PolicyNoiseArgs policy_noise = {};  // BODY_OP_POLICY_NOISY (emei_rollout_policy_noisy): the noise of the call, next to `policy`
     PolicyArgs policy = {};  // BODY_OP_POLICY: BODY_OP_ROLLOUT's fields without `actions`; weights, ctrlrange and actions_out (float32)
                              // BODY_OP_POLICY_EVAL: the STACKED weights (member p at p * its size), with `plan` as PLAN_GIVEN takes it:
                              // n_candidates = the number of policies, return_out / length_out [P, n]; obs_out = final_obs [P, n, NO] or null
@@ -729,6 +731,150 @@ __global__ void __launch_bounds__(rollout_block<Body>()) __attribute__((amdgpu_w
     if (lane == 0 && active) a.done_mask[i / kWave] = mk;
 }
 
+// emei_rollout_policy_noisy: body_policy_rollout_kernel with the exploration term drawn in the lane (emei_device.h:
+// policy_eval_t<NOISY>): the action of step 0 under the key nz.seed, the action of step t + 1, computed at the end of step t, under
+// nz.seed + t + 1.  Nothing else differs.  A kernel of its own name, so that the deterministic one stays the code it was.
+template <class Body, bool RK4>
+__global__ void __launch_bounds__(rollout_block<Body>()) __attribute__((amdgpu_waves_per_eu(Body::kMinWavesPerEU)))
+    body_policy_rollout_noisy_kernel(const BodyArgs<Body> a, const PolicyArgs pol, const PolicyNoiseArgs nz) {
+    using R = typename Body::real;
+    constexpr int NS = Body::NS, NO = Body::NO, NA = Body::NA;
+    constexpr int kBlock = rollout_block<Body>();  // shadows the library-wide 256 inside this kernel
+    constexpr int kWaves = kBlock / kWave;
+    constexpr int kObsVec = (kWave * NO + 3) / 4;  // 16-byte vectors per wave block
+    constexpr int kObsIt = (kObsVec + kWave - 1) / kWave;
+    __shared__ __attribute__((aligned(16))) float obs_s[kWaves][kObsIt * kWave * 4];
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table<kBlock>(trig_s, a.trig);  // every thread reaches the barrier: inactive lanes stay in the kernel
+    TrigCtx trig;
+    trig.tab = trig_s;
+    __shared__ R scratch_s[(Body::kScratchPerLane > 0 ? Body::kScratchPerLane : 1) * (Body::kScratchPerLane > 0 ? kBlock : 1)];
+    if constexpr (Body::kScratchPerLane > 0) trig.scratch = scratch_s;
+    trig.scratch_stride = kBlock;
+    trig.cap_hits = a.cap_hits;
+    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t n = a.n;
+    const int64_t i0 = i - lane;                             // first env of this wave
+    const int wave_envs = (int)min((int64_t)kWave, n - i0);  // ragged last wave
+    const bool active = i < n;
+
+    R s[NS];
+    int32_t steps = 0;
+    uint32_t episode = 0;
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = a.state[(int64_t)k * n + i];
+        steps = a.steps[i];
+        episode = a.episode[i];
+    } else {
+        Body::park(s);  // see body_rollout_kernel
+    }
+    const bool auto_reset = (a.flags & EMEI_FLAG_AUTO_RESET) != 0;
+    const bool obs_noise = a.noise.obs_on != 0;
+    uint32_t done = 0;
+    R spare[Body::kSpareReset ? NS : 1];
+    bool have_spare = false;
+
+    // the float32 observation of the state, as emei_get_obs / emei_episode_init_obs round it
+    auto observe = [&](float (&x)[NO]) __attribute__((always_inline)) {
+        double od[NO];
+        Body::obs_of(s, od, a.m);
+#pragma unroll
+        for (int k = 0; k < NO; ++k) x[k] = (float)od[k];
+    };
+    const uint64_t g = a.env_offset + (uint64_t)i;  // the noise words are the global env index's
+    float act[NA];
+    {
+        float x[NO];
+        observe(x);
+        policy_eval_t<NO, NA, false, true>(pol, nz, nz.seed, g, x, act);
+    }
+    for (int t = 0; t < a.n_steps; ++t) {
+        R ctrl[NA];
+#pragma unroll
+        for (int k = 0; k < NA; ++k) ctrl[k] = active ? (R)act[k] : R(0);
+        if (pol.actions_out && active) {
+            float* dst = (float*)pol.actions_out + ((int64_t)t * n + i) * NA;
+#pragma unroll
+            for (int k = 0; k < NA; ++k) dst[k] = act[k];
+        }
+
+        R pre[NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) pre[k] = s[k];
+        typename Body::Warm warm{};  // per env-step, as body_rollout_kernel
+        for (int k = 0; k < a.freq_rate; ++k) {  // mujoco_env.py:91-104
+            body_substep<Body, RK4>(s, ctrl, a.m, a.semi != 0, trig, warm);
+            if (obs_noise)
+                gauss_state<R, NS, false>(s, a.seed ^ kObsNoiseKey, a.env_offset + (uint64_t)i, episode,
+                                          ((uint32_t)steps * (uint32_t)a.freq_rate + (uint32_t)k) * (uint32_t)((NS + 3) / 4),
+                                          a.noise.obs, a.noise.shared != 0);
+        }
+        float o[NO];
+        R rew;
+        bool term;
+        Body::outputs(s, pre, ctrl, a.m, a.freq_rate, o, rew, term, trig);
+        ++steps;
+        const bool trunc = (a.max_episode_steps > 0) & (steps >= a.max_episode_steps);
+        done = active ? ((term ? EMEI_DONE_TERMINAL : 0u) | (trunc ? EMEI_DONE_TRUNCATED : 0u)) : 0u;
+
+        if (a.obs_out) {  // lane-wise into LDS, linear out
+            float* mine = &obs_s[wv][lane * NO];
+#pragma unroll
+            for (int k = 0; k < NO; ++k) mine[k] = o[k];
+            wave_lds_fence();
+            float* dst = a.obs_out + ((int64_t)t * n + i0) * NO;
+            if (wave_envs == kWave && (((uintptr_t)dst) & 15u) == 0) {
+#pragma unroll
+                for (int c = 0; c < kObsIt; ++c) {
+                    const int vec = c * kWave + lane;
+                    if (vec < kObsVec) store_body_out<Body::kStreamOutputs>((float4*)dst + vec, ((const float4*)obs_s[wv])[vec]);
+                }
+            } else {
+                for (int e = lane; e < wave_envs * NO; e += kWave) dst[e] = obs_s[wv][e];
+            }
+            wave_lds_fence();
+        }
+        if (active) {
+            if (a.reward_out) store_body_out<Body::kStreamOutputs>(a.reward_out + (int64_t)t * n + i, (float)rew);
+            if (a.done_out) store_body_out<Body::kStreamOutputs>(a.done_out + (int64_t)t * n + i, (uint8_t)done);
+        }
+        if (__builtin_expect(auto_reset && __ballot(done != 0) != 0ull, 0)) {
+            if constexpr (Body::kSpareReset) {
+                if (__ballot((done != 0) & !have_spare) != 0ull) {
+                    if (!have_spare) {
+                        body_init<Body>(spare, a.seed, a.env_offset + (uint64_t)i, episode + 1u, a.noise);
+                        have_spare = true;
+                    }
+                }
+                if (done != 0) {
+                    ++episode;
+                    steps = 0;
+#pragma unroll
+                    for (int k = 0; k < NS; ++k) s[k] = spare[k];
+                    have_spare = false;
+                    observe(o);
+                }
+            } else if (done != 0) {  // episodes only end by TimeLimit, for all lanes at once
+                ++episode;
+                steps = 0;
+                body_init<Body>(s, a.seed, a.env_offset + (uint64_t)i, episode, a.noise);
+                observe(o);
+            }
+        }
+        if (t + 1 < a.n_steps) policy_eval_t<NO, NA, false, true>(pol, nz, nz.seed + (uint64_t)t + 1u, g, o, act);  // wave-uniform: the next step's action
+    }
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) a.state[(int64_t)k * n + i] = s[k];
+        a.steps[i] = steps;
+        a.episode[i] = episode;
+    }
+    unsigned long long mk = __ballot(done != 0);
+    if (lane == 0 && active) a.done_mask[i / kWave] = mk;
+}
+
 template <class Body>
 __global__ void __launch_bounds__(kBlock)
     body_reset_kernel(typename Body::real* state, int32_t* steps, uint32_t* episode, int64_t n, uint64_t seed,
@@ -1109,7 +1255,9 @@ static int launch_body(const BodyLaunch& L) {
                                      : (L.integrator == EMEI_INTEG_RK4 ? EMEI_KERNEL_BODY_RK4 : EMEI_KERNEL_BODY);
             break;
         }
-        case BODY_OP_POLICY: {  // always one piece: block b = env block b (the work queue is body_rollout_kernel's)
+        case BODY_OP_POLICY:
+        case BODY_OP_POLICY_NOISY: {  // always one piece: block b = env block b (the work queue is body_rollout_kernel's)
+            const bool rk4 = L.integrator == EMEI_INTEG_RK4;
             BodyArgs<Body> a;
             a.state = (R*)L.state, a.steps = L.steps, a.episode = L.episode, a.done_mask = L.done_mask;
             a.actions = nullptr, a.obs_out = L.obs_out, a.reward_out = L.reward_out, a.done_out = L.done_out;
@@ -1119,11 +1267,16 @@ static int launch_body(const BodyLaunch& L) {
             a.trig = (const SinCosEntry*)L.trig;
             a.cap_hits = L.cap_hits;
             a.work = nullptr, a.chunk_steps = 0, a.n_waves = rgrid.x, a.n_items = 0;
-            if (L.integrator == EMEI_INTEG_RK4)
-                hipLaunchKernelGGL((body_policy_rollout_kernel<Body, true>), rgrid, dim3(rollout_block<Body>()), 0, L.stream, a, L.policy);
-            else
-                hipLaunchKernelGGL((body_policy_rollout_kernel<Body, false>), rgrid, dim3(rollout_block<Body>()), 0, L.stream, a, L.policy);
-            if (L.selected) *L.selected = L.integrator == EMEI_INTEG_RK4 ? EMEI_KERNEL_BODY_POLICY_RK4 : EMEI_KERNEL_BODY_POLICY;
+            const dim3 blk(rollout_block<Body>());
+            if (L.op == BODY_OP_POLICY_NOISY) {
+                if (rk4) hipLaunchKernelGGL((body_policy_rollout_noisy_kernel<Body, true>), rgrid, blk, 0, L.stream, a, L.policy, L.policy_noise);
+                else hipLaunchKernelGGL((body_policy_rollout_noisy_kernel<Body, false>), rgrid, blk, 0, L.stream, a, L.policy, L.policy_noise);
+                if (L.selected) *L.selected = rk4 ? EMEI_KERNEL_BODY_POLICY_NOISY_RK4 : EMEI_KERNEL_BODY_POLICY_NOISY;
+            } else {
+                if (rk4) hipLaunchKernelGGL((body_policy_rollout_kernel<Body, true>), rgrid, blk, 0, L.stream, a, L.policy);
+                else hipLaunchKernelGGL((body_policy_rollout_kernel<Body, false>), rgrid, blk, 0, L.stream, a, L.policy);
+                if (L.selected) *L.selected = rk4 ? EMEI_KERNEL_BODY_POLICY_RK4 : EMEI_KERNEL_BODY_POLICY;
+            }
             break;
         }
         case BODY_OP_POLICY_EVAL: {  // emei_evaluate_policies: block b = (policy b / grid.x, env block b % grid.x); abi.hip bounds the grid

@@ -747,13 +747,36 @@ struct PolicyArgs {
 // for the cheetah at EMEI_POLICY_MAX_HIDDEN, on top of its solver's slots — and a fill phase per launch.)
 typedef const __attribute__((address_space(4))) float* PolicyWeights;
 
+struct PolicyNoiseArgs {  // kernel-argument form of struct emei_policy_noise
+    uint64_t seed;
+    const float* std;  // GAUSS: [n_out] or null (then sigma)
+    const float* ws;   // GAUSS_HEAD: [n_out, hidden] (hidden == 0: [n_out, NO])
+    const float* bs;   // GAUSS_HEAD: [n_out]
+    float sigma;       // GAUSS with std null: every component's std; EPS_GREEDY: epsilon
+    float log_std_min, log_std_max;
+    int32_t mode;      // enum emei_policy_noise_mode
+};
+
 // One evaluation for one lane: x[NO] -> act[NA] (discrete envs: act[0] is 0.f or 1.f).  One hidden unit at a time: z over the
 // NO inputs, h_j, then its contribution to the NA accumulators — nothing of size `hidden` is ever live.  fma() on float64: the
 // products of two widened float32 values are exact, so this is the ascending-order sum of the specification, bit for bit.
-template <int NO, int NA, bool DISCRETE>
-__device__ __forceinline__ void policy_eval(const PolicyArgs& pa, const float (&x)[NO], float (&act)[NA]) {
+//
+// NOISY (emei_rollout_policy_noisy; nz, key = seed + t and g = the global env index are read only then): the exploration term of
+// step t joins y last, s_q * z_q with z from the lane's own words CandidateWords(key, g, 0) — the normals candidate k = 0 draws at
+// step 0 under that key — or, on a discrete env, the epsilon-greedy draws W[0] / W[1] replace the threshold.  The log-std head's NA
+// accumulators ride the hidden-unit loop next to y.  NOISY = false is policy_eval, the code it was.
+template <int NO, int NA, bool DISCRETE, bool NOISY>
+__device__ __forceinline__ void policy_eval_t(const PolicyArgs& pa, const PolicyNoiseArgs& nz, uint64_t key, uint64_t g,
+                                              const float (&x)[NO], float (&act)[NA]) {
     const PolicyWeights w1 = (PolicyWeights)pa.w1, b1 = (PolicyWeights)pa.b1, w2 = (PolicyWeights)pa.w2, b2 = (PolicyWeights)pa.b2;
     const int hidden = pa.hidden;  // wave-uniform, as every index below
+    [[maybe_unused]] const PolicyWeights ws = (PolicyWeights)nz.ws, bs = (PolicyWeights)nz.bs;
+    [[maybe_unused]] const bool head = NOISY && !DISCRETE && nz.mode == EMEI_POLICY_NOISE_GAUSS_HEAD;  // wave-uniform
+    [[maybe_unused]] double l[NA];
+    if constexpr (NOISY && !DISCRETE) {
+#pragma unroll
+        for (int q = 0; q < NA; ++q) l[q] = head ? (double)bs[q] : 0.0;
+    }
     double y[NA];
 #pragma unroll
     for (int q = 0; q < NA; ++q) y[q] = (double)b2[q];
@@ -766,12 +789,47 @@ __device__ __forceinline__ void policy_eval(const PolicyArgs& pa, const float (&
             hj = hj > 0.f ? hj : 0.f;  // NaN -> 0
 #pragma unroll
             for (int q = 0; q < NA; ++q) y[q] = fma((double)w2[q * hidden + j], (double)hj, y[q]);
+            if constexpr (NOISY && !DISCRETE) {
+                if (head) {
+#pragma unroll
+                    for (int q = 0; q < NA; ++q) l[q] = fma((double)ws[q * hidden + j], (double)hj, l[q]);
+                }
+            }
         }
     } else {
 #pragma unroll
         for (int k = 0; k < NO; ++k) {
 #pragma unroll
             for (int q = 0; q < NA; ++q) y[q] = fma((double)w2[q * NO + k], (double)x[k], y[q]);
+            if constexpr (NOISY && !DISCRETE) {
+                if (head) {
+#pragma unroll
+                    for (int q = 0; q < NA; ++q) l[q] = fma((double)ws[q * NO + k], (double)x[k], l[q]);
+                }
+            }
+        }
+    }
+    if constexpr (NOISY && DISCRETE) {
+        CandidateWords cw(key, g, 0u);
+        const bool explore = u01(cw.word(0u)) < nz.sigma, coin = u01(cw.word(1u)) < 0.5f;
+        act[0] = explore ? (coin ? 1.f : 0.f) : (y[0] >= 0.0 ? 1.f : 0.f);
+        return;
+    }
+    if constexpr (NOISY && !DISCRETE) {
+        CandidateWords cw(key, g, 0u);
+        const PolicyWeights sd = (PolicyWeights)nz.std;
+#pragma unroll
+        for (int p = 0; p < (NA + 1) / 2; ++p) {  // the pair (W[2p], W[2p + 1]) lies inside one Philox block
+            float z[2];
+            const uint32_t wa = cw.word(2u * p), wb = cw.word(2u * p + 1u);
+            boxmuller(wa, wb, z[0], z[1]);
+#pragma unroll
+            for (int q = 2 * p; q < 2 * p + 2 && q < NA; ++q) {
+                float sq;
+                if (head) sq = (float)exp(fmin(fmax(l[q], (double)nz.log_std_min), (double)nz.log_std_max));
+                else sq = sd ? sd[q] : nz.sigma;
+                y[q] = fma((double)sq, (double)z[q & 1], y[q]);  // the last term of the sum
+            }
         }
     }
 #pragma unroll
@@ -784,6 +842,10 @@ __device__ __forceinline__ void policy_eval(const PolicyArgs& pa, const float (&
             act[q] = fminf(fmaxf((float)y[q], pa.lo), pa.hi);  // NaN -> lo
         }
     }
+}
+template <int NO, int NA, bool DISCRETE>
+__device__ __forceinline__ void policy_eval(const PolicyArgs& pa, const float (&x)[NO], float (&act)[NA]) {
+    policy_eval_t<NO, NA, DISCRETE, false>(pa, PolicyNoiseArgs{}, 0, 0, x, act);
 }
 
 // ---------------------------------------------------------------------------------------------

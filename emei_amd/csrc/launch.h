@@ -7,7 +7,7 @@
 
 namespace emei {
 
-enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC, PEND_OP_MPC_CEM, PEND_OP_POLICY, PEND_OP_POLICY_EVAL };
+enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC, PEND_OP_MPC_CEM, PEND_OP_POLICY, PEND_OP_POLICY_EVAL, PEND_OP_POLICY_NOISY };
 
 // emei_set_obs_peers: the gathered buffers the staged rollout kernel also writes every observation row to
 struct ObsPeers {
@@ -89,6 +89,8 @@ struct PendLaunch {
     // PEND_OP_POLICY (emei_rollout_policy): PEND_OP_ROLLOUT's fields without `actions`; the weights, the ctrlrange and actions_out (in
     // policy.action_dtype) travel in `policy`
     PolicyArgs policy = {};
+    // PEND_OP_POLICY_NOISY (emei_rollout_policy_noisy): PEND_OP_POLICY's fields and the noise of the call
+    PolicyNoiseArgs policy_noise = {};
     // PEND_OP_POLICY_EVAL (emei_evaluate_policies): `policy` holds the STACKED weights (member p at p * its size; actions_out unused),
     // `plan` what PLAN_GIVEN takes with n_candidates = the number of policies and return_out / length_out [P, n] policy-major;
     // n_steps = the horizon, obs_out = final_obs [P, n, 4] or null

@@ -225,6 +225,77 @@ __global__ void __launch_bounds__(kBlock) pend_policy_rollout_kernel(const Rollo
     if ((threadIdx.x & (kWave - 1)) == 0) a.done_mask[i / kWave] = m;
 }
 
+// emei_rollout_policy_noisy: pend_policy_rollout_kernel with the exploration term of step t drawn in the lane under the key
+// nz.seed + t (emei_device.h:policy_eval_t<NOISY>); nothing else differs.  A kernel of its own name, so that the deterministic one
+// stays the code it was.
+template <class Env>
+__global__ void __launch_bounds__(kBlock) pend_policy_rollout_noisy_kernel(const RolloutArgs<Env> a, const PolicyArgs pol,
+                                                                           const PolicyNoiseArgs nz) {
+    using R = typename Env::real;
+    using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table(trig_s, a.trig, Env::trig_rot_c(), Env::trig_rot_s());
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const int64_t n = a.n;
+    const uint32_t li = (uint32_t)i;  // n_envs < 2^31 (checked in emei_create)
+
+    R s[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = a.state[k * n + i];
+    int32_t steps = a.steps[i];
+    uint32_t episode = a.episode[i];
+    typename Env::Carry c;
+    trig_ctx_init(c.trig, trig_s);
+    Env::prime(s, c, a.p);
+
+    const bool auto_reset = (a.flags & EMEI_FLAG_AUTO_RESET) != 0;
+    float x[4];
+    {
+        R o[4];
+        Env::obs_of(s, o);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = (float)o[k];
+    }
+    uint32_t done = 0;
+    for (int t = 0; t < a.n_steps; ++t) {
+        float av[1];
+        policy_eval_t<4, 1, Env::kDiscrete, true>(pol, nz, nz.seed + (uint64_t)t, a.env_offset + (uint64_t)i, x, av);
+        const int64_t row = (int64_t)t * n;  // uniform (scalar) row base + 32-bit lane index
+        if (pol.actions_out) store_action(pol.actions_out, pol.action_dtype, row + li, av[0]);
+        R o[4], rew;
+        bool term;
+        Env::step(s, c, Env::decode_t((DrawT)av[0]), a.p, a.freq_rate, o, rew, term);
+        ++steps;
+        bool trunc = (a.max_episode_steps > 0) & (steps >= a.max_episode_steps);
+        done = (term ? EMEI_DONE_TERMINAL : 0u) | (trunc ? EMEI_DONE_TRUNCATED : 0u);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = (float)o[k];
+        if (a.obs_out) (a.obs_out + row)[li] = make_float4(x[0], x[1], x[2], x[3]);
+        if (a.reward_out) (a.reward_out + row)[li] = (float)rew;
+        if (a.done_out) (a.done_out + row)[li] = (uint8_t)done;
+        if (auto_reset && __ballot(done != 0) != 0ull) {
+            if (done != 0) {
+                ++episode;
+                steps = 0;
+                Env::init(s, a.seed, a.env_offset + (uint64_t)i, episode, a.p);
+                Env::prime(s, c, a.p);
+                Env::obs_of(s, o);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) x[k] = (float)o[k];
+            }
+        }
+    }
+
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a.state[k * n + i] = s[k];
+    a.steps[i] = steps;
+    a.episode[i] = episode;
+    // done bits of the last step, one 64-bit word per wave, for emei_compact_done
+    unsigned long long m = __ballot(done != 0);
+    if ((threadIdx.x & (kWave - 1)) == 0) a.done_mask[i / kWave] = m;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Staged rollout: the fast path of emei_rollout (all outputs present, n a multiple of 64,
 // 16-byte aligned buffers).  Same arithmetic and results as pend_rollout_kernel; what changes is
@@ -1557,6 +1628,11 @@ static int launch_env(const PendLaunch& L) {
             if (L.peers.count > 0) return EMEI_ERR_UNSUPPORTED;  // no peer stores on this kernel (abi.hip refuses with a message)
             hipLaunchKernelGGL(pend_policy_rollout_kernel<Env>, grid, dim3(kBlock), 0, L.stream, a, L.policy);
             if (L.selected) *L.selected = EMEI_KERNEL_PEND_POLICY;
+            break;
+        case PEND_OP_POLICY_NOISY:
+            if (L.peers.count > 0) return EMEI_ERR_UNSUPPORTED;
+            hipLaunchKernelGGL(pend_policy_rollout_noisy_kernel<Env>, grid, dim3(kBlock), 0, L.stream, a, L.policy, L.policy_noise);
+            if (L.selected) *L.selected = EMEI_KERNEL_PEND_POLICY_NOISY;
             break;
         case PEND_OP_POLICY_EVAL: {  // emei_evaluate_policies: block b = (policy b / grid.x, env block b % grid.x); abi.hip bounds the grid
             const PlanLaunch& P = L.plan;

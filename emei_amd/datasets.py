@@ -34,7 +34,7 @@ def random_actions(env, n_steps, generator=None):
     return (lo + (hi - lo) * u).float().contiguous()
 
 
-def collect(env, n_steps, actions=None, seed=0, device_rng=True, policy=None, mpc=None):
+def collect(env, n_steps, actions=None, seed=0, device_rng=True, policy=None, mpc=None, noise=None):
     """Roll every env of `env` (a vectorised emei_amd env) for n_steps with auto-reset and return
     (dataset dict of torch tensors with N*n_steps rows, rollout_info dict like zoo/util.py:85-91).
 
@@ -44,12 +44,17 @@ def collect(env, n_steps, actions=None, seed=0, device_rng=True, policy=None, mp
     actions (`env.action_space.sample()`, zoo/util.py:58) in ONE fused rollout launch.
     A policy that is an emei_amd.MLPPolicy is evaluated inside the rollout kernel (Engine.rollout_policy: ONE launch, the same
     actions as the loop gives with that object as the callable); any other callable takes the per-step loop.
+    noise: an emei_amd.PolicyNoise next to policy=MLPPolicy — the stochastic behaviour policy of the zoo's datasets
+    (agent.predict(obs, deterministic=False), zoo/util.py:56), its exploration noise drawn inside the same ONE launch under the
+    noise's own seed; any other action source with noise= raises ValueError.
     mpc: instead of either, dict(horizon=, n_candidates=, temperature=[, seed=, discount=, sigma=, refill=, clamp=, nominal=]) — an
     MPPI controller on the true dynamics acts (Engine.mpc_mppi: ONE launch with auto-reset, the 4-state envs and the
     InvertedDoublePendulum — a continuous env needs sigma=; seed defaults to `seed`, nominal to `refill` everywhere).  With
     planner="cem" in the dict a CEM controller acts instead (Engine.mpc_cem):
     dict(planner="cem", horizon=, n_candidates=, n_elites=[, iterations=, sigma=, sigma_min=, seed=, discount=, refill=, clamp=,
     nominal=]); planner defaults to "mppi"."""
+    if noise is not None and not (actions is None and mpc is None and isinstance(policy, MLPPolicy)):
+        raise ValueError("collect: noise= goes with policy=MLPPolicy alone (the fused launch draws it)")
     eng = env.engine
     N, T, od = eng.n_envs, int(n_steps), eng.obs_dim
     obs0, _ = env.reset(seed=seed, options={"device_rng": True} if device_rng else None)
@@ -76,7 +81,7 @@ def collect(env, n_steps, actions=None, seed=0, device_rng=True, policy=None, mp
         else:
             actions, next_obs, rew, done = eng.mpc_cem(T, H, K, plan_arg, kw.pop("seed", seed), nominal, auto_reset=True, **kw)
     elif actions is None and isinstance(policy, MLPPolicy):  # the policy is evaluated inside the rollout kernel: ONE launch
-        actions, next_obs, rew, done = eng.rollout_policy(T, policy, auto_reset=True)
+        actions, next_obs, rew, done = eng.rollout_policy(T, policy, auto_reset=True, noise=noise)
     elif actions is None and policy is not None:
         next_obs, rew, done = eng.alloc_outputs(T)
         acts_t, cur, epi = [], obs0, epi0.clone()

@@ -325,18 +325,21 @@ class Engine:
         return obs, rew, done
 
     @_on_device
-    def rollout_policy(self, T, policy, auto_reset=False, out=None):
+    def rollout_policy(self, T, policy, auto_reset=False, out=None, noise=None):
         """T closed-loop steps under a feedback policy in one launch (emei_rollout_policy): per step the policy (policy.MLPPolicy)
         is evaluated inside the kernel on the observation the env holds — get_obs() rounded to float32 at first, then the row each
         step emits, or episode_init_obs of the new episode after an auto-reset — and the envs take step(action, auto_reset): bit for
         bit what that loop computes with policy(obs) as the callable (out="clip" and the discrete envs; out="tanh" up to the
         device's tanh), state, counters and compact_done() included.
         -> (actions [T, N(, act_dim)] int64 / float32, obs [T, N, obs_dim] f32, reward [T, N] f32, done [T, N] u8).
-        out: (obs, reward, done) as rollout's."""
+        out: (obs, reward, done) as rollout's.
+        noise: a policy.PolicyNoise — exploration noise drawn inside the kernel (emei_rollout_policy_noisy): Gaussian on the continuous
+        envs, epsilon-greedy on the discrete ones; step t draws under the key noise.seed + t, and the loop that calls
+        policy(obs, noise, t) gives the same actions.  None: the deterministic launch."""
         T = int(T)
         if T < 1:
             raise ValueError(f"n_steps={T} must be >= 1")
-        from .policy import MLPPolicy
+        from .policy import MLPPolicy, PolicyNoise
 
         if not isinstance(policy, MLPPolicy):
             raise TypeError("rollout_policy takes an emei_amd.MLPPolicy (any other callable acts through the per-step loop: step())")
@@ -345,8 +348,16 @@ class Engine:
         dtype = torch.int64 if self.act_dim == 0 else torch.float32
         act = torch.empty((T, self.n_envs) + self._act_tail, dtype=dtype, device=self.device)
         ps = policy.struct()
-        L.check(L.lib().emei_rollout_policy(self._h, T, C.byref(ps), _ptr(act), _ACT_DTYPES[dtype], _ptr(obs), _ptr(rew), _ptr(done),
-                                            L.FLAG_AUTO_RESET if auto_reset else 0, _stream()))
+        flags = L.FLAG_AUTO_RESET if auto_reset else 0
+        if noise is None:
+            L.check(L.lib().emei_rollout_policy(self._h, T, C.byref(ps), _ptr(act), _ACT_DTYPES[dtype], _ptr(obs), _ptr(rew), _ptr(done),
+                                                flags, _stream()))
+            return act, obs, rew, done
+        if not isinstance(noise, PolicyNoise):
+            raise TypeError("noise= takes an emei_amd.PolicyNoise")
+        ns = noise.bind(self).struct(policy.hidden if policy.hidden else policy.obs_dim)
+        L.check(L.lib().emei_rollout_policy_noisy(self._h, T, C.byref(ps), C.byref(ns), _ptr(act), _ACT_DTYPES[dtype], _ptr(obs), _ptr(rew),
+                                                  _ptr(done), flags, _stream()))
         return act, obs, rew, done
 
     @_on_device

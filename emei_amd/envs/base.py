@@ -184,12 +184,14 @@ class HipEnv(EmeiEnv):
         obs, rew, done = self.engine.rollout(actions, auto_reset=self.auto_reset if auto_reset is None else auto_reset)
         return obs, rew, (done & 1).bool(), (done & 2).bool()
 
-    def rollout_policy(self, n_steps, policy, auto_reset=None):
+    def rollout_policy(self, n_steps, policy, auto_reset=None, noise=None):
         """n_steps closed-loop steps under an emei_amd.MLPPolicy in one launch (Engine.rollout_policy, ABI emei_rollout_policy): what
         rollout() returns — obs [T,N,obs_dim] f32, reward [T,N] f32, terminal [T,N] bool, truncated [T,N] bool — plus the actions
-        [T, N(, act_dim)] the policy took.  auto_reset: the env's own setting unless given."""
+        [T, N(, act_dim)] the policy took.  auto_reset: the env's own setting unless given.  noise: an emei_amd.PolicyNoise, exploration
+        noise drawn inside the kernel (ABI emei_rollout_policy_noisy)."""
         assert self.state is not None, "Call reset before using step method."
-        act, obs, rew, done = self.engine.rollout_policy(n_steps, policy, auto_reset=self.auto_reset if auto_reset is None else auto_reset)
+        act, obs, rew, done = self.engine.rollout_policy(n_steps, policy, auto_reset=self.auto_reset if auto_reset is None else auto_reset,
+                                                         noise=noise)
         return obs, rew, (done & 1).bool(), (done & 2).bool(), act
 
     # -- freeze / unfreeze: device-to-device snapshot of the state SoA -------------------------------

@@ -1,7 +1,8 @@
 """Feedback policies the engine evaluates INSIDE a rollout launch (emei_rollout_policy, include/emei_hip.h).
 
 MLPPolicy holds the weights of a small network — one ReLU hidden layer, or affine — as contiguous float32 device tensors.
-Engine.rollout_policy hands their pointers to the kernel; calling the object, `policy(obs)`, evaluates the same normative
+Engine.rollout_policy hands their pointers to the kernel (with noise=PolicyNoise: emei_rollout_policy_noisy, exploration noise drawn
+inside the kernel); calling the object, `policy(obs)`, evaluates the same normative
 arithmetic (float64 sums in ascending index order) with torch operations, so the one object also serves the per-step path
 (`datasets.collect(env, n, policy=lambda o: policy(o))`) and gives the same actions there.
 """
@@ -88,12 +89,17 @@ class MLPPolicy:
         p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
         return L.EmeiPolicy(C.sizeof(L.EmeiPolicy), self.hidden, _OUT_MODES[self.out], 0, p(self.w1), p(self.b1), p(self.w2), p(self.b2))
 
-    def __call__(self, obs):
+    def __call__(self, obs, noise=None, t=None):
         """obs [N, obs_dim] -> actions [N] int64 (discrete), [N] float32 (one control) or [N, act_dim] float32: the normative
         arithmetic of emei_rollout_policy in torch float64 (products of float32 values are exact there; the sums run in ascending
-        index order, one elementwise operation per term).  Needs bind(engine) first (Engine.rollout_policy does it)."""
+        index order, one elementwise operation per term).  Needs bind(engine) first (Engine.rollout_policy does it).
+        noise, t: a bound PolicyNoise and the step index — the action step t of emei_rollout_policy_noisy takes on these rows
+        (row n is env n of the engine `noise` is bound to), the exploration term from noise.draws(engine, t): the same actions as the launch,
+        bit for bit under out="clip" with a given std and on the discrete envs."""
         if self.discrete is None:
             raise ValueError("MLPPolicy: bind(engine) first (which env's action space is this for?)")
+        if (noise is None) != (t is None):
+            raise ValueError("noise and t come together")
         x = torch.as_tensor(obs, device=self.w2.device).to(torch.float32).to(torch.float64)
         if self.hidden:
             z = self.b1.to(torch.float64)[None, :].repeat(x.shape[0], 1)
@@ -109,7 +115,14 @@ class MLPPolicy:
         for j in range(h.shape[1]):
             y = y + w2[None, :, j] * h[:, j:j + 1]
         if self.discrete:
-            return (y[:, 0] >= 0).to(torch.int64)
+            greedy = (y[:, 0] >= 0).to(torch.int64)
+            if noise is None:
+                return greedy
+            explore, coin = noise.draws(noise.bound_engine(), t)
+            return torch.where(explore != 0, coin.to(torch.int64), greedy)
+        if noise is not None:  # the last term of the sum: y_q + (double)s_q * (double)z_q
+            z = noise.draws(noise.bound_engine(), t).reshape(x.shape[0], self.n_out)
+            y = y + noise.scale(h).to(torch.float64) * z.to(torch.float64)
         if self.out == "tanh":
             a = (0.5 * (self.hi + self.lo) + 0.5 * (self.hi - self.lo) * torch.tanh(y)).to(torch.float32)
         else:
@@ -117,6 +130,102 @@ class MLPPolicy:
             a = torch.where(a >= self.lo, a, torch.full_like(a, self.lo))  # fmaxf(a, lo): NaN -> lo
             a = torch.where(a <= self.hi, a, torch.full_like(a, self.hi))
         return a[:, 0].contiguous() if self.n_out == 1 else a.contiguous()
+
+
+class PolicyNoise:
+    """The exploration noise of Engine.rollout_policy(..., noise=) (emei_rollout_policy_noisy, include/emei_hip.h), drawn inside the
+    kernel from the word stream of (seed + t, global env index).  Exactly one of
+      std: a float or [n_out] values — Gaussian noise std * z on the continuous envs, added to the network's output before clip / tanh;
+      log_std_head=(ws [n_out, hidden] (or [n_out, obs_dim] without a hidden layer), bs [n_out]): the std is exp(clamp(ws @ h + bs,
+          *log_std_range)), a second head on the policy's hidden layer (SAC's actor with out="tanh");
+      epsilon: in [0, 1] — epsilon-greedy on the discrete envs: with probability epsilon a fair coin replaces the policy's action."""
+
+    def __init__(self, seed, std=None, epsilon=None, log_std_head=None, log_std_range=(-20.0, 2.0)):
+        if sum(v is not None for v in (std, epsilon, log_std_head)) != 1:
+            raise ValueError("PolicyNoise takes exactly one of std=, epsilon= and log_std_head=")
+        self.seed = int(seed)
+        self.sigma, self.std, self.ws, self.bs = 0.0, None, None, None
+        self.log_std_min, self.log_std_max = (float(v) for v in log_std_range)
+        f = lambda v: torch.as_tensor(v).detach().to(torch.float32).contiguous()
+        if epsilon is not None:
+            self.mode, self.sigma = L.POLICY_NOISE_EPS_GREEDY, float(epsilon)
+            if not 0.0 <= self.sigma <= 1.0:
+                raise ValueError(f"epsilon={epsilon} is outside [0, 1]")
+        elif log_std_head is not None:
+            self.mode = L.POLICY_NOISE_GAUSS_HEAD
+            self.ws, self.bs = (f(v) for v in log_std_head)
+            if self.ws.dim() != 2 or self.bs.dim() != 1 or self.bs.shape[0] != self.ws.shape[0]:
+                raise ValueError(f"log_std_head: ws {tuple(self.ws.shape)} must be [n_out, n_in] and bs {tuple(self.bs.shape)} [n_out]")
+            if not self.log_std_min <= self.log_std_max:
+                raise ValueError(f"log_std_range={log_std_range}: min <= max, neither NaN")
+        else:
+            self.mode = L.POLICY_NOISE_GAUSS
+            if torch.as_tensor(std).dim() == 0:
+                self.sigma = float(std)
+                if not (self.sigma >= 0.0 and self.sigma != float("inf")):
+                    raise ValueError(f"std={std} must be finite and >= 0")
+            else:
+                self.std = f(std)
+                if self.std.dim() != 1:
+                    raise ValueError(f"std {tuple(self.std.shape)} must be a float or [n_out] values")
+        self._engine = None
+
+    def bind(self, engine):
+        """check the mode against `engine`'s env kind and the shapes against its action space; move the tensors to its device"""
+        discrete = engine.act_dim == 0
+        if discrete != (self.mode == L.POLICY_NOISE_EPS_GREEDY):
+            raise ValueError(f"{engine.env_name} is a {'discrete' if discrete else 'continuous'} env: epsilon= is for the discrete envs, "
+                             "std= and log_std_head= for the continuous ones")
+        n_out = engine.act_dim if engine.act_dim > 0 else 1
+        for k in ("std", "ws", "bs"):
+            v = getattr(self, k)
+            if v is not None:
+                if v.shape[0] != n_out:
+                    raise ValueError(f"noise {k} {tuple(v.shape)}: {engine.env_name} has {n_out} policy output(s)")
+                setattr(self, k, v.to(engine.device).contiguous())
+        self._engine = engine
+        return self
+
+    def bound_engine(self):
+        if self._engine is None:
+            raise ValueError("PolicyNoise: bind(engine) first")
+        return self._engine
+
+    def struct(self, hidden_in=None):
+        """struct emei_policy_noise over the tensors (which the caller keeps alive for the launch); hidden_in: the width the policy's
+        output layer reads, which the log-std head must read too"""
+        if self.ws is not None and hidden_in is not None and self.ws.shape[1] != hidden_in:
+            raise ValueError(f"log_std_head: ws {tuple(self.ws.shape)} must be [n_out, {hidden_in}] like the policy's w2")
+        p = lambda v: C.c_void_p(0 if v is None else v.data_ptr())
+        return L.EmeiPolicyNoise(C.sizeof(L.EmeiPolicyNoise), self.mode, self.seed & (2**64 - 1), self.sigma, p(self.std), p(self.ws),
+                                 p(self.bs), self.log_std_min, self.log_std_max, 0)
+
+    def draws(self, engine, t):
+        """what step t draws for every env of `engine`, obtained from the DEVICE through Engine.sample_candidates (candidate 0
+        under the key seed + t is the noise stream).  Continuous envs: z float32 [N(, act_dim)] = 8 * (the clipped Gaussian candidate
+        with mean 0 and sigma 0.125) — exact: |z| <= 5.77, so 0.125 z never reaches a ctrlrange of +-1 or +-3, and scaling by a power
+        of two is exact.  Discrete envs: (explore, coin) [N] int64, the Bernoulli draws with p = epsilon at t = 0 and p = 0.5 at t = 1."""
+        eng = engine
+        key = self.seed + int(t)
+        if eng.act_dim == 0:
+            nominal = torch.tensor([self.sigma, 0.5], dtype=torch.float32, device=eng.device)[:, None].repeat(1, eng.n_envs).contiguous()
+            d = eng.sample_candidates(2, 1, key, nominal=nominal)
+            return d[0, :, 0], d[1, :, 0]
+        zeros = torch.zeros((1, eng.n_envs) + eng._act_tail, dtype=torch.float32, device=eng.device)
+        return 8.0 * eng.sample_candidates(1, 1, key, nominal=zeros, sigma=0.125)[0, :, 0]
+
+    def scale(self, h):
+        """s [N, n_out] float32 for the rows whose hidden activations (float64 [N, hidden], or the inputs without a hidden layer)
+        are h: the given std, or the log-std head's float32(exp(clamp(l)))"""
+        if self.mode == L.POLICY_NOISE_GAUSS:
+            s = self.std if self.std is not None else torch.full((1,), self.sigma, dtype=torch.float32, device=h.device)
+            return s[None, :].expand(h.shape[0], -1)
+        lq = self.bs.to(torch.float64)[None, :].repeat(h.shape[0], 1)
+        ws = self.ws.to(torch.float64)
+        for j in range(h.shape[1]):
+            lq = lq + ws[None, :, j] * h[:, j:j + 1]
+        lq = torch.clamp(lq, self.log_std_min, self.log_std_max)
+        return torch.exp(lq).to(torch.float32)
 
 
 class PolicyPopulation:

@@ -52,7 +52,10 @@ extern "C" {
  *    layer or affine, evaluated per lane inside the rollout launch: every env on its family's kernel), EMEI_KERNEL_PEND_POLICY /
  *    EMEI_KERNEL_BODY_POLICY / EMEI_KERNEL_BODY_POLICY_RK4;
  *    emei_evaluate_policies (the policy-side counterpart of emei_evaluate_sequences: n_policies stacked struct emei_policy networks,
- *    each scored on every env from the envs' current or given states in one launch; the handle is untouched, no kernel id). */
+ *    each scored on every env from the envs' current or given states in one launch; the handle is untouched, no kernel id);
+ *    emei_rollout_policy_noisy with struct emei_policy_noise (emei_rollout_policy with exploration noise drawn in the lanes: Gaussian
+ *    with a given or a network-head standard deviation on the continuous envs, epsilon-greedy on the discrete ones),
+ *    EMEI_KERNEL_PEND_POLICY_NOISY / EMEI_KERNEL_BODY_POLICY_NOISY / EMEI_KERNEL_BODY_POLICY_NOISY_RK4. */
 #define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
@@ -626,6 +629,63 @@ typedef struct emei_policy {
 EMEI_API int emei_rollout_policy(emei_env* h, int32_t n_steps, const emei_policy* policy, void* actions_out, int action_dtype,
                                  float* obs_out, float* reward_out, uint8_t* done_out, uint32_t flags, void* stream);
 
+/* emei_rollout_policy under a STOCHASTIC behaviour policy, the way every policy dataset of the reference's zoo is sampled
+ * (zoo/main.py:109-122, zoo/util.py:56: agent.predict(obs, deterministic=False)): Gaussian exploration on the continuous envs,
+ * epsilon-greedy on the discrete ones.  The noise is drawn inside the lanes from a counter-based stream and never exists in memory.
+ * std / ws / bs are DEVICE pointers like the weights: read during the launch, not retained, not overlapping any output.
+ *
+ * Semantics (normative).  Everything is emei_rollout_policy's clause list (Observe, Policy, Step), its outputs and the state it leaves
+ * in the handle, with one addition to clause 2.
+ *   Noise words.  Step t of the call, for env i with g = env_index_offset + i, owns the word stream
+ *        W[m] = philox4x32_10(key = seed + t (mod 2^64), counter = (g lo, g hi, 0, m >> 2)).v[m & 3]
+ *      — the stream of candidate k = 0 of the candidate specification above under the key seed + t: a pure function of (seed, t, g),
+ *      independent of the shard, of n_envs, of episodes and of auto-resets.  A planner call (emei_sample_candidates, emei_plan_*,
+ *      emei_mpc_*) given the same key draws candidate 0 of env g from the same words; that coincidence is harmless (the two calls
+ *      consume the words for different purposes, and neither reads the other's results), but distinct seeds keep them independent.
+ *   Continuous envs, EMEI_POLICY_NOISE_GAUSS and EMEI_POLICY_NOISE_GAUSS_HEAD.  For component q, p = q >> 1 and (z0, z1) = the reset
+ *      generator's Box-Muller of (W[2p], W[2p + 1]); z_q = (q & 1) ? z1 : z0 — the normals the candidate specification draws at step 0.
+ *      After the ascending sum that gives y_q one more term is added, last:  y_q = y_q + (double)s_q * (double)z_q  (a product of two
+ *      float32 values, exact in float64).  The output clause (CLIP or TANH, with its NaN handling) then acts on that y_q, unchanged:
+ *      under CLIP Gaussian exploration on a deterministic actor (TD3, DDPG) or a PPO Gaussian, under TANH SAC's squashed Gaussian.
+ *        GAUSS: s_q = std[q], or (float)sigma when std is NULL.  Entries are used as they are; a non-finite entry gives a non-finite
+ *               y_q, which the output clause handles (the call does not fault).
+ *        GAUSS_HEAD: l_q = (double)bs[q]; for j ascending, l_q = l_q + (double)ws[q,j] * (double)h_j, h the hidden activations y_q
+ *               uses (hidden == 0: the inputs x); s_q = (float)exp(fmin(fmax(l_q, (double)log_std_min), (double)log_std_max)), the
+ *               device's float64 exp: this mode is NOT pinned bit for bit, like EMEI_POLICY_OUT_TANH.
+ *   Discrete envs, EMEI_POLICY_NOISE_EPS_GREEDY.  With u(w) = (w >> 8) * 2^-24: explore = u(W[0]) < (float)sigma;
+ *      a = explore ? (u(W[1]) < 0.5f ? 1 : 0) : (y_0 >= 0 ? 1 : 0) — the candidate specification's discrete draws at t = 0 with
+ *      p = epsilon and at t = 1 with p = 0.5.
+ * Consequences.  Replay: emei_rollout(actions_out) reproduces the other outputs bit for bit in every mode.  Chunking: n_steps = a + b
+ * equals a call with (a, seed) followed by one with (b, seed + a), under emei_rollout_policy's observation condition.  Sharding:
+ * results depend on g only.  Stream: the call neither allocates nor synchronises.  With s_q = 0 for all q, or epsilon 0, the actions
+ * equal emei_rollout_policy's as values.
+ * Kernels: pend_policy_rollout_noisy_kernel / body_policy_rollout_noisy_kernel, emei_rollout_policy's kernels with the noisy
+ * evaluation; the action of step t + 1 of the body kernel is computed at the end of step t under the key seed + t + 1.
+ * EMEI_ERR_INVALID before any HIP call, each message naming the argument, in this order: emei_rollout_policy's checks up to and
+ * including policy.reserved; NULL noise; noise.struct_size wrong; unknown noise.mode; noise.reserved != 0; GAUSS with std NULL: sigma
+ * not finite or < 0; EPS_GREEDY: sigma outside [0, 1] or NaN; GAUSS_HEAD: log_std_min > log_std_max or either NaN, then NULL ws or bs;
+ * a NULL handle; emei_rollout_policy's weight, dtype and flag checks; a GAUSS mode on a discrete env or EPS_GREEDY on a continuous
+ * one.  EMEI_ERR_STATE and EMEI_ERR_UNSUPPORTED where emei_rollout_policy gives them. */
+enum emei_policy_noise_mode {
+    EMEI_POLICY_NOISE_GAUSS = 0,       /* continuous envs: a std per action component, given */
+    EMEI_POLICY_NOISE_GAUSS_HEAD = 1,  /* continuous envs: the std from a log-std head next to the output layer (SAC's actor) */
+    EMEI_POLICY_NOISE_EPS_GREEDY = 2   /* discrete envs */
+};
+typedef struct emei_policy_noise {
+    uint32_t struct_size;   /* = sizeof(emei_policy_noise) */
+    int32_t mode;           /* enum emei_policy_noise_mode */
+    uint64_t seed;          /* this call's own key; the handle's reset key is not involved */
+    double sigma;           /* GAUSS with std NULL: the std of every component, finite, >= 0.  EPS_GREEDY: epsilon in [0, 1] */
+    const float* std;       /* GAUSS: [n_out] device floats, or NULL (then sigma) */
+    const float* ws;        /* GAUSS_HEAD: [n_out, hidden] ([n_out, obs_dim] when hidden == 0), laid out as w2 */
+    const float* bs;        /* GAUSS_HEAD: [n_out] */
+    float log_std_min, log_std_max;   /* GAUSS_HEAD: clamp of the head's output (SAC: -20, 2); min <= max, neither NaN */
+    int32_t reserved;       /* 0 */
+} emei_policy_noise;
+EMEI_API int emei_rollout_policy_noisy(emei_env* h, int32_t n_steps, const emei_policy* policy, const emei_policy_noise* noise,
+                                       void* actions_out, int action_dtype, float* obs_out, float* reward_out, uint8_t* done_out,
+                                       uint32_t flags, void* stream);
+
 /* A population of feedback policies scored from the envs' current states in ONE launch, for policy search (evolution strategies and
  * ARS over perturbed policies, CEM over policy weights, population-based training, choosing among checkpoints): the policy-side
  * counterpart of emei_evaluate_sequences.  `stacked` is a struct emei_policy whose pointers each name P = n_policies networks laid end
@@ -688,7 +748,10 @@ enum emei_kernel_id {
     EMEI_KERNEL_BODY_MPC_CEM = 14,           /* body_mpc_cem_kernel<Body, RK4>: emei_mpc_cem on an InvertedDoublePendulum handle */
     EMEI_KERNEL_PEND_POLICY = 15,            /* pend_policy_rollout_kernel<Env>: emei_rollout_policy (it steps the handle, so it reports here) */
     EMEI_KERNEL_BODY_POLICY = 16,            /* body_policy_rollout_kernel<Body, false>: emei_rollout_policy on the body kernels */
-    EMEI_KERNEL_BODY_POLICY_RK4 = 17         /* body_policy_rollout_kernel<Body, true> */
+    EMEI_KERNEL_BODY_POLICY_RK4 = 17,        /* body_policy_rollout_kernel<Body, true> */
+    EMEI_KERNEL_PEND_POLICY_NOISY = 18,      /* pend_policy_rollout_noisy_kernel<Env>: emei_rollout_policy_noisy */
+    EMEI_KERNEL_BODY_POLICY_NOISY = 19,      /* body_policy_rollout_noisy_kernel<Body, false> */
+    EMEI_KERNEL_BODY_POLICY_NOISY_RK4 = 20   /* body_policy_rollout_noisy_kernel<Body, true> */
 };
 EMEI_API int emei_last_rollout_kernel(emei_env* h);
 

@@ -13,8 +13,12 @@ the rounds and the spread (min, max) of either route, and the ratio of the media
 A third figure per shape, `replay_ms`: emei_rollout on the actions the fused call took, from the same start (the same trajectory, the
 actions loaded instead of computed; at aligned shapes on the staged kernels) — what the in-kernel policy costs on top of the env step.
 Shapes: CartPoleSwingUp N = 256 and N = 65 536, HalfCheetahRunning N = 256 and N = 16 384; one hidden layer of 64 units.
+--noise: the exploration noise of emei_rollout_policy_noisy in the same method — per shape the fused NOISY launch (Gaussian std 0.1
+on the continuous envs, epsilon 0.1 on the discrete ones: PolicyNoise), the fused deterministic launch and the per-step loop with the
+same policy and noise objects (policy(obs, noise, t): one sample_candidates launch more per step), alternating inside every round;
+the step count is sized on the noisy launch.  Reported: noisy_ms, fused_ms, loop_ms and the two ratios.
 One JSON line per shape.  Run on the GPU box:
-    python tools/policy_timing.py [--warmup 2] [--repeats 7] [--only INDEX]"""
+    python tools/policy_timing.py [--warmup 2] [--repeats 7] [--only INDEX] [--noise]"""
 import argparse
 import json
 import os
@@ -25,7 +29,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from emei_amd.engine import Engine  # noqa: E402
-from emei_amd.policy import MLPPolicy  # noqa: E402
+from emei_amd.policy import MLPPolicy, PolicyNoise  # noqa: E402
 
 # (env, N, starting T, engine kwargs)
 SHAPES = [
@@ -44,13 +48,13 @@ def make_policy(eng):
     return MLPPolicy(r(n_out, HIDDEN), r(n_out), r(HIDDEN, eng.obs_dim), r(HIDDEN)).bind(eng)
 
 
-def loop_episode(eng, T, policy, outs):
-    """datasets.collect's per-step route, statement for statement, at the Engine level"""
+def loop_episode(eng, T, policy, outs, noise=None):
+    """datasets.collect's per-step route, statement for statement, at the Engine level (noise: the callable draws step t's noise)"""
     next_obs, rew, done = outs
     cur = eng.get_obs().float()
     _, epi = eng.get_counters()
     for t in range(T):
-        a = policy(cur)
+        a = policy(cur) if noise is None else policy(cur, noise, t)
         a = (a.to(torch.float32) if eng.act_dim else a.to(torch.int64)).contiguous()
         eng.step(a, auto_reset=True, out=(next_obs[t], rew[t], done[t]))
         cur = next_obs[t]
@@ -62,11 +66,43 @@ def loop_episode(eng, T, policy, outs):
             cur[idx] = eng.episode_init_obs(idx, epi[idx])
 
 
+def noisy_shape(args, eng, name, N, T, policy, timed):
+    """--noise: one shape, the three routes alternating inside every round"""
+    noise = (PolicyNoise(7, epsilon=0.1) if eng.act_dim == 0 else PolicyNoise(7, std=0.1)).bind(eng)
+    box = {"outs": eng.alloc_outputs(T), "T": T}
+    routes = {
+        "noisy": lambda: eng.rollout_policy(box["T"], policy, auto_reset=True, out=box["outs"], noise=noise),
+        "fused": lambda: eng.rollout_policy(box["T"], policy, auto_reset=True, out=box["outs"]),
+        "loop": lambda: loop_episode(eng, box["T"], policy, box["outs"], noise),
+    }
+    timed(routes["noisy"])  # code objects loaded
+    while timed(routes["noisy"]) < MIN_WINDOW_MS and 2 * box["T"] <= MAX_T:
+        box["T"] *= 2
+        box["outs"] = eng.alloc_outputs(box["T"])
+    kernel = eng.last_kernel()
+    for _ in range(args.warmup):
+        for fn in routes.values():
+            timed(fn)
+    ms = {k: [] for k in routes}
+    for _ in range(args.repeats):
+        for k, fn in routes.items():
+            ms[k].append(timed(fn))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    row = {"env": name, "n_envs": N, "hidden": HIDDEN, "n_steps": box["T"], "repeats": args.repeats, "noise": "eps 0.1" if eng.act_dim == 0 else "std 0.1"}
+    for k in routes:
+        row[k + "_ms"] = round(med[k], 4)
+        row[k + "_ms_min_max"] = [round(min(ms[k]), 4), round(max(ms[k]), 4)]
+    row.update(noisy_over_fused=round(med["noisy"] / med["fused"], 3), loop_over_noisy=round(med["loop"] / med["noisy"], 3),
+               noisy_us_per_step=round(1e3 * med["noisy"] / box["T"], 3), kernel=kernel)
+    print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--only", type=int, default=None, help="index of the one shape to run")
+    ap.add_argument("--noise", action="store_true", help="time emei_rollout_policy_noisy against the deterministic launch and the noisy loop")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("policy_timing.py needs a GPU")
@@ -92,6 +128,10 @@ def main():
             torch.cuda.synchronize()
             return e0.elapsed_time(e1)
 
+        if args.noise:
+            noisy_shape(args, eng, name, N, T, policy, timed)
+            eng.close()
+            continue
         outs = eng.alloc_outputs(T)
         fused = lambda: eng.rollout_policy(T, policy, auto_reset=True, out=outs)
         loop = lambda: loop_episode(eng, T, policy, outs)
