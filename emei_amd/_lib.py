@@ -46,11 +46,14 @@ POLICY_KERNEL_NAMES = {15: "pend_policy_rollout_kernel", 16: "body_policy_rollou
 # ... and those of emei_rollout_policy_noisy, likewise a table of their own
 POLICY_NOISY_KERNEL_NAMES = {18: "pend_policy_rollout_noisy_kernel", 19: "body_policy_rollout_noisy_kernel",
                              20: "body_policy_rollout_noisy_kernel<rk4>"}
+# ... and those of emei_rollout_policy_deep (one kernel per family, with or without noise), likewise
+POLICY_DEEP_KERNEL_NAMES = {21: "pend_policy_rollout_deep_kernel", 22: "body_policy_rollout_deep_kernel",
+                            23: "body_policy_rollout_deep_kernel<rk4>"}
 
 
 def kernel_name(kernel_id):
     """name of an enum emei_kernel_id value (emei_last_rollout_kernel)"""
-    for table in (KERNEL_NAMES, POLICY_KERNEL_NAMES, POLICY_NOISY_KERNEL_NAMES):
+    for table in (KERNEL_NAMES, POLICY_KERNEL_NAMES, POLICY_NOISY_KERNEL_NAMES, POLICY_DEEP_KERNEL_NAMES):
         if kernel_id in table:
             return table[kernel_id]
     raise KeyError(kernel_id)
@@ -67,6 +70,8 @@ POLICY_OUT_CLIP, POLICY_OUT_TANH = 0, 1  # enum emei_policy_out
 KERNEL_PEND_POLICY_NOISY, KERNEL_BODY_POLICY_NOISY, KERNEL_BODY_POLICY_NOISY_RK4 = 18, 19, 20  # emei_rollout_policy_noisy
 POLICY_NOISE_GAUSS, POLICY_NOISE_GAUSS_HEAD, POLICY_NOISE_EPS_GREEDY = 0, 1, 2  # enum emei_policy_noise_mode
 POLICY_MAX_HIDDEN = 1024  # EMEI_POLICY_MAX_HIDDEN
+KERNEL_PEND_POLICY_DEEP, KERNEL_BODY_POLICY_DEEP, KERNEL_BODY_POLICY_DEEP_RK4 = 21, 22, 23  # emei_rollout_policy_deep
+POLICY_DEEP_MAX_HIDDEN = 256  # EMEI_POLICY_DEEP_MAX_HIDDEN
 MPC_MAX_HORIZON = 256  # EMEI_MPC_MAX_HORIZON
 MAX_OBS_PEERS = 8  # EMEI_MAX_OBS_PEERS
 # enum emei_ode_method: `method` of ODE_approximation (base_control.py:133-173), classic control only
@@ -127,6 +132,24 @@ class EmeiPolicy(C.Structure):
         ("b1", C.c_void_p),
         ("w2", C.c_void_p),
         ("b2", C.c_void_p),
+    ]
+
+
+class EmeiPolicyDeep(C.Structure):
+    """struct emei_policy_deep (include/emei_hip.h): two hidden layers; the weights are device pointers."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("hidden1", C.c_int32),
+        ("hidden2", C.c_int32),
+        ("out_mode", C.c_int32),
+        ("w1", C.c_void_p),
+        ("b1", C.c_void_p),
+        ("w2", C.c_void_p),
+        ("b2", C.c_void_p),
+        ("w3", C.c_void_p),
+        ("b3", C.c_void_p),
+        ("reserved", C.c_int64),
     ]
 
 
@@ -194,6 +217,9 @@ SYMBOLS = {
     "emei_rollout_policy_noisy": (C.c_int, [_vp, _i32, C.POINTER(EmeiPolicy), C.POINTER(EmeiPolicyNoise), _vp, C.c_int, _vp, _vp, _vp, _u32,
                                             _vp]),
     "emei_evaluate_policies": (C.c_int, [_vp, _i32, _i32, C.POINTER(EmeiPolicy), _dbl, _vp, _vp, _vp, _vp, _vp]),
+    "emei_rollout_policy_deep": (C.c_int, [_vp, _i32, C.POINTER(EmeiPolicyDeep), C.POINTER(EmeiPolicyNoise), _vp, C.c_int, _vp, _vp, _vp, _u32,
+                                           _vp]),
+    "emei_evaluate_policies_deep": (C.c_int, [_vp, _i32, _i32, C.POINTER(EmeiPolicyDeep), _dbl, _vp, _vp, _vp, _vp, _vp]),
     "emei_compact_done": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emei_get_counters": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emei_episode_init_obs": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),

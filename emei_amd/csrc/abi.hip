@@ -1260,6 +1260,130 @@ extern "C" EMEI_API int emei_evaluate_policies(emei_env* h, int32_t horizon, int
     return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
 }
 
+// ---------------------------------------------------------------------------------------------
+// emei_rollout_policy_deep / emei_evaluate_policies_deep: the policy calls above for struct emei_policy_deep (two hidden layers), on
+// kernels of their own (pend_policy_rollout_deep_kernel / body_policy_rollout_deep_kernel, pend_policy_eval_deep_kernel /
+// body_policy_eval_deep_kernel).  The refusals mirror check_policy_struct / check_policy_weights.
+static int check_policy_deep_struct(const char* fn, const char* arg, const emei_policy_deep* policy) {
+    if (!policy) return fail(EMEI_ERR_INVALID, "%s: null %s", fn, arg);
+    if (policy->struct_size != sizeof(emei_policy_deep))
+        return fail(EMEI_ERR_INVALID, "%s: %s.struct_size=%u != sizeof(emei_policy_deep)=%zu", fn, arg, policy->struct_size,
+                    sizeof(emei_policy_deep));
+    if (policy->hidden1 < 1 || policy->hidden1 > EMEI_POLICY_DEEP_MAX_HIDDEN)
+        return fail(EMEI_ERR_INVALID, "%s: %s.hidden1=%d is outside [1, EMEI_POLICY_DEEP_MAX_HIDDEN=%d]", fn, arg, policy->hidden1,
+                    EMEI_POLICY_DEEP_MAX_HIDDEN);
+    if (policy->hidden2 < 1 || policy->hidden2 > EMEI_POLICY_DEEP_MAX_HIDDEN)
+        return fail(EMEI_ERR_INVALID, "%s: %s.hidden2=%d is outside [1, EMEI_POLICY_DEEP_MAX_HIDDEN=%d]", fn, arg, policy->hidden2,
+                    EMEI_POLICY_DEEP_MAX_HIDDEN);
+    if (policy->out_mode != EMEI_POLICY_OUT_CLIP && policy->out_mode != EMEI_POLICY_OUT_TANH)
+        return fail(EMEI_ERR_INVALID, "%s: unknown %s.out_mode=%d", fn, arg, policy->out_mode);
+    if (policy->reserved != 0) return fail(EMEI_ERR_INVALID, "%s: %s.reserved=%lld must be 0", fn, arg, (long long)policy->reserved);
+    return EMEI_OK;
+}
+static int check_policy_deep_weights(const char* fn, const char* arg, const emei_policy_deep* policy) {
+    const float* const ptr[6] = {policy->w1, policy->b1, policy->w2, policy->b2, policy->w3, policy->b3};
+    static const char* const name[6] = {"w1", "b1", "w2", "b2", "w3", "b3"};
+    for (int k = 0; k < 6; ++k)
+        if (!ptr[k]) return fail(EMEI_ERR_INVALID, "%s: null %s.%s", fn, arg, name[k]);
+    return EMEI_OK;
+}
+static PolicyDeepArgs policy_deep_args(const emei_env* h, const emei_policy_deep* policy) {
+    PolicyDeepArgs pa{};
+    pa.w1 = policy->w1, pa.b1 = policy->b1, pa.w2 = policy->w2, pa.b2 = policy->b2, pa.w3 = policy->w3, pa.b3 = policy->b3;
+    pa.hidden1 = policy->hidden1, pa.hidden2 = policy->hidden2, pa.out_mode = policy->out_mode;
+    ctrl_range(h->cfg.env_id, pa.lo, pa.hi);
+    return pa;
+}
+
+extern "C" EMEI_API int emei_rollout_policy_deep(emei_env* h, int32_t n_steps, const emei_policy_deep* policy, const emei_policy_noise* noise,
+                                                 void* actions_out, int action_dtype, float* obs_out, float* reward_out, uint8_t* done_out,
+                                                 uint32_t flags, void* stream) {
+    const char* fn = "emei_rollout_policy_deep";
+    if (n_steps < 1) return fail(EMEI_ERR_INVALID, "%s: n_steps=%d < 1", fn, n_steps);
+    if (int rc = check_policy_deep_struct(fn, "policy", policy)) return rc;
+    if (noise)
+        if (int rc = check_policy_noise(fn, noise)) return rc;
+    if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = check_policy_deep_weights(fn, "policy", policy)) return rc;
+    if (action_dtype < EMEI_ACT_U8 || action_dtype > EMEI_ACT_F32 || (h->act_dim > 0) != (action_dtype == EMEI_ACT_F32))
+        return fail(EMEI_ERR_INVALID, "%s: action_dtype=%d: actions_out is uint8 / int32 / int64 for the discrete envs, float32 for the "
+                                      "continuous ones", fn, action_dtype);
+    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "%s: unknown flags 0x%x", fn, flags);
+    if (noise && (h->act_dim > 0) == (noise->mode == EMEI_POLICY_NOISE_EPS_GREEDY))
+        return fail(EMEI_ERR_INVALID, "%s: noise.mode=%d: the Gaussian modes are for the continuous envs, EMEI_POLICY_NOISE_EPS_GREEDY for "
+                                      "the discrete ones", fn, noise->mode);
+    EMEI_ON_DEVICE(h, fn);
+    if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    if (h->peers.count > 0)
+        return fail(EMEI_ERR_UNSUPPORTED, "%s: observation peers are set (emei_set_obs_peers), which this kernel does not serve", fn);
+    PolicyDeepArgs pa = policy_deep_args(h, policy);
+    pa.actions_out = actions_out, pa.action_dtype = action_dtype, pa.noisy = noise ? 1 : 0;
+    PolicyNoiseArgs na{};
+    if (noise) {
+        na.seed = noise->seed, na.mode = noise->mode, na.sigma = (float)noise->sigma;
+        if (noise->mode == EMEI_POLICY_NOISE_GAUSS) na.std = noise->std;
+        if (noise->mode == EMEI_POLICY_NOISE_GAUSS_HEAD)
+            na.ws = noise->ws, na.bs = noise->bs, na.log_std_min = noise->log_std_min, na.log_std_max = noise->log_std_max;
+    }
+    int rc;
+    if (!steps_as_body(h->cfg)) {
+        PendLaunch L = pend_base(h, stream);
+        L.op = PEND_OP_POLICY_DEEP;
+        L.action_dtype = action_dtype;
+        L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
+        L.n_steps = n_steps;
+        L.flags = flags;
+        L.policy_deep = pa, L.policy_noise = na;
+        L.selected = &h->last_kernel;
+        rc = pend_launch(L);
+    } else {
+        BodyLaunch L = body_base(h, stream);
+        L.op = BODY_OP_POLICY_DEEP;
+        L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
+        L.n_steps = n_steps;
+        L.flags = flags;
+        L.policy_deep = pa, L.policy_noise = na;
+        L.selected = &h->last_kernel;
+        rc = body_launch(L);
+    }
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+}
+
+extern "C" EMEI_API int emei_evaluate_policies_deep(emei_env* h, int32_t horizon, int32_t n_policies, const emei_policy_deep* stacked,
+                                                    double discount, const double* start_state, double* return_out, int32_t* length_out,
+                                                    float* final_obs_out, void* stream) {
+    const char* fn = "emei_evaluate_policies_deep";
+    if (int rc = check_plan_scalars(fn, horizon, n_policies, discount, "n_policies")) return rc;
+    if (int rc = check_policy_deep_struct(fn, "stacked", stacked)) return rc;
+    if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = check_policy_deep_weights(fn, "stacked", stacked)) return rc;
+    if (!return_out) return fail(EMEI_ERR_INVALID, "%s: null return_out", fn);
+    // one lane per (policy, env) pair with 32-bit indices, one grid dimension of ceil(n_envs / 64) one-wave blocks per policy
+    const int64_t np = h->cfg.n_envs * (int64_t)n_policies;
+    if (np > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs * n_policies = %lld exceeds 2^31 - 1", fn, (long long)np);
+    const int64_t blocks = (h->cfg.n_envs + kWave - 1) / kWave * (int64_t)n_policies;
+    if (blocks > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_policies=%d needs %lld blocks, more than 2^31 - 1", fn, n_policies, (long long)blocks);
+    EMEI_ON_DEVICE(h, fn);
+    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    const PolicyDeepArgs pa = policy_deep_args(h, stacked);  // noisy = 0: the population is scored without exploration noise
+    PlanLaunch p;
+    p.mode = PLAN_GIVEN, p.start_rows = start_state, p.n_candidates = n_policies, p.discount = discount;
+    p.return_out = return_out, p.length_out = length_out;
+    int rc;
+    if (!steps_as_body(h->cfg)) {
+        PendLaunch L = pend_base(h, stream);
+        L.op = PEND_OP_POLICY_EVAL_DEEP, L.plan = p, L.policy_deep = pa;
+        L.n_steps = horizon, L.obs_out = final_obs_out;
+        rc = pend_launch(L);
+    } else {
+        BodyLaunch L = body_base(h, stream);
+        L.op = BODY_OP_POLICY_EVAL_DEEP, L.plan = p, L.policy_deep = pa;
+        L.n_steps = horizon, L.obs_out = final_obs_out;
+        rc = body_launch(L);
+    }
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+}
+
 extern "C" EMEI_API int emei_compact_done(emei_env* h, int32_t* idx_out, int32_t* count_out, void* stream) {
     if (!h || !idx_out || !count_out) return fail(EMEI_ERR_INVALID, "emei_compact_done: null argument");
     EMEI_ON_DEVICE(h, "emei_compact_done");

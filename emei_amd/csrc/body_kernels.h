@@ -170,7 +170,9 @@ enum BodyOp { BODY_OP_ROLLOUT = 0, BODY_OP_RESET, BODY_OP_GET_OBS, BODY_OP_INIT_
               BODY_OP_MPC_CEM /* emei_mpc_cem: body_mpc_cem_kernel (Body::kFusedMpc) */,
               BODY_OP_POLICY /* emei_rollout_policy: body_policy_rollout_kernel */,
               BODY_OP_POLICY_EVAL /* emei_evaluate_policies: body_policy_eval_kernel */,
-              BODY_OP_POLICY_NOISY /* emei_rollout_policy_noisy: body_policy_rollout_noisy_kernel */ };
+              BODY_OP_POLICY_NOISY /* emei_rollout_policy_noisy: body_policy_rollout_noisy_kernel */,
+              BODY_OP_POLICY_DEEP /* emei_rollout_policy_deep: body_policy_rollout_deep_kernel */,
+              BODY_OP_POLICY_EVAL_DEEP /* emei_evaluate_policies_deep: body_policy_eval_deep_kernel */ };
 
 // What BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM take beyond the base descriptor: n_steps control steps of the planner with plan.n_candidates
 // candidates over `horizon` steps under plan.discount; plan.cand carries the call's seed, sigma and the ctrlrange (its nominal is
@@ -232,6 +234,9 @@ struct BodyLaunch {
     PolicyArgs policy = {};  // BODY_OP_POLICY: BODY_OP_ROLLOUT's fields without `actions`; weights, ctrlrange and actions_out (float32)
                              // BODY_OP_POLICY_EVAL: the STACKED weights (member p at p * its size), with `plan` as PLAN_GIVEN takes it:
                              // n_candidates = the number of policies, return_out / length_out [P, n]; obs_out = final_obs [P, n, NO] or null
+    PolicyDeepArgs policy_deep = {};  // BODY_OP_POLICY_DEEP: BODY_OP_POLICY_NOISY's fields with the two-hidden-layer network here
+                                      // (policy_deep.noisy: whether `policy_noise` is the call's noise or unused);
+                                      // BODY_OP_POLICY_EVAL_DEEP: BODY_OP_POLICY_EVAL's fields with the STACKED networks here
 };
 int body_launch(const BodyLaunch& L);  // body_dispatch.hip
 
@@ -875,6 +880,153 @@ __global__ void __launch_bounds__(rollout_block<Body>()) __attribute__((amdgpu_w
     if (lane == 0 && active) a.done_mask[i / kWave] = mk;
 }
 
+// emei_rollout_policy_deep: body_policy_rollout_noisy_kernel's loop under the network with two hidden layers
+// (emei_device.h:policy_eval_deep_t; the noise is that function's wave-uniform switch pol.noisy, so this one kernel serves the call
+// with and without it).  ONE-WAVE blocks for every body (block b = env wave b, the wave-mates of the one-layer kernels): the
+// block's dynamic LDS is the wave's h1 tile, behind the observation staging, the {sin,cos} table and the solver's slots.
+template <class Body, bool RK4>
+__global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(Body::kMinWavesPerEU)))
+    body_policy_rollout_deep_kernel(const BodyArgs<Body> a, const PolicyDeepArgs pol, const PolicyNoiseArgs nz) {
+    using R = typename Body::real;
+    constexpr int NS = Body::NS, NO = Body::NO, NA = Body::NA;
+    constexpr int kObsVec = (kWave * NO + 3) / 4;  // 16-byte vectors per wave block
+    constexpr int kObsIt = (kObsVec + kWave - 1) / kWave;
+    extern __shared__ __attribute__((aligned(16))) float4 deep_h1_s[];
+    __shared__ __attribute__((aligned(16))) float obs_s[kObsIt * kWave * 4];
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table<kWave>(trig_s, a.trig);  // every thread reaches the barrier: inactive lanes stay in the kernel
+    TrigCtx trig;
+    trig.tab = trig_s;
+    if constexpr (Body::kScratchPerLane > 0) {
+        __shared__ __attribute__((aligned(16))) R scratch_s[Body::kScratchPerLane * kWave];
+        trig.scratch = scratch_s;
+    }
+    trig.scratch_stride = kWave;
+    trig.cap_hits = a.cap_hits;
+    const int lane = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int64_t n = a.n;
+    const int64_t i0 = i - lane;                             // first env of this wave
+    const int wave_envs = (int)min((int64_t)kWave, n - i0);  // ragged last wave
+    const bool active = i < n;
+
+    R s[NS];
+    int32_t steps = 0;
+    uint32_t episode = 0;
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = a.state[(int64_t)k * n + i];
+        steps = a.steps[i];
+        episode = a.episode[i];
+    } else {
+        Body::park(s);  // see body_rollout_kernel
+    }
+    const bool auto_reset = (a.flags & EMEI_FLAG_AUTO_RESET) != 0;
+    const bool obs_noise = a.noise.obs_on != 0;
+    uint32_t done = 0;
+    R spare[Body::kSpareReset ? NS : 1];
+    bool have_spare = false;
+
+    // the float32 observation of the state, as emei_get_obs / emei_episode_init_obs round it
+    auto observe = [&](float (&x)[NO]) __attribute__((always_inline)) {
+        double od[NO];
+        Body::obs_of(s, od, a.m);
+#pragma unroll
+        for (int k = 0; k < NO; ++k) x[k] = (float)od[k];
+    };
+    const uint64_t g = a.env_offset + (uint64_t)i;  // the noise words are the global env index's
+    float act[NA];
+    {
+        float x[NO];
+        observe(x);
+        policy_eval_deep_t<NO, NA, false>(pol, nz, nz.seed, g, x, act, deep_h1_s, lane);
+    }
+    for (int t = 0; t < a.n_steps; ++t) {
+        R ctrl[NA];
+#pragma unroll
+        for (int k = 0; k < NA; ++k) ctrl[k] = active ? (R)act[k] : R(0);
+        if (pol.actions_out && active) {
+            float* dst = (float*)pol.actions_out + ((int64_t)t * n + i) * NA;
+#pragma unroll
+            for (int k = 0; k < NA; ++k) dst[k] = act[k];
+        }
+
+        R pre[NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) pre[k] = s[k];
+        typename Body::Warm warm{};  // per env-step, as body_rollout_kernel
+        for (int k = 0; k < a.freq_rate; ++k) {  // mujoco_env.py:91-104
+            body_substep<Body, RK4>(s, ctrl, a.m, a.semi != 0, trig, warm);
+            if (obs_noise)
+                gauss_state<R, NS, false>(s, a.seed ^ kObsNoiseKey, a.env_offset + (uint64_t)i, episode,
+                                          ((uint32_t)steps * (uint32_t)a.freq_rate + (uint32_t)k) * (uint32_t)((NS + 3) / 4),
+                                          a.noise.obs, a.noise.shared != 0);
+        }
+        float o[NO];
+        R rew;
+        bool term;
+        Body::outputs(s, pre, ctrl, a.m, a.freq_rate, o, rew, term, trig);
+        ++steps;
+        const bool trunc = (a.max_episode_steps > 0) & (steps >= a.max_episode_steps);
+        done = active ? ((term ? EMEI_DONE_TERMINAL : 0u) | (trunc ? EMEI_DONE_TRUNCATED : 0u)) : 0u;
+
+        if (a.obs_out) {  // lane-wise into LDS, linear out
+            float* mine = &obs_s[lane * NO];
+#pragma unroll
+            for (int k = 0; k < NO; ++k) mine[k] = o[k];
+            wave_lds_fence();
+            float* dst = a.obs_out + ((int64_t)t * n + i0) * NO;
+            if (wave_envs == kWave && (((uintptr_t)dst) & 15u) == 0) {
+#pragma unroll
+                for (int c = 0; c < kObsIt; ++c) {
+                    const int vec = c * kWave + lane;
+                    if (vec < kObsVec) store_body_out<Body::kStreamOutputs>((float4*)dst + vec, ((const float4*)obs_s)[vec]);
+                }
+            } else {
+                for (int e = lane; e < wave_envs * NO; e += kWave) dst[e] = obs_s[e];
+            }
+            wave_lds_fence();
+        }
+        if (active) {
+            if (a.reward_out) store_body_out<Body::kStreamOutputs>(a.reward_out + (int64_t)t * n + i, (float)rew);
+            if (a.done_out) store_body_out<Body::kStreamOutputs>(a.done_out + (int64_t)t * n + i, (uint8_t)done);
+        }
+        if (__builtin_expect(auto_reset && __ballot(done != 0) != 0ull, 0)) {
+            if constexpr (Body::kSpareReset) {
+                if (__ballot((done != 0) & !have_spare) != 0ull) {
+                    if (!have_spare) {
+                        body_init<Body>(spare, a.seed, a.env_offset + (uint64_t)i, episode + 1u, a.noise);
+                        have_spare = true;
+                    }
+                }
+                if (done != 0) {
+                    ++episode;
+                    steps = 0;
+#pragma unroll
+                    for (int k = 0; k < NS; ++k) s[k] = spare[k];
+                    have_spare = false;
+                    observe(o);
+                }
+            } else if (done != 0) {  // episodes only end by TimeLimit, for all lanes at once
+                ++episode;
+                steps = 0;
+                body_init<Body>(s, a.seed, a.env_offset + (uint64_t)i, episode, a.noise);
+                observe(o);
+            }
+        }
+        if (t + 1 < a.n_steps)  // wave-uniform: the next step's action
+            policy_eval_deep_t<NO, NA, false>(pol, nz, nz.seed + (uint64_t)t + 1u, g, o, act, deep_h1_s, lane);
+    }
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) a.state[(int64_t)k * n + i] = s[k];
+        a.steps[i] = steps;
+        a.episode[i] = episode;
+    }
+    unsigned long long mk = __ballot(done != 0);
+    if (lane == 0 && active) a.done_mask[i / kWave] = mk;
+}
+
 template <class Body>
 __global__ void __launch_bounds__(kBlock)
     body_reset_kernel(typename Body::real* state, int32_t* steps, uint32_t* episode, int64_t n, uint64_t seed,
@@ -1181,6 +1333,94 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
+// emei_evaluate_policies_deep for the bodies: body_policy_eval_kernel's loop under the network with two hidden layers, as ONE-WAVE
+// blocks (the block's dynamic LDS is the wave's h1 tile): with env_waves = ceil(n_envs / 64), block b serves policy p = b / env_waves
+// and env wave b % env_waves, so p is still scalar, member p's offset weight bases stay wave-uniform, and wave w of a policy holds
+// envs 64 w .. 64 w + 63 as in the policy rollouts.
+template <class Body, bool RK4>
+__global__ void __launch_bounds__(kWave)
+    body_policy_eval_deep_kernel(const typename Body::real* state, const double* start_rows, int64_t n_envs, uint32_t env_waves,
+                                 int32_t horizon, double discount, int freq_rate, int semi, typename Body::Model m,
+                                 const SinCosEntry* trig_tab, unsigned long long* cap_hits, const PolicyDeepArgs stacked,
+                                 double* ret_out, int32_t* len_out, float* final_obs) {
+    using R = typename Body::real;
+    constexpr int NS = Body::NS, NO = Body::NO, NA = Body::NA;
+    extern __shared__ __attribute__((aligned(16))) float4 deep_h1_s[];
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table<kWave>(trig_s, trig_tab);  // every thread reaches the barrier
+    TrigCtx trig;
+    trig.tab = trig_s;
+    if constexpr (Body::kScratchPerLane > 0) {
+        __shared__ __attribute__((aligned(16))) R scratch_s[Body::kScratchPerLane * kWave];
+        trig.scratch = scratch_s;
+    }
+    trig.scratch_stride = kWave;
+    trig.cap_hits = cap_hits;
+    const int lane = threadIdx.x;
+    const uint32_t pi = blockIdx.x / env_waves;  // the block's policy: scalar
+    const int64_t i_raw = (int64_t)(blockIdx.x - pi * env_waves) * kWave + threadIdx.x;
+    const bool active = i_raw < n_envs;
+    const int64_t i = active ? i_raw : 0;  // no divergent branch around the loads: see body_plan_kernel
+    const int64_t j = (int64_t)pi * n_envs + i;
+    PolicyDeepArgs pol = stacked;  // member pi of the population: n_out = NA
+    pol.w1 += (int64_t)pi * pol.hidden1 * NO, pol.b1 += (int64_t)pi * pol.hidden1;
+    pol.w2 += (int64_t)pi * pol.hidden2 * pol.hidden1, pol.b2 += (int64_t)pi * pol.hidden2;
+    pol.w3 += (int64_t)pi * NA * pol.hidden2, pol.b3 += (int64_t)pi * NA;
+    const PolicyNoiseArgs none{};  // pol.noisy == 0: never read
+
+    R s[NS], parked[NS];
+    if (start_rows) {  // wave-uniform; the caller's float64 rows are narrowed as emei_set_state narrows them (util_kernels.hip)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = (R)start_rows[i * NS + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = state[(int64_t)k * n_envs + i];
+    }
+    Body::park(parked);  // as body_rollout_kernel's padding lanes
+#pragma unroll
+    for (int k = 0; k < NS; ++k) s[k] = active ? s[k] : parked[k];
+    float act[NA];
+    {  // x_0: the float32 observation of the state, as emei_get_obs rounds it
+        double od[NO];
+        Body::obs_of(s, od, m);
+        float x[NO];
+#pragma unroll
+        for (int k = 0; k < NO; ++k) x[k] = (float)od[k];
+        policy_eval_deep_t<NO, NA, false>(pol, none, 0, 0, x, act, deep_h1_s, lane);
+    }
+    double ret = 0.0, g = 1.0;
+    bool live = active;
+    for (int t = 0; t < horizon; ++t) {
+        R ctrl[NA];  // padding lanes: zero, as the rollout's staging gives them
+#pragma unroll
+        for (int k = 0; k < NA; ++k) ctrl[k] = active ? (R)act[k] : R(0);
+        R pre[NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) pre[k] = s[k];
+        typename Body::Warm warm{};
+        for (int k = 0; k < freq_rate; ++k) body_substep<Body, RK4>(s, ctrl, m, semi != 0, trig, warm);
+        float o[NO];
+        R rew;
+        bool term;
+        Body::outputs(s, pre, ctrl, m, freq_rate, o, rew, term, trig);
+        if (live) {
+            ret = ret + g * (double)(float)rew;
+            g = g * discount;
+            if (term || t == horizon - 1) {  // the lane's last counted step
+                live = false;
+                ret_out[j] = ret;
+                if (len_out) len_out[j] = t + 1;
+                if (final_obs) {
+#pragma unroll
+                    for (int k = 0; k < NO; ++k) final_obs[j * NO + k] = o[k];
+                }
+            }
+        }
+        if (__ballot(live) == 0ull) break;  // wave-uniform
+        policy_eval_deep_t<NO, NA, false>(pol, none, 0, 0, o, act, deep_h1_s, lane);  // wave-uniform: the next step's action
+    }
+}
+
 // the one launch of body_plan_kernel: DRAWN kernels read no actions and write no lengths or final observations, and only KEEP
 // gives them a return_out; one lane per candidate, n * n_candidates < 2^31 (checked in abi.hip)
 template <class Body, bool RK4, bool DRAWN, bool KEEP, class Spec>
@@ -1276,6 +1516,50 @@ static int launch_body(const BodyLaunch& L) {
                 if (rk4) hipLaunchKernelGGL((body_policy_rollout_kernel<Body, true>), rgrid, blk, 0, L.stream, a, L.policy);
                 else hipLaunchKernelGGL((body_policy_rollout_kernel<Body, false>), rgrid, blk, 0, L.stream, a, L.policy);
                 if (L.selected) *L.selected = rk4 ? EMEI_KERNEL_BODY_POLICY_RK4 : EMEI_KERNEL_BODY_POLICY;
+            }
+            break;
+        }
+        case BODY_OP_POLICY_DEEP: {  // one piece, ONE-WAVE blocks for every body: block b = env wave b, its dynamic LDS the h1 tile
+            const bool rk4 = L.integrator == EMEI_INTEG_RK4;
+            const dim3 wgrid((unsigned)((L.n + kWave - 1) / kWave));
+            BodyArgs<Body> a;
+            a.state = (R*)L.state, a.steps = L.steps, a.episode = L.episode, a.done_mask = L.done_mask;
+            a.actions = nullptr, a.obs_out = L.obs_out, a.reward_out = L.reward_out, a.done_out = L.done_out;
+            a.n = L.n, a.n_steps = L.n_steps, a.freq_rate = L.freq_rate, a.max_episode_steps = L.max_episode_steps;
+            a.flags = L.flags, a.seed = L.seed, a.env_offset = L.env_offset, a.m = m;
+            a.semi = L.integrator == EMEI_INTEG_SEMI_IMPLICIT, a.noise = NoiseArgs<Body::NS>(L.noise);
+            a.trig = (const SinCosEntry*)L.trig;
+            a.cap_hits = L.cap_hits;
+            a.work = nullptr, a.chunk_steps = 0, a.n_waves = wgrid.x, a.n_items = 0;
+            const uint32_t tile = policy_deep_tile_bytes(L.policy_deep.hidden1);
+            if (rk4) {
+                if (int rc = policy_deep_lds_opt_in<body_policy_rollout_deep_kernel<Body, true>>()) return rc;
+                hipLaunchKernelGGL((body_policy_rollout_deep_kernel<Body, true>), wgrid, dim3(kWave), tile, L.stream, a, L.policy_deep,
+                                   L.policy_noise);
+            } else {
+                if (int rc = policy_deep_lds_opt_in<body_policy_rollout_deep_kernel<Body, false>>()) return rc;
+                hipLaunchKernelGGL((body_policy_rollout_deep_kernel<Body, false>), wgrid, dim3(kWave), tile, L.stream, a, L.policy_deep,
+                                   L.policy_noise);
+            }
+            if (L.selected) *L.selected = rk4 ? EMEI_KERNEL_BODY_POLICY_DEEP_RK4 : EMEI_KERNEL_BODY_POLICY_DEEP;
+            break;
+        }
+        case BODY_OP_POLICY_EVAL_DEEP: {  // block b = (policy b / env waves, env wave b % env waves); abi.hip bounds the grid
+            const PlanLaunch& P = L.plan;
+            const unsigned env_waves = (unsigned)((L.n + kWave - 1) / kWave);
+            const dim3 egrid(env_waves * (unsigned)P.n_candidates);
+            const int semi = (int)(L.integrator == EMEI_INTEG_SEMI_IMPLICIT);
+            const uint32_t tile = policy_deep_tile_bytes(L.policy_deep.hidden1);
+            if (L.integrator == EMEI_INTEG_RK4) {
+                if (int rc = policy_deep_lds_opt_in<body_policy_eval_deep_kernel<Body, true>>()) return rc;
+                hipLaunchKernelGGL((body_policy_eval_deep_kernel<Body, true>), egrid, dim3(kWave), tile, L.stream, (const R*)L.state,
+                                   P.start_rows, L.n, env_waves, L.n_steps, P.discount, L.freq_rate, 0, m, (const SinCosEntry*)L.trig,
+                                   L.cap_hits, L.policy_deep, P.return_out, P.length_out, L.obs_out);
+            } else {
+                if (int rc = policy_deep_lds_opt_in<body_policy_eval_deep_kernel<Body, false>>()) return rc;
+                hipLaunchKernelGGL((body_policy_eval_deep_kernel<Body, false>), egrid, dim3(kWave), tile, L.stream, (const R*)L.state,
+                                   P.start_rows, L.n, env_waves, L.n_steps, P.discount, L.freq_rate, semi, m, (const SinCosEntry*)L.trig,
+                                   L.cap_hits, L.policy_deep, P.return_out, P.length_out, L.obs_out);
             }
             break;
         }

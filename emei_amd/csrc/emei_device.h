@@ -849,6 +849,160 @@ __device__ __forceinline__ void policy_eval(const PolicyArgs& pa, const float (&
 }
 
 // ---------------------------------------------------------------------------------------------
+// emei_rollout_policy_deep / emei_evaluate_policies_deep: the network with TWO ReLU hidden layers (the normative text:
+// include/emei_hip.h).  Kernel-argument form of struct emei_policy_deep plus what the kernels need with it; the noise of the call
+// travels in PolicyNoiseArgs as for the one-layer kernels and is consulted only when `noisy` is set (wave-uniform: ONE deep rollout
+// kernel per family serves both emei_rollout_policy's and emei_rollout_policy_noisy's semantics).
+struct PolicyDeepArgs {
+    const float* w1;  // [hidden1, NO]
+    const float* b1;  // [hidden1]
+    const float* w2;  // [hidden2, hidden1]
+    const float* b2;  // [hidden2]
+    const float* w3;  // [n_out, hidden2]
+    const float* b3;  // [n_out]
+    void* actions_out;  // [n_steps, n(, NA)] in action_dtype, or null
+    int32_t hidden1, hidden2, out_mode, action_dtype, noisy;
+    float lo, hi;  // the env's ctrlrange (continuous envs)
+};
+// Where h1 lives.  The second layer needs all of h1 for every unit of h2, at a runtime width: registers cannot be indexed at run
+// time and a per-lane array would go to scratch, so the wave keeps h1 in LDS — float32 (the specification has already rounded it),
+// lane-minor in groups of four units: unit j of lane l is float (j >> 2) * 256 + l * 4 + (j & 3) of the wave's tile.  A group is one
+// float4 per lane, so the wave reads and writes 1 KiB contiguous per ds_read_b128 / ds_write_b128: conflict-free.  The tile is
+// DYNAMIC LDS (policy_deep_tile_bytes(hidden1) at launch, 64 KiB at the cap), carved behind the kernel's static arrays, so a small
+// network does not pay the cap's occupancy.  The deep kernels are launched as one-wave blocks: the tile is the block's, each lane
+// reads back only what it wrote, and no barrier is needed.
+__host__ __device__ constexpr uint32_t policy_deep_tile_bytes(int hidden1) { return (uint32_t)((hidden1 + 3) / 4) * kWave * 16u; }
+constexpr int kDeepBlockI = 4;  // units of h2 whose float64 accumulators share one read of h1
+
+// One evaluation for one lane: x[NO] -> act[NA].  `tile` is the wave's h1 tile, `lane` the lane's index in the wave.
+// First layer: four units at a time (indices clamped to hidden1 - 1 in the last group, whose surplus entries nobody reads), one
+// float4 into the tile.  Second layer: kDeepBlockI accumulators z_i over ascending j, each float4 of h1 feeding 4 * kDeepBlockI
+// fma()s (without the blocking every fma() would wait for its own 256 B per wave from the LDS); the indices of the last block are
+// clamped to hidden2 - 1 and its surplus results dropped.  h2_i then joins y (and the log-std head's l) in ascending i, so nothing
+// of size hidden2 is ever live.  Every accumulator adds its terms in ascending index order with fma() on exact products: the
+// specification's sums, bit for bit.  The weights are wave-uniform scalar loads, as policy_eval_t's.
+template <int NO, int NA, bool DISCRETE>
+__device__ __forceinline__ void policy_eval_deep_t(const PolicyDeepArgs& pa, const PolicyNoiseArgs& nz, uint64_t key, uint64_t g,
+                                                   const float (&x)[NO], float (&act)[NA], float4* tile, int lane) {
+    const PolicyWeights w1 = (PolicyWeights)pa.w1, b1 = (PolicyWeights)pa.b1, w2 = (PolicyWeights)pa.w2, b2 = (PolicyWeights)pa.b2;
+    const PolicyWeights w3 = (PolicyWeights)pa.w3, b3 = (PolicyWeights)pa.b3;
+    const int h1n = pa.hidden1, h2n = pa.hidden2;  // wave-uniform, as every index below
+    const bool noisy = pa.noisy != 0;              // wave-uniform
+    const PolicyWeights ws = (PolicyWeights)nz.ws, bs = (PolicyWeights)nz.bs;
+    const bool head = !DISCRETE && noisy && nz.mode == EMEI_POLICY_NOISE_GAUSS_HEAD;  // wave-uniform
+    const int groups = (h1n + 3) >> 2;
+    float4* mine = tile + lane;
+
+    for (int jg = 0; jg < groups; ++jg) {
+        float hv[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int j = min(4 * jg + c, h1n - 1);
+            double z = (double)b1[j];
+#pragma unroll
+            for (int k = 0; k < NO; ++k) z = fma((double)w1[j * NO + k], (double)x[k], z);
+            const float hj = (float)z;
+            hv[c] = hj > 0.f ? hj : 0.f;  // NaN -> 0
+        }
+        mine[jg * kWave] = make_float4(hv[0], hv[1], hv[2], hv[3]);
+    }
+    wave_lds_fence();  // the lane reads back its own stores: program order in the LDS queue, the fence is for the compiler
+
+    [[maybe_unused]] double l[NA];
+    double y[NA];
+#pragma unroll
+    for (int q = 0; q < NA; ++q) {
+        y[q] = (double)b3[q];
+        if constexpr (!DISCRETE) l[q] = head ? (double)bs[q] : 0.0;
+    }
+    const int full = h1n >> 2;  // groups all four units of which exist
+    for (int i0 = 0; i0 < h2n; i0 += kDeepBlockI) {
+        int row[kDeepBlockI];
+        double z[kDeepBlockI];
+#pragma unroll
+        for (int b = 0; b < kDeepBlockI; ++b) {
+            const int i = min(i0 + b, h2n - 1);
+            row[b] = i * h1n;
+            z[b] = (double)b2[i];
+        }
+        for (int jg = 0; jg < full; ++jg) {
+            const float4 v = mine[jg * kWave];
+            const double hd[4] = {(double)v.x, (double)v.y, (double)v.z, (double)v.w};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+#pragma unroll
+                for (int b = 0; b < kDeepBlockI; ++b) z[b] = fma((double)w2[row[b] + 4 * jg + c], hd[c], z[b]);
+            }
+        }
+        if (full < groups) {  // the ragged last group: wave-uniform
+            const float4 v = mine[full * kWave];
+            const double hd[4] = {(double)v.x, (double)v.y, (double)v.z, (double)v.w};
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (4 * full + c < h1n) {
+#pragma unroll
+                    for (int b = 0; b < kDeepBlockI; ++b) z[b] = fma((double)w2[row[b] + 4 * full + c], hd[c], z[b]);
+                }
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < kDeepBlockI; ++b) {
+            const int i = i0 + b;
+            if (i < h2n) {  // wave-uniform
+                float hi2 = (float)z[b];
+                hi2 = hi2 > 0.f ? hi2 : 0.f;  // NaN -> 0
+#pragma unroll
+                for (int q = 0; q < NA; ++q) y[q] = fma((double)w3[q * h2n + i], (double)hi2, y[q]);
+                if constexpr (!DISCRETE) {
+                    if (head) {
+#pragma unroll
+                        for (int q = 0; q < NA; ++q) l[q] = fma((double)ws[q * h2n + i], (double)hi2, l[q]);
+                    }
+                }
+            }
+        }
+    }
+    wave_lds_fence();  // the next evaluation's stores stay behind these reads
+
+    if constexpr (DISCRETE) {
+        bool one = y[0] >= 0.0;  // NaN -> 0
+        if (noisy) {
+            CandidateWords cw(key, g, 0u);
+            const bool explore = u01(cw.word(0u)) < nz.sigma, coin = u01(cw.word(1u)) < 0.5f;
+            one = explore ? coin : one;
+        }
+        act[0] = one ? 1.f : 0.f;
+        return;
+    } else {
+        if (noisy) {
+            CandidateWords cw(key, g, 0u);
+            const PolicyWeights sd = (PolicyWeights)nz.std;
+#pragma unroll
+            for (int p = 0; p < (NA + 1) / 2; ++p) {  // the pair (W[2p], W[2p + 1]) lies inside one Philox block
+                float zn[2];
+                const uint32_t wa = cw.word(2u * p), wb = cw.word(2u * p + 1u);
+                boxmuller(wa, wb, zn[0], zn[1]);
+#pragma unroll
+                for (int q = 2 * p; q < 2 * p + 2 && q < NA; ++q) {
+                    float sq;
+                    if (head) sq = (float)exp(fmin(fmax(l[q], (double)nz.log_std_min), (double)nz.log_std_max));
+                    else sq = sd ? sd[q] : nz.sigma;
+                    y[q] = fma((double)sq, (double)zn[q & 1], y[q]);  // the last term of the sum
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < NA; ++q) {
+            if (pa.out_mode == EMEI_POLICY_OUT_TANH) {  // wave-uniform
+                act[q] = (float)(0.5 * ((double)pa.hi + (double)pa.lo) + 0.5 * ((double)pa.hi - (double)pa.lo) * tanh(y[q]));
+            } else {
+                act[q] = fminf(fmaxf((float)y[q], pa.lo), pa.hi);  // NaN -> lo
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // action loads: dtype is wave-uniform, so the switch is a scalar branch
 __device__ __forceinline__ int load_discrete_action(const void* p, int dtype, int64_t idx) {
     switch (dtype) {

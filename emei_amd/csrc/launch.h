@@ -7,7 +7,7 @@
 
 namespace emei {
 
-enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC, PEND_OP_MPC_CEM, PEND_OP_POLICY, PEND_OP_POLICY_EVAL, PEND_OP_POLICY_NOISY };
+enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC, PEND_OP_MPC_CEM, PEND_OP_POLICY, PEND_OP_POLICY_EVAL, PEND_OP_POLICY_NOISY, PEND_OP_POLICY_DEEP, PEND_OP_POLICY_EVAL_DEEP };
 
 // emei_set_obs_peers: the gathered buffers the staged rollout kernel also writes every observation row to
 struct ObsPeers {
@@ -94,7 +94,27 @@ struct PendLaunch {
     // PEND_OP_POLICY_EVAL (emei_evaluate_policies): `policy` holds the STACKED weights (member p at p * its size; actions_out unused),
     // `plan` what PLAN_GIVEN takes with n_candidates = the number of policies and return_out / length_out [P, n] policy-major;
     // n_steps = the horizon, obs_out = final_obs [P, n, 4] or null
+    // PEND_OP_POLICY_DEEP (emei_rollout_policy_deep): PEND_OP_POLICY_NOISY's fields with the two-hidden-layer network in `policy_deep`
+    // (policy_deep.noisy: whether `policy_noise` is the call's noise or unused)
+    // PEND_OP_POLICY_EVAL_DEEP (emei_evaluate_policies_deep): PEND_OP_POLICY_EVAL's fields with the STACKED networks in `policy_deep`
+    PolicyDeepArgs policy_deep = {};
 };
+
+// The deep policy kernels keep h1 in dynamic LDS (emei_device.h:policy_deep_tile_bytes, up to 64 KiB): the opt-in HIP wants of a
+// kernel that asks for a large dynamic segment, made once per kernel and device for the cap.  Host only; no stream is involved.
+template <auto Kernel>
+inline int policy_deep_lds_opt_in() {
+    constexpr int kMaxDevices = 64;
+    static bool done[kMaxDevices] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return EMEI_ERR_HIP;
+    if (dev >= 0 && dev < kMaxDevices && done[dev]) return EMEI_OK;
+    if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)policy_deep_tile_bytes(EMEI_POLICY_DEEP_MAX_HIDDEN)) != hipSuccess)
+        return EMEI_ERR_HIP;
+    if (dev >= 0 && dev < kMaxDevices) done[dev] = true;
+    return EMEI_OK;
+}
 
 // pendulum_kernels.hip
 int pend_launch(const PendLaunch& L);

@@ -296,6 +296,79 @@ __global__ void __launch_bounds__(kBlock) pend_policy_rollout_noisy_kernel(const
     if ((threadIdx.x & (kWave - 1)) == 0) a.done_mask[i / kWave] = m;
 }
 
+// emei_rollout_policy_deep: pend_policy_rollout_noisy_kernel's loop under the network with two hidden layers
+// (emei_device.h:policy_eval_deep_t; the noise is that function's wave-uniform switch pol.noisy, so this one kernel serves the call
+// with and without it).  ONE-WAVE blocks: block b is env wave b, and the block's dynamic LDS is the wave's h1 tile.
+template <class Env>
+__global__ void __launch_bounds__(kWave) pend_policy_rollout_deep_kernel(const RolloutArgs<Env> a, const PolicyDeepArgs pol,
+                                                                         const PolicyNoiseArgs nz) {
+    using R = typename Env::real;
+    using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
+    extern __shared__ __attribute__((aligned(16))) float4 deep_h1_s[];
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table<kWave>(trig_s, a.trig, Env::trig_rot_c(), Env::trig_rot_s());
+    const int64_t i = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    if (i >= a.n) return;
+    const int64_t n = a.n;
+    const uint32_t li = (uint32_t)i;  // n_envs < 2^31 (checked in emei_create)
+
+    R s[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = a.state[k * n + i];
+    int32_t steps = a.steps[i];
+    uint32_t episode = a.episode[i];
+    typename Env::Carry c;
+    trig_ctx_init(c.trig, trig_s);
+    Env::prime(s, c, a.p);
+
+    const bool auto_reset = (a.flags & EMEI_FLAG_AUTO_RESET) != 0;
+    float x[4];
+    {
+        R o[4];
+        Env::obs_of(s, o);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = (float)o[k];
+    }
+    uint32_t done = 0;
+    for (int t = 0; t < a.n_steps; ++t) {
+        float av[1];
+        policy_eval_deep_t<4, 1, Env::kDiscrete>(pol, nz, nz.seed + (uint64_t)t, a.env_offset + (uint64_t)i, x, av, deep_h1_s,
+                                                 (int)threadIdx.x);
+        const int64_t row = (int64_t)t * n;  // uniform (scalar) row base + 32-bit lane index
+        if (pol.actions_out) store_action(pol.actions_out, pol.action_dtype, row + li, av[0]);
+        R o[4], rew;
+        bool term;
+        Env::step(s, c, Env::decode_t((DrawT)av[0]), a.p, a.freq_rate, o, rew, term);
+        ++steps;
+        bool trunc = (a.max_episode_steps > 0) & (steps >= a.max_episode_steps);
+        done = (term ? EMEI_DONE_TERMINAL : 0u) | (trunc ? EMEI_DONE_TRUNCATED : 0u);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = (float)o[k];
+        if (a.obs_out) (a.obs_out + row)[li] = make_float4(x[0], x[1], x[2], x[3]);
+        if (a.reward_out) (a.reward_out + row)[li] = (float)rew;
+        if (a.done_out) (a.done_out + row)[li] = (uint8_t)done;
+        if (auto_reset && __ballot(done != 0) != 0ull) {
+            if (done != 0) {
+                ++episode;
+                steps = 0;
+                Env::init(s, a.seed, a.env_offset + (uint64_t)i, episode, a.p);
+                Env::prime(s, c, a.p);
+                Env::obs_of(s, o);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) x[k] = (float)o[k];
+            }
+        }
+    }
+
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a.state[k * n + i] = s[k];
+    a.steps[i] = steps;
+    a.episode[i] = episode;
+    // done bits of the last step, one 64-bit word per wave, for emei_compact_done
+    unsigned long long m = __ballot(done != 0);
+    if (threadIdx.x == 0) a.done_mask[i / kWave] = m;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Staged rollout: the fast path of emei_rollout (all outputs present, n a multiple of 64,
 // 16-byte aligned buffers).  Same arithmetic and results as pend_rollout_kernel; what changes is
@@ -869,6 +942,67 @@ __global__ void __launch_bounds__(kBlock)
     for (int t = 0; t < horizon; ++t) {
         float av[1];
         policy_eval<4, 1, Env::kDiscrete>(pol, x, av);
+        R o[4], rew;
+        bool term;
+        Env::step(s, c, Env::decode_t((DrawT)av[0]), p, freq_rate, o, rew, term);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = (float)o[k];
+        if (live) {
+            ret = ret + g * (double)(float)rew;
+            g = g * discount;
+            if (term || t == horizon - 1) {  // the lane's last counted step
+                live = false;
+                ret_out[j] = ret;
+                if (len_out) len_out[j] = t + 1;
+                if (final_obs) final_obs[j] = make_float4(x[0], x[1], x[2], x[3]);
+            }
+        }
+        if (__ballot(live) == 0ull) break;  // wave-uniform
+    }
+}
+
+// emei_evaluate_policies_deep: pend_policy_eval_kernel's loop under the network with two hidden layers, as ONE-WAVE blocks (the
+// block's dynamic LDS is the wave's h1 tile): with env_waves = ceil(n_envs / 64), block b serves policy p = b / env_waves and env
+// wave b % env_waves, so p is still scalar and member p's offset weight bases stay wave-uniform.
+template <class Env>
+__global__ void __launch_bounds__(kWave)
+    pend_policy_eval_deep_kernel(const typename Env::real* state, const double* start_rows, int64_t n_envs, uint32_t env_waves,
+                                 int32_t horizon, double discount, int freq_rate, typename Env::Params p, const SinCosEntry* trig,
+                                 const PolicyDeepArgs stacked, double* ret_out, int32_t* len_out, float4* final_obs) {
+    using R = typename Env::real;
+    using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
+    extern __shared__ __attribute__((aligned(16))) float4 deep_h1_s[];
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table<kWave>(trig_s, trig, Env::trig_rot_c(), Env::trig_rot_s());
+    const uint32_t pi = blockIdx.x / env_waves;  // the block's policy: scalar
+    const int64_t i = (int64_t)(blockIdx.x - pi * env_waves) * kWave + threadIdx.x;
+    if (i >= n_envs) return;
+    const int64_t j = (int64_t)pi * n_envs + i;
+    PolicyDeepArgs pol = stacked;  // member pi of the population: n_out = 1
+    pol.w1 += (int64_t)pi * pol.hidden1 * 4, pol.b1 += (int64_t)pi * pol.hidden1;
+    pol.w2 += (int64_t)pi * pol.hidden2 * pol.hidden1, pol.b2 += (int64_t)pi * pol.hidden2;
+    pol.w3 += (int64_t)pi * pol.hidden2, pol.b3 += pi;
+    const PolicyNoiseArgs none{};  // pol.noisy == 0: never read
+
+    R s[4];
+    // start state: the handle's SoA, or the caller's float64 rows narrowed as emei_set_state narrows them (util_kernels.hip)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = start_rows ? (R)start_rows[i * 4 + k] : state[k * n_envs + i];
+    typename Env::Carry c;
+    trig_ctx_init(c.trig, trig_s);
+    Env::prime(s, c, p);
+    float x[4];
+    {
+        R o[4];
+        Env::obs_of(s, o);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = (float)o[k];
+    }
+    double ret = 0.0, g = 1.0;
+    bool live = true;
+    for (int t = 0; t < horizon; ++t) {
+        float av[1];
+        policy_eval_deep_t<4, 1, Env::kDiscrete>(pol, none, 0, 0, x, av, deep_h1_s, (int)threadIdx.x);
         R o[4], rew;
         bool term;
         Env::step(s, c, Env::decode_t((DrawT)av[0]), p, freq_rate, o, rew, term);
@@ -1639,6 +1773,25 @@ static int launch_env(const PendLaunch& L) {
             hipLaunchKernelGGL(pend_policy_eval_kernel<Env>, dim3(grid.x * (unsigned)P.n_candidates), dim3(kBlock), 0, L.stream,
                                (const R*)L.state, P.start_rows, L.n, grid.x, L.n_steps, P.discount, L.freq_rate, a.p, a.trig, L.policy,
                                P.return_out, P.length_out, (float4*)L.obs_out);
+            break;
+        }
+        case PEND_OP_POLICY_DEEP: {  // one-wave blocks, the wave's h1 tile as dynamic LDS
+            if (L.peers.count > 0) return EMEI_ERR_UNSUPPORTED;
+            if (int rc = policy_deep_lds_opt_in<pend_policy_rollout_deep_kernel<Env>>()) return rc;
+            const dim3 wgrid((unsigned)((L.n + kWave - 1) / kWave));
+            hipLaunchKernelGGL(pend_policy_rollout_deep_kernel<Env>, wgrid, dim3(kWave), policy_deep_tile_bytes(L.policy_deep.hidden1),
+                               L.stream, a, L.policy_deep, L.policy_noise);
+            if (L.selected) *L.selected = EMEI_KERNEL_PEND_POLICY_DEEP;
+            break;
+        }
+        case PEND_OP_POLICY_EVAL_DEEP: {  // block b = (policy b / env waves, env wave b % env waves); abi.hip bounds the grid
+            const PlanLaunch& P = L.plan;
+            if (int rc = policy_deep_lds_opt_in<pend_policy_eval_deep_kernel<Env>>()) return rc;
+            const unsigned env_waves = (unsigned)((L.n + kWave - 1) / kWave);
+            hipLaunchKernelGGL(pend_policy_eval_deep_kernel<Env>, dim3(env_waves * (unsigned)P.n_candidates), dim3(kWave),
+                               policy_deep_tile_bytes(L.policy_deep.hidden1), L.stream, (const R*)L.state, P.start_rows, L.n, env_waves,
+                               L.n_steps, P.discount, L.freq_rate, a.p, a.trig, L.policy_deep, P.return_out, P.length_out,
+                               (float4*)L.obs_out);
             break;
         }
         default: return EMEI_ERR_INVALID;

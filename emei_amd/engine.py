@@ -335,11 +335,12 @@ class Engine:
         out: (obs, reward, done) as rollout's.
         noise: a policy.PolicyNoise — exploration noise drawn inside the kernel (emei_rollout_policy_noisy): Gaussian on the continuous
         envs, epsilon-greedy on the discrete ones; step t draws under the key noise.seed + t, and the loop that calls
-        policy(obs, noise, t) gives the same actions.  None: the deterministic launch."""
+        policy(obs, noise, t) gives the same actions.  None: the deterministic launch.
+        A policy.DeepMLPPolicy (two hidden layers) goes to emei_rollout_policy_deep, with or without noise."""
         T = int(T)
         if T < 1:
             raise ValueError(f"n_steps={T} must be >= 1")
-        from .policy import MLPPolicy, PolicyNoise
+        from .policy import DeepMLPPolicy, MLPPolicy, PolicyNoise
 
         if not isinstance(policy, MLPPolicy):
             raise TypeError("rollout_policy takes an emei_amd.MLPPolicy (any other callable acts through the per-step loop: step())")
@@ -349,6 +350,13 @@ class Engine:
         act = torch.empty((T, self.n_envs) + self._act_tail, dtype=dtype, device=self.device)
         ps = policy.struct()
         flags = L.FLAG_AUTO_RESET if auto_reset else 0
+        if noise is not None and not isinstance(noise, PolicyNoise):
+            raise TypeError("noise= takes an emei_amd.PolicyNoise")
+        if isinstance(policy, DeepMLPPolicy):
+            ns = None if noise is None else noise.bind(self).struct(policy.hidden2)
+            L.check(L.lib().emei_rollout_policy_deep(self._h, T, C.byref(ps), None if ns is None else C.byref(ns), _ptr(act),
+                                                     _ACT_DTYPES[dtype], _ptr(obs), _ptr(rew), _ptr(done), flags, _stream()))
+            return act, obs, rew, done
         if noise is None:
             L.check(L.lib().emei_rollout_policy(self._h, T, C.byref(ps), _ptr(act), _ACT_DTYPES[dtype], _ptr(obs), _ptr(rew), _ptr(done),
                                                 flags, _stream()))
@@ -390,14 +398,17 @@ class Engine:
         """Score a population of P feedback policies, each on every env, from the current state (or `start_state`) in one launch, for
         policy search (emei_evaluate_policies): pair (p, i) runs policy p closed-loop for H steps from env i's start state, as
         rollout_policy(H, pop[p], auto_reset=False) would, and is scored as evaluate_sequences scores.  The handle's state, counters
-        and snapshot are left as they are.  pop: a policy.PolicyPopulation, or one MLPPolicy as a population of one.
+        and snapshot are left as they are.  pop: a policy.PolicyPopulation, or one MLPPolicy as a population of one; a
+        policy.DeepPolicyPopulation or one DeepMLPPolicy (two hidden layers) goes to emei_evaluate_policies_deep.
         -> (returns float64 [P, N], lengths int32 [P, N][, final_obs float32 [P, N, obs_dim]: the observation of the last counted step])"""
-        from .policy import MLPPolicy, PolicyPopulation
+        from .policy import DeepMLPPolicy, DeepPolicyPopulation, MLPPolicy, PolicyPopulation
 
-        if isinstance(pop, MLPPolicy):
+        if isinstance(pop, DeepMLPPolicy):
+            pop = DeepPolicyPopulation.from_policies([pop])
+        elif isinstance(pop, MLPPolicy):
             pop = PolicyPopulation.from_policies([pop])
-        if not isinstance(pop, PolicyPopulation):
-            raise TypeError("evaluate_policies takes an emei_amd.PolicyPopulation or an emei_amd.MLPPolicy")
+        if not isinstance(pop, (PolicyPopulation, DeepPolicyPopulation)):
+            raise TypeError("evaluate_policies takes an emei_amd.PolicyPopulation / DeepPolicyPopulation or an emei_amd.MLPPolicy")
         H = int(H)
         if H < 1:
             raise ValueError(f"horizon={H} must be >= 1")
@@ -408,8 +419,8 @@ class Engine:
         length = torch.empty((P, self.n_envs), dtype=torch.int32, device=self.device)
         fo = torch.empty((P, self.n_envs, self.obs_dim), dtype=torch.float32, device=self.device) if final_obs else None
         ps = pop.struct()
-        L.check(L.lib().emei_evaluate_policies(self._h, H, P, C.byref(ps), float(discount), _ptr(st), _ptr(ret), _ptr(length), _ptr(fo),
-                                               _stream()))
+        entry = L.lib().emei_evaluate_policies_deep if isinstance(pop, DeepPolicyPopulation) else L.lib().emei_evaluate_policies
+        L.check(entry(self._h, H, P, C.byref(ps), float(discount), _ptr(st), _ptr(ret), _ptr(length), _ptr(fo), _stream()))
         return (ret, length, fo) if final_obs else (ret, length)
 
     def _start_rows(self, start_state):

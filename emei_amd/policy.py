@@ -1,6 +1,7 @@
 """Feedback policies the engine evaluates INSIDE a rollout launch (emei_rollout_policy, include/emei_hip.h).
 
-MLPPolicy holds the weights of a small network — one ReLU hidden layer, or affine — as contiguous float32 device tensors.
+MLPPolicy holds the weights of a small network — one ReLU hidden layer, or affine — as contiguous float32 device tensors;
+DeepMLPPolicy, its subclass, a network with two ReLU hidden layers (emei_rollout_policy_deep: the shape of the zoo's SAC / TD3 actors).
 Engine.rollout_policy hands their pointers to the kernel (with noise=PolicyNoise: emei_rollout_policy_noisy, exploration noise drawn
 inside the kernel); calling the object, `policy(obs)`, evaluates the same normative
 arithmetic (float64 sums in ascending index order) with torch operations, so the one object also serves the per-step path
@@ -48,7 +49,8 @@ class MLPPolicy:
 
     @classmethod
     def from_module(cls, seq):
-        """torch.nn.Sequential(Linear[, ReLU, Linear][, Tanh]) -> MLPPolicy; a trailing Tanh selects out="tanh"."""
+        """torch.nn.Sequential(Linear[, ReLU, Linear[, ReLU, Linear]][, Tanh]) -> MLPPolicy (a DeepMLPPolicy for two hidden layers);
+        a trailing Tanh selects out="tanh"."""
         mods = list(seq)
         out = "clip"
         if mods and isinstance(mods[-1], torch.nn.Tanh):
@@ -59,8 +61,13 @@ class MLPPolicy:
             first, last = None, mods[0]
         elif kinds == [lin, relu, lin]:
             first, last = mods[0], mods[2]
+        elif kinds == [lin, relu, lin, relu, lin]:
+            if any(m.bias is None for m in mods[::2]):
+                raise ValueError("from_module: every Linear needs a bias")
+            return DeepMLPPolicy(mods[4].weight, mods[4].bias, mods[2].weight, mods[2].bias, mods[0].weight, mods[0].bias, out=out)
         else:
-            raise ValueError("from_module takes Linear[, ReLU, Linear][, Tanh]; got " + ", ".join(k.__name__ for k in map(type, seq)))
+            raise ValueError("from_module takes Linear[, ReLU, Linear[, ReLU, Linear]][, Tanh]; got "
+                             + ", ".join(k.__name__ for k in map(type, seq)))
         for m in (first, last):
             if m is not None and m.bias is None:
                 raise ValueError("from_module: every Linear needs a bias")
@@ -114,6 +121,11 @@ class MLPPolicy:
         w2 = self.w2.to(torch.float64)
         for j in range(h.shape[1]):
             y = y + w2[None, :, j] * h[:, j:j + 1]
+        return self._output(x, h, y, noise, t)
+
+    def _output(self, x, h, y, noise, t):
+        """what follows y: the threshold / epsilon-greedy of the discrete envs, or the noise term and the clip / tanh clause; h is what
+        the output layer read (the log-std head reads it too)"""
         if self.discrete:
             greedy = (y[:, 0] >= 0).to(torch.int64)
             if noise is None:
@@ -130,6 +142,75 @@ class MLPPolicy:
             a = torch.where(a >= self.lo, a, torch.full_like(a, self.lo))  # fmaxf(a, lo): NaN -> lo
             a = torch.where(a <= self.hi, a, torch.full_like(a, self.hi))
         return a[:, 0].contiguous() if self.n_out == 1 else a.contiguous()
+
+
+class DeepMLPPolicy(MLPPolicy):
+    """a = pi(obs) with TWO ReLU hidden layers: h1 = relu(w1 @ obs + b1), h2 = relu(w2 @ h1 + b2), y = w3 @ h2 + b3, then MLPPolicy's
+    output clause (clip / tanh / threshold).  w3 [n_out, hidden2], b3 [n_out], w2 [hidden2, hidden1], b2 [hidden2],
+    w1 [hidden1, obs_dim], b1 [hidden1], both widths in 1 .. 256 (emei_rollout_policy_deep, include/emei_hip.h).  An MLPPolicy
+    wherever one is taken: Engine.rollout_policy (noise= included; a log_std_head reads h2: ws [n_out, hidden2]),
+    Engine.evaluate_policies, datasets.collect; calling it evaluates the same normative arithmetic in torch float64."""
+
+    _WEIGHTS = ("w1", "b1", "w2", "b2", "w3", "b3")
+
+    def __init__(self, w3, b3, w2, b2, w1, b1, out="clip"):
+        if out not in _OUT_MODES:
+            raise ValueError(f"out {out!r}: 'clip' or 'tanh'")
+        f = lambda t: torch.as_tensor(t).detach().to(torch.float32).contiguous()
+        self.w1, self.b1, self.w2, self.b2, self.w3, self.b3 = f(w1), f(b1), f(w2), f(b2), f(w3), f(b3)
+        self.out = out
+        for w, b, name in ((self.w1, self.b1, "1"), (self.w2, self.b2, "2"), (self.w3, self.b3, "3")):
+            if w.dim() != 2 or b.dim() != 1 or b.shape[0] != w.shape[0]:
+                raise ValueError(f"w{name} {tuple(w.shape)} must be [n, n_in] and b{name} {tuple(b.shape)} [n]")
+        if self.w2.shape[1] != self.w1.shape[0]:
+            raise ValueError(f"w2 {tuple(self.w2.shape)} must be [hidden2, hidden1] with hidden1 = {int(self.w1.shape[0])} (w1's rows)")
+        if self.w3.shape[1] != self.w2.shape[0]:
+            raise ValueError(f"w3 {tuple(self.w3.shape)} must be [n_out, hidden2] with hidden2 = {int(self.w2.shape[0])} (w2's rows)")
+        self.hidden1, self.hidden2 = int(self.w1.shape[0]), int(self.w2.shape[0])
+        for name, v in (("hidden1", self.hidden1), ("hidden2", self.hidden2)):
+            if not 1 <= v <= L.POLICY_DEEP_MAX_HIDDEN:
+                raise ValueError(f"{name}={v} is outside [1, {L.POLICY_DEEP_MAX_HIDDEN}]")
+        self.hidden = self.hidden2  # the width the output layer (and a log-std head) reads
+        self.obs_dim = int(self.w1.shape[1])
+        self.n_out = int(self.w3.shape[0])
+        self.lo = self.hi = None
+        self.discrete = None
+
+    def to(self, device):
+        for k in self._WEIGHTS:
+            t = getattr(self, k)
+            if t.device != torch.device(device):
+                setattr(self, k, t.to(device).contiguous())
+        return self
+
+    def struct(self):
+        """struct emei_policy_deep over the weights (which the caller keeps alive for the launch)"""
+        p = lambda t: C.c_void_p(t.data_ptr())
+        return L.EmeiPolicyDeep(C.sizeof(L.EmeiPolicyDeep), self.hidden1, self.hidden2, _OUT_MODES[self.out], p(self.w1), p(self.b1),
+                                p(self.w2), p(self.b2), p(self.w3), p(self.b3), 0)
+
+    def __call__(self, obs, noise=None, t=None):
+        """MLPPolicy.__call__ for the two-hidden-layer network: the normative arithmetic of emei_rollout_policy_deep in torch float64,
+        one elementwise operation per term, every sum in ascending index order; the same actions as the launch (bit for bit where
+        MLPPolicy's are)."""
+        if self.discrete is None:
+            raise ValueError("DeepMLPPolicy: bind(engine) first (which env's action space is this for?)")
+        if (noise is None) != (t is None):
+            raise ValueError("noise and t come together")
+        h = torch.as_tensor(obs, device=self.w3.device).to(torch.float32).to(torch.float64)
+        x = h
+        for w, b in ((self.w1, self.b1), (self.w2, self.b2)):
+            z = b.to(torch.float64)[None, :].repeat(h.shape[0], 1)
+            w = w.to(torch.float64)
+            for k in range(h.shape[1]):
+                z = z + w[None, :, k] * h[:, k:k + 1]
+            h = z.to(torch.float32)
+            h = torch.where(h > 0, h, torch.zeros_like(h)).to(torch.float64)
+        y = self.b3.to(torch.float64)[None, :].repeat(h.shape[0], 1)
+        w3 = self.w3.to(torch.float64)
+        for i in range(h.shape[1]):
+            y = y + w3[None, :, i] * h[:, i:i + 1]
+        return self._output(x, h, y, noise, t)
 
 
 class PolicyNoise:
@@ -269,6 +350,8 @@ class PolicyPopulation:
         policies = list(policies)
         if not policies or not all(isinstance(p, MLPPolicy) for p in policies):
             raise ValueError("from_policies takes a non-empty list of MLPPolicy")
+        if any(isinstance(p, DeepMLPPolicy) for p in policies):
+            raise ValueError("from_policies: a DeepMLPPolicy belongs in a DeepPolicyPopulation")
         first = policies[0]
         for n, p in enumerate(policies):
             if p.out != first.out:
@@ -315,3 +398,90 @@ class PolicyPopulation:
         """the stacked struct emei_policy over the weights (which the caller keeps alive for the launch)"""
         p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
         return L.EmeiPolicy(C.sizeof(L.EmeiPolicy), self.hidden, _OUT_MODES[self.out], 0, p(self.w1), p(self.b1), p(self.w2), p(self.b2))
+
+
+class DeepPolicyPopulation:
+    """P DeepMLPPolicy networks of one architecture stacked along a leading axis, for Engine.evaluate_policies
+    (emei_evaluate_policies_deep): w3 [P, n_out, hidden2], b3 [P, n_out], w2 [P, hidden2, hidden1], b2 [P, hidden2],
+    w1 [P, hidden1, obs_dim], b1 [P, hidden1]; `out` is shared.  Kept as contiguous float32 tensors, member p's weights at
+    p * (the member's size) behind each base pointer.  len(pop) is P; pop[p] is a DeepMLPPolicy viewing member p."""
+
+    _WEIGHTS = DeepMLPPolicy._WEIGHTS
+
+    def __init__(self, w3, b3, w2, b2, w1, b1, out="clip"):
+        if out not in _OUT_MODES:
+            raise ValueError(f"out {out!r}: 'clip' or 'tanh'")
+        f = lambda t: torch.as_tensor(t).detach().to(torch.float32).contiguous()
+        self.w1, self.b1, self.w2, self.b2, self.w3, self.b3 = f(w1), f(b1), f(w2), f(b2), f(w3), f(b3)
+        self.out = out
+        if self.w3.dim() != 3 or self.w3.shape[0] < 1:
+            raise ValueError(f"w3 {tuple(self.w3.shape)} must be [P, n_out, hidden2] with P >= 1")
+        P = int(self.w3.shape[0])
+        for w, b, name in ((self.w1, self.b1, "1"), (self.w2, self.b2, "2"), (self.w3, self.b3, "3")):
+            if w.dim() != 3 or w.shape[0] != P:
+                raise ValueError(f"w{name} {tuple(w.shape)} must be [P, n, n_in] with P = {P}")
+            if tuple(b.shape) != (P, w.shape[1]):
+                raise ValueError(f"b{name} {tuple(b.shape)} must be [P, n] = {(P, int(w.shape[1]))}")
+        if self.w2.shape[2] != self.w1.shape[1]:
+            raise ValueError(f"w2 {tuple(self.w2.shape)} must be [P, hidden2, hidden1] with hidden1 = {int(self.w1.shape[1])}")
+        if self.w3.shape[2] != self.w2.shape[1]:
+            raise ValueError(f"w3 {tuple(self.w3.shape)} must be [P, n_out, hidden2] with hidden2 = {int(self.w2.shape[1])}")
+        self.hidden1, self.hidden2 = int(self.w1.shape[1]), int(self.w2.shape[1])
+        for name, v in (("hidden1", self.hidden1), ("hidden2", self.hidden2)):
+            if not 1 <= v <= L.POLICY_DEEP_MAX_HIDDEN:
+                raise ValueError(f"{name}={v} is outside [1, {L.POLICY_DEEP_MAX_HIDDEN}]")
+        self.n_policies = P
+        self.obs_dim = int(self.w1.shape[2])
+        self.n_out = int(self.w3.shape[1])
+        self._engine = None
+
+    @classmethod
+    def from_policies(cls, policies):
+        """[DeepMLPPolicy, ...] of the same shapes and the same `out` -> the population holding copies of their weights"""
+        policies = list(policies)
+        if not policies or not all(isinstance(p, DeepMLPPolicy) for p in policies):
+            raise ValueError("from_policies takes a non-empty list of DeepMLPPolicy")
+        first = policies[0]
+        for n, p in enumerate(policies):
+            if p.out != first.out:
+                raise ValueError(f"policy {n}: out={p.out!r} differs from policy 0's {first.out!r}")
+            for k in cls._WEIGHTS:
+                if getattr(first, k).shape != getattr(p, k).shape:
+                    raise ValueError(f"policy {n}: {k} {tuple(getattr(p, k).shape)} differs from policy 0's {tuple(getattr(first, k).shape)}")
+        dev = first.w3.device
+        st = lambda k: torch.stack([getattr(p, k).to(dev) for p in policies])
+        return cls(st("w3"), st("b3"), st("w2"), st("b2"), st("w1"), st("b1"), out=first.out)
+
+    def __len__(self):
+        return self.n_policies
+
+    def __getitem__(self, p):
+        """member p as a DeepMLPPolicy over VIEWS of the stacked weights (bound as the population is)"""
+        p = int(p)
+        if not -self.n_policies <= p < self.n_policies:
+            raise IndexError(f"policy {p} of a population of {self.n_policies}")
+        m = DeepMLPPolicy(self.w3[p], self.b3[p], self.w2[p], self.b2[p], self.w1[p], self.b1[p], out=self.out)
+        return m.bind(self._engine) if self._engine is not None else m
+
+    def to(self, device):
+        for k in self._WEIGHTS:
+            t = getattr(self, k)
+            if t.device != torch.device(device):
+                setattr(self, k, t.to(device).contiguous())
+        return self
+
+    def bind(self, engine):
+        """check the shapes against `engine`'s env and move the weights to its device, as MLPPolicy.bind"""
+        n_out = engine.act_dim if engine.act_dim > 0 else 1
+        if self.obs_dim != engine.obs_dim or self.n_out != n_out:
+            raise ValueError(f"the policies map {self.obs_dim} -> {self.n_out} but {engine.env_name} has obs_dim={engine.obs_dim} and "
+                             f"{n_out} policy output(s)")
+        self.to(engine.device)
+        self._engine = engine
+        return self
+
+    def struct(self):
+        """the stacked struct emei_policy_deep over the weights (which the caller keeps alive for the launch)"""
+        p = lambda t: C.c_void_p(t.data_ptr())
+        return L.EmeiPolicyDeep(C.sizeof(L.EmeiPolicyDeep), self.hidden1, self.hidden2, _OUT_MODES[self.out], p(self.w1), p(self.b1),
+                                p(self.w2), p(self.b2), p(self.w3), p(self.b3), 0)

@@ -55,7 +55,10 @@ extern "C" {
  *    each scored on every env from the envs' current or given states in one launch; the handle is untouched, no kernel id);
  *    emei_rollout_policy_noisy with struct emei_policy_noise (emei_rollout_policy with exploration noise drawn in the lanes: Gaussian
  *    with a given or a network-head standard deviation on the continuous envs, epsilon-greedy on the discrete ones),
- *    EMEI_KERNEL_PEND_POLICY_NOISY / EMEI_KERNEL_BODY_POLICY_NOISY / EMEI_KERNEL_BODY_POLICY_NOISY_RK4. */
+ *    EMEI_KERNEL_PEND_POLICY_NOISY / EMEI_KERNEL_BODY_POLICY_NOISY / EMEI_KERNEL_BODY_POLICY_NOISY_RK4;
+ *    emei_rollout_policy_deep and emei_evaluate_policies_deep with struct emei_policy_deep (the three policy calls for a network with
+ *    two ReLU hidden layers of up to EMEI_POLICY_DEEP_MAX_HIDDEN units each; struct emei_policy and its entry points are unchanged),
+ *    EMEI_KERNEL_PEND_POLICY_DEEP / EMEI_KERNEL_BODY_POLICY_DEEP / EMEI_KERNEL_BODY_POLICY_DEEP_RK4. */
 #define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
@@ -728,6 +731,64 @@ EMEI_API int emei_evaluate_policies(emei_env* h, int32_t horizon, int32_t n_poli
                                     const double* start_state, double* return_out, int32_t* length_out, float* final_obs_out,
                                     void* stream);
 
+/* emei_rollout_policy / emei_rollout_policy_noisy / emei_evaluate_policies for a network with TWO ReLU hidden layers — the shape of
+ * the actors the reference's zoo trains (stable-baselines3 MlpPolicy: 256-256 ReLU, SAC with a mean head, a log-std head and a tanh
+ * squash; TD3, DDPG and most PPO actors likewise).  struct emei_policy is unchanged; the deep network has a struct and two entry
+ * points of its own.  The six weight arrays are DEVICE pointers, read during the launch and not retained; they must not overlap any
+ * output of the call.
+ *
+ * Semantics (normative).  emei_rollout_policy_deep is emei_rollout_policy (noise NULL) or emei_rollout_policy_noisy (noise given),
+ * emei_evaluate_policies_deep is emei_evaluate_policies, clause for clause — Observe, Step, Start, scoring, the outputs, the state the
+ * handle is left in — except for the network of clause 2 ("Policy").  All sums run in ascending index order, in float64 (a product of
+ * two float32 values is exact in float64, so fused and unfused multiply-add give the same bits):
+ *        for j ascending, z = (double)b1[j]; for k ascending, z = z + (double)w1[j,k] * (double)x[k]; h1_j = (float)z;
+ *                    h1_j = h1_j > 0.f ? h1_j : 0.f (NaN gives 0).
+ *        for i ascending, z = (double)b2[i]; for j ascending, z = z + (double)w2[i,j] * (double)h1_j; h2_i = (float)z;
+ *                    h2_i = h2_i > 0.f ? h2_i : 0.f (NaN gives 0).
+ *        y_q = (double)b3[q]; for i ascending, y_q = y_q + (double)w3[q,i] * (double)h2_i.
+ *      What follows y_q is emei_rollout_policy's and emei_rollout_policy_noisy's text with h2 in the place of h: the CLIP, TANH and
+ *      threshold output clauses and their NaN handling; the noise term y_q = y_q + (double)s_q * (double)z_q, added last; the
+ *      EMEI_POLICY_NOISE_GAUSS_HEAD head ws [n_out, hidden2], l_q = (double)bs[q] + the ascending sum of (double)ws[q,i] * (double)h2_i;
+ *      epsilon-greedy; the noise words W[m] of (seed + t, g).  As there, TANH and GAUSS_HEAD are not pinned bit for bit.
+ *      emei_evaluate_policies_deep: `stacked` names P = n_policies networks laid end to end — w1 [P, hidden1, obs_dim], b1 [P, hidden1],
+ *      w2 [P, hidden2, hidden1], b2 [P, hidden2], w3 [P, n_out, hidden2], b3 [P, n_out] — hidden1, hidden2 and out_mode shared.
+ * Consequences.  Those of the one-layer calls: replay through emei_rollout (bit for bit in every mode) and through
+ * emei_evaluate_sequences; chunking, (a + b, seed) = (a, seed) then (b, seed + a); sharding, results depend on the global env index
+ * only; the calls neither allocate nor synchronise (capturable).  A deep network whose first layer is (e_k, -e_k) rows with zero
+ * biases and whose second layer is (w1[i,k], -w1[i,k]) computes the one-layer network's sums with zero terms between them: the same
+ * bits (finite weights and observations).
+ * Kernels: pend_policy_rollout_deep_kernel / body_policy_rollout_deep_kernel (one kernel per family, the noise a wave-uniform switch)
+ * and pend_policy_eval_deep_kernel / body_policy_eval_deep_kernel, all launched as ONE-WAVE blocks: the wave keeps h1 in a tile of
+ * dynamic LDS of 256 * ceil(hidden1 / 4) * 4 bytes (float32, lane-minor in groups of four units: 64 KiB at the cap) next to its
+ * kernel's static LDS; wave w holds envs 64 w .. 64 w + 63 as in the one-layer calls, and a block of the population call serves one
+ * policy (block b: policy b / nb, env wave b % nb, nb = ceil(n_envs / 64)).
+ * EMEI_ERR_INVALID before any HIP call, each message naming the argument, in this order: the scalars (n_steps < 1; horizon < 1,
+ * n_policies < 1, discount outside (0, 1]); NULL policy / stacked; struct_size wrong; hidden1, then hidden2, outside
+ * [1, EMEI_POLICY_DEEP_MAX_HIDDEN]; unknown out_mode; reserved != 0; with a non-NULL noise, emei_rollout_policy_noisy's checks of it in
+ * their order; a NULL handle; NULL w1, b1, w2, b2, w3 or b3, in this order; a wrong action_dtype, then unknown flags (the population
+ * call: NULL return_out, then n_envs * n_policies > 2^31 - 1 or more than 2^31 - 1 blocks); a GAUSS mode on a discrete env or
+ * EPS_GREEDY on a continuous one.  EMEI_ERR_STATE and EMEI_ERR_UNSUPPORTED where the one-layer calls give them. */
+#define EMEI_POLICY_DEEP_MAX_HIDDEN 256
+typedef struct emei_policy_deep {
+    uint32_t struct_size;   /* = sizeof(emei_policy_deep) */
+    int32_t hidden1;        /* width of the first hidden layer (ReLU), 1 .. EMEI_POLICY_DEEP_MAX_HIDDEN */
+    int32_t hidden2;        /* width of the second hidden layer (ReLU), 1 .. EMEI_POLICY_DEEP_MAX_HIDDEN */
+    int32_t out_mode;       /* enum emei_policy_out; ignored by the discrete envs */
+    const float* w1;        /* [hidden1, obs_dim] row-major */
+    const float* b1;        /* [hidden1] */
+    const float* w2;        /* [hidden2, hidden1] */
+    const float* b2;        /* [hidden2] */
+    const float* w3;        /* [n_out, hidden2];  n_out = act_dim, or 1 for the discrete envs */
+    const float* b3;        /* [n_out] */
+    int64_t reserved;       /* must be 0 */
+} emei_policy_deep;
+EMEI_API int emei_rollout_policy_deep(emei_env* h, int32_t n_steps, const emei_policy_deep* policy, const emei_policy_noise* noise,
+                                      void* actions_out, int action_dtype, float* obs_out, float* reward_out, uint8_t* done_out,
+                                      uint32_t flags, void* stream);
+EMEI_API int emei_evaluate_policies_deep(emei_env* h, int32_t horizon, int32_t n_policies, const emei_policy_deep* stacked,
+                                         double discount, const double* start_state, double* return_out, int32_t* length_out,
+                                         float* final_obs_out, void* stream);
+
 /* Which kernel the LAST emei_step / emei_rollout of this handle launched (enum emei_kernel_id): a debug /
  * test getter, so that a parity test can assert that the path it checked is the path bench.py times. */
 enum emei_kernel_id {
@@ -751,7 +812,10 @@ enum emei_kernel_id {
     EMEI_KERNEL_BODY_POLICY_RK4 = 17,        /* body_policy_rollout_kernel<Body, true> */
     EMEI_KERNEL_PEND_POLICY_NOISY = 18,      /* pend_policy_rollout_noisy_kernel<Env>: emei_rollout_policy_noisy */
     EMEI_KERNEL_BODY_POLICY_NOISY = 19,      /* body_policy_rollout_noisy_kernel<Body, false> */
-    EMEI_KERNEL_BODY_POLICY_NOISY_RK4 = 20   /* body_policy_rollout_noisy_kernel<Body, true> */
+    EMEI_KERNEL_BODY_POLICY_NOISY_RK4 = 20,  /* body_policy_rollout_noisy_kernel<Body, true> */
+    EMEI_KERNEL_PEND_POLICY_DEEP = 21,       /* pend_policy_rollout_deep_kernel<Env>: emei_rollout_policy_deep, with or without noise */
+    EMEI_KERNEL_BODY_POLICY_DEEP = 22,       /* body_policy_rollout_deep_kernel<Body, false> */
+    EMEI_KERNEL_BODY_POLICY_DEEP_RK4 = 23    /* body_policy_rollout_deep_kernel<Body, true> */
 };
 EMEI_API int emei_last_rollout_kernel(emei_env* h);
 

@@ -17,8 +17,13 @@ Shapes: CartPoleSwingUp N = 256 and N = 65 536, HalfCheetahRunning N = 256 and N
 on the continuous envs, epsilon 0.1 on the discrete ones: PolicyNoise), the fused deterministic launch and the per-step loop with the
 same policy and noise objects (policy(obs, noise, t): one sample_candidates launch more per step), alternating inside every round;
 the step count is sized on the noisy launch.  Reported: noisy_ms, fused_ms, loop_ms and the two ratios.
+--deep H1,H2: the two-hidden-layer network of emei_rollout_policy_deep in the same method — per shape the fused DEEP launch (a
+DeepMLPPolicy of widths H1, H2), the per-step loop with that same object as the callable, and the fused ONE-LAYER launch at
+hidden = H1 (what the second layer adds), alternating inside every round; the step count is sized on the deep launch, starting from an
+eighth of the shape's usual start (the loop of a wide net enqueues some thousand launches per step).  Reported: deep_ms, loop_ms,
+one_layer_ms and the two ratios.
 One JSON line per shape.  Run on the GPU box:
-    python tools/policy_timing.py [--warmup 2] [--repeats 7] [--only INDEX] [--noise]"""
+    python tools/policy_timing.py [--warmup 2] [--repeats 7] [--only INDEX] [--noise | --deep H1,H2]"""
 import argparse
 import json
 import os
@@ -29,7 +34,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from emei_amd.engine import Engine  # noqa: E402
-from emei_amd.policy import MLPPolicy, PolicyNoise  # noqa: E402
+from emei_amd.policy import DeepMLPPolicy, MLPPolicy, PolicyNoise  # noqa: E402
 
 # (env, N, starting T, engine kwargs)
 SHAPES = [
@@ -97,13 +102,59 @@ def noisy_shape(args, eng, name, N, T, policy, timed):
     print(json.dumps(row), flush=True)
 
 
+def deep_shape(args, eng, name, N, T, timed):
+    """--deep: one shape, the three routes alternating inside every round"""
+    h1, h2 = args.deep
+    g = torch.Generator().manual_seed(1)
+    n_out = max(eng.act_dim, 1)
+    r = lambda *s: torch.randn(*s, generator=g) / s[-1] ** 0.5
+    deep = DeepMLPPolicy(r(n_out, h2), r(n_out), r(h2, h1), r(h2), r(h1, eng.obs_dim), r(h1)).bind(eng)
+    one = MLPPolicy(r(n_out, h1), r(n_out), r(h1, eng.obs_dim), r(h1)).bind(eng)
+    box = {"T": max(T // 8, 8)}
+    box["outs"] = eng.alloc_outputs(box["T"])
+    routes = {
+        "deep": lambda: eng.rollout_policy(box["T"], deep, auto_reset=True, out=box["outs"]),
+        "loop": lambda: loop_episode(eng, box["T"], deep, box["outs"]),
+        "one_layer": lambda: eng.rollout_policy(box["T"], one, auto_reset=True, out=box["outs"]),
+    }
+    timed(routes["deep"])  # code objects loaded
+    while timed(routes["deep"]) < MIN_WINDOW_MS and 2 * box["T"] <= MAX_T:
+        box["T"] *= 2
+        box["outs"] = eng.alloc_outputs(box["T"])
+    kernel = eng.last_kernel()
+    for _ in range(args.warmup):
+        for fn in routes.values():
+            timed(fn)
+    ms = {k: [] for k in routes}
+    for _ in range(args.repeats):
+        for k, fn in routes.items():
+            ms[k].append(timed(fn))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    row = {"env": name, "n_envs": N, "hidden1": h1, "hidden2": h2, "n_steps": box["T"], "repeats": args.repeats}
+    for k in routes:
+        row[k + "_ms"] = round(med[k], 4)
+        row[k + "_ms_min_max"] = [round(min(ms[k]), 4), round(max(ms[k]), 4)]
+    row.update(loop_over_deep=round(med["loop"] / med["deep"], 3), deep_over_one_layer=round(med["deep"] / med["one_layer"], 3),
+               deep_us_per_step=round(1e3 * med["deep"] / box["T"], 3), kernel=kernel)
+    print(json.dumps(row), flush=True)
+
+
+def _widths(text):
+    h1, h2 = (int(v) for v in text.split(","))
+    return h1, h2
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--only", type=int, default=None, help="index of the one shape to run")
     ap.add_argument("--noise", action="store_true", help="time emei_rollout_policy_noisy against the deterministic launch and the noisy loop")
+    ap.add_argument("--deep", type=_widths, default=None, metavar="H1,H2",
+                    help="time emei_rollout_policy_deep at these widths against its per-step loop and the one-layer launch at H1")
     args = ap.parse_args()
+    if args.noise and args.deep:
+        raise SystemExit("--noise and --deep are separate measurements")
     if not torch.cuda.is_available():
         raise SystemExit("policy_timing.py needs a GPU")
     for idx, (name, N, T, kw) in enumerate(SHAPES):
@@ -130,6 +181,10 @@ def main():
 
         if args.noise:
             noisy_shape(args, eng, name, N, T, policy, timed)
+            eng.close()
+            continue
+        if args.deep:
+            deep_shape(args, eng, name, N, T, timed)
             eng.close()
             continue
         outs = eng.alloc_outputs(T)
