@@ -217,6 +217,9 @@ SYMBOLS = {
     "emei_rollout_policy_noisy": (C.c_int, [_vp, _i32, C.POINTER(EmeiPolicy), C.POINTER(EmeiPolicyNoise), _vp, C.c_int, _vp, _vp, _vp, _u32,
                                             _vp]),
     "emei_evaluate_policies": (C.c_int, [_vp, _i32, _i32, C.POINTER(EmeiPolicy), _dbl, _vp, _vp, _vp, _vp, _vp]),
+    "emei_plan_policy_workspace_bytes": (_i64, [_i64, _i32]),
+    "emei_plan_policy": (C.c_int, [_vp, _i32, _i32, C.POINTER(EmeiPolicy), C.POINTER(EmeiPolicyNoise), _dbl, _dbl, _vp, _vp, _vp, C.c_int,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "emei_rollout_policy_deep": (C.c_int, [_vp, _i32, C.POINTER(EmeiPolicyDeep), C.POINTER(EmeiPolicyNoise), _vp, C.c_int, _vp, _vp, _vp, _u32,
                                            _vp]),
     "emei_evaluate_policies_deep": (C.c_int, [_vp, _i32, _i32, C.POINTER(EmeiPolicyDeep), _dbl, _vp, _vp, _vp, _vp, _vp]),

@@ -1261,6 +1261,76 @@ extern "C" EMEI_API int emei_evaluate_policies(emei_env* h, int32_t horizon, int
 }
 
 // ---------------------------------------------------------------------------------------------
+// emei_plan_policy: shooting and MPPI over closed-loop rollouts of one feedback policy under exploration noise.  First launch: the
+// family's policy plan kernel (pendulum_kernels.h:pend_policy_plan_kernel, body_kernels.h:body_policy_plan_kernel) through the
+// plan-launch descriptor, as PLAN_DRAWN_KEEP with the policy in the place of the draws; second launch: plan_policy_finish_kernel.
+// Workspace: emei_plan_shooting's partials (a multiple of 16 bytes), then n_envs * n_candidates float64 returns (unused when the
+// caller gives return_out: the kernel then writes there), then kPlanPolicyMaxAct float32 slots per candidate, of which the actions of
+// step 0 take [n_envs * n_candidates, act_dim].  Nothing of the handle is written (h->last_kernel included).
+extern "C" EMEI_API int64_t emei_plan_policy_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
+    const int64_t nk = check_plan_shape("emei_plan_policy_workspace_bytes", n_envs, n_candidates);
+    return nk < 0 ? nk : plan_partials_bytes(n_envs, nk) + (int64_t)(sizeof(double) + kPlanPolicyMaxAct * sizeof(float)) * nk;
+}
+
+extern "C" EMEI_API int emei_plan_policy(emei_env* h, int32_t horizon, int32_t n_candidates, const emei_policy* policy,
+                                         const emei_policy_noise* noise, double discount, double temperature, const double* start_state,
+                                         void* workspace, void* best_action_out, int action_dtype, float* mean_action_out,
+                                         double* best_return_out, int32_t* best_index_out, int32_t* best_length_out, double* return_out,
+                                         double* ess_out, void* stream) {
+    const char* fn = "emei_plan_policy";
+    if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
+    if (mean_action_out || ess_out)
+        if (int rc = check_temperature(fn, temperature)) return rc;
+    if (int rc = check_policy_struct(fn, "policy", policy)) return rc;
+    if (int rc = check_policy_noise(fn, noise)) return rc;
+    if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = check_policy_weights(fn, "policy", policy)) return rc;
+    if (int rc = check_plan_lanes(fn, h, n_candidates)) return rc;
+    if (action_dtype < EMEI_ACT_U8 || action_dtype > EMEI_ACT_F32 || (h->act_dim > 0) != (action_dtype == EMEI_ACT_F32))
+        return fail(EMEI_ERR_INVALID, "%s: action_dtype=%d: best_action_out is uint8 / int32 / int64 for the discrete envs, float32 for the "
+                                      "continuous ones", fn, action_dtype);
+    if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
+    if (!best_action_out) return fail(EMEI_ERR_INVALID, "%s: null best_action_out", fn);
+    if ((h->act_dim > 0) == (noise->mode == EMEI_POLICY_NOISE_EPS_GREEDY))
+        return fail(EMEI_ERR_INVALID, "%s: noise.mode=%d: the Gaussian modes are for the continuous envs, EMEI_POLICY_NOISE_EPS_GREEDY for "
+                                      "the discrete ones", fn, noise->mode);
+    EMEI_ON_DEVICE(h, fn);
+    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    PolicyArgs pa{};
+    pa.w1 = policy->w1, pa.b1 = policy->b1, pa.w2 = policy->w2, pa.b2 = policy->b2;
+    pa.hidden = policy->hidden, pa.out_mode = policy->out_mode, pa.action_dtype = action_dtype;
+    ctrl_range(h->cfg.env_id, pa.lo, pa.hi);
+    PolicyNoiseArgs na{};
+    na.seed = noise->seed, na.mode = noise->mode, na.sigma = (float)noise->sigma;
+    if (noise->mode == EMEI_POLICY_NOISE_GAUSS) na.std = noise->std;
+    if (noise->mode == EMEI_POLICY_NOISE_GAUSS_HEAD)
+        na.ws = noise->ws, na.bs = noise->bs, na.log_std_min = noise->log_std_min, na.log_std_max = noise->log_std_max;
+    const int64_t nk = h->cfg.n_envs * (int64_t)n_candidates;
+    PlanLaunch p;
+    p.mode = PLAN_DRAWN_KEEP, p.start_rows = start_state, p.n_candidates = n_candidates, p.discount = discount;
+    p.partials = workspace;
+    p.return_out = return_out ? return_out : plan_returns(h, n_candidates, workspace);
+    p.first_actions = (float*)(plan_returns(h, n_candidates, workspace) + nk);
+    int rc;
+    if (!steps_as_body(h->cfg)) {
+        PendLaunch L = pend_base(h, stream);
+        L.op = PEND_OP_POLICY_PLAN, L.plan = p, L.policy = pa, L.policy_noise = na;
+        L.n_steps = horizon;
+        rc = pend_launch(L);
+    } else {
+        BodyLaunch L = body_base(h, stream);
+        L.op = BODY_OP_POLICY_PLAN, L.plan = p, L.policy = pa, L.policy_noise = na;
+        L.n_steps = horizon;
+        rc = body_launch(L);
+    }
+    if (rc == EMEI_OK)
+        rc = launch_plan_policy_finish(workspace, p.return_out, p.first_actions, h->cfg.n_envs, n_candidates, h->act_dim, temperature,
+                                       best_action_out, action_dtype, mean_action_out, best_return_out, best_index_out, best_length_out,
+                                       ess_out, (hipStream_t)stream);
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+}
+
+// ---------------------------------------------------------------------------------------------
 // emei_rollout_policy_deep / emei_evaluate_policies_deep: the policy calls above for struct emei_policy_deep (two hidden layers), on
 // kernels of their own (pend_policy_rollout_deep_kernel / body_policy_rollout_deep_kernel, pend_policy_eval_deep_kernel /
 // body_policy_eval_deep_kernel).  The refusals mirror check_policy_struct / check_policy_weights.

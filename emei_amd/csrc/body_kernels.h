@@ -172,7 +172,8 @@ enum BodyOp { BODY_OP_ROLLOUT = 0, BODY_OP_RESET, BODY_OP_GET_OBS, BODY_OP_INIT_
               BODY_OP_POLICY_EVAL /* emei_evaluate_policies: body_policy_eval_kernel */,
               BODY_OP_POLICY_NOISY /* emei_rollout_policy_noisy: body_policy_rollout_noisy_kernel */,
               BODY_OP_POLICY_DEEP /* emei_rollout_policy_deep: body_policy_rollout_deep_kernel */,
-              BODY_OP_POLICY_EVAL_DEEP /* emei_evaluate_policies_deep: body_policy_eval_deep_kernel */ };
+              BODY_OP_POLICY_EVAL_DEEP /* emei_evaluate_policies_deep: body_policy_eval_deep_kernel */,
+              BODY_OP_POLICY_PLAN /* emei_plan_policy: body_policy_plan_kernel */ };
 
 // What BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM take beyond the base descriptor: n_steps control steps of the planner with plan.n_candidates
 // candidates over `horizon` steps under plan.discount; plan.cand carries the call's seed, sigma and the ctrlrange (its nominal is
@@ -237,6 +238,8 @@ struct BodyLaunch {
     PolicyDeepArgs policy_deep = {};  // BODY_OP_POLICY_DEEP: BODY_OP_POLICY_NOISY's fields with the two-hidden-layer network here
                                       // (policy_deep.noisy: whether `policy_noise` is the call's noise or unused);
                                       // BODY_OP_POLICY_EVAL_DEEP: BODY_OP_POLICY_EVAL's fields with the STACKED networks here
+    // BODY_OP_POLICY_PLAN (emei_plan_policy): `policy` and `policy_noise` as BODY_OP_POLICY_NOISY takes them (actions_out unused), `plan`
+    // what PLAN_DRAWN_KEEP takes (cand unused) plus plan.first_actions; n_steps = the horizon
 };
 int body_launch(const BodyLaunch& L);  // body_dispatch.hip
 
@@ -1333,6 +1336,93 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
+// emei_plan_policy (the normative text: include/emei_hip.h) for the bodies: body_plan_kernel's DRAWN + KEEP loop — one lane per
+// candidate (i = j / K, k = j % K), the lanes on waves as emei_evaluate_sequences has them, every active lane's return kept in
+// ret_out[j] and one PlanPartial per (wave, env) segment through plan_reduce_wave — with the drawn controls replaced by the lane's
+// evaluation of THE policy on the float32 row it holds, as body_policy_rollout_noisy_kernel evaluates it: the action of step 0 under
+// the key nz.seed, the action of step t + 1 at the end of step t under nz.seed + t + 1, the lane's k in the counter word and no noise
+// at all for k = 0.  Every lane reads the same network: the weights stay wave-uniform scalar loads.  An active lane leaves its action
+// of step 0 in first_out[j * NA ..] for plan_policy_finish_kernel.  Padding lanes as body_plan_kernel's.
+template <class Body, bool RK4>
+__global__ void __launch_bounds__(kBlock)
+    body_policy_plan_kernel(const typename Body::real* state, const double* start_rows, int64_t n_envs, int32_t n_cand, int32_t horizon,
+                            double discount, int freq_rate, int semi, typename Body::Model m, const SinCosEntry* trig_tab,
+                            unsigned long long* cap_hits, const PolicyArgs pol, const PolicyNoiseArgs nz, uint64_t env_offset,
+                            double* ret_out, float* first_out, PlanPartial* partials) {
+    using R = typename Body::real;
+    constexpr int NS = Body::NS, NO = Body::NO, NA = Body::NA;
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table(trig_s, trig_tab);  // every thread reaches the barrier
+    TrigCtx trig;
+    trig.tab = trig_s;
+    __shared__ R scratch_s[(Body::kScratchPerLane > 0 ? Body::kScratchPerLane : 1) * (Body::kScratchPerLane > 0 ? kBlock : 1)];
+    if constexpr (Body::kScratchPerLane > 0) trig.scratch = scratch_s;
+    trig.scratch_stride = kBlock;
+    trig.cap_hits = cap_hits;
+    const int64_t nk = n_envs * n_cand;
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool active = j < nk;
+    // no divergent branch around the loads: see body_plan_kernel.  nk <= 2^31 - 1 (abi.hip), so an active j divides in 32 bits: the
+    // 64-bit division expands into two paths, and with i in a spill register both ended in stores in front of the EXEC restore
+    const uint32_t ju = active ? (uint32_t)j : 0u, iu = ju / (uint32_t)n_cand;
+    const int64_t i = iu;
+    static_assert(NA <= kPlanPolicyMaxAct, "first_out holds kPlanPolicyMaxAct float32 slots per candidate (abi.hip sizes the workspace)");
+    const uint32_t kc = ju - iu * (uint32_t)n_cand;
+    const uint64_t genv = env_offset + (uint64_t)i;
+    R s[NS], parked[NS];
+    if (start_rows) {  // wave-uniform; the caller's float64 rows are narrowed as emei_set_state narrows them (util_kernels.hip)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = (R)start_rows[i * NS + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = state[(int64_t)k * n_envs + i];
+    }
+    Body::park(parked);  // as body_rollout_kernel's padding lanes
+    float act[NA];
+    {  // x_0: the float32 observation of the START state (a padding lane: env 0's), as emei_get_obs rounds it
+        double od[NO];
+        Body::obs_of(s, od, m);
+        float x[NO];
+#pragma unroll
+        for (int k = 0; k < NO; ++k) x[k] = (float)od[k];
+        policy_eval_t<NO, NA, false, true>(pol, nz, nz.seed, genv, x, act, kc, kc != 0u);
+    }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) s[k] = active ? s[k] : parked[k];
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < NA; ++k) first_out[j * NA + k] = act[k];
+    }
+    double ret = 0.0, g = 1.0;
+    int32_t len = 0;  // steps counted so far (ret and len stop changing with the lane's last counted step)
+    bool live = active;
+    for (int t = 0; t < horizon; ++t) {
+        R ctrl[NA];  // padding lanes: zero, as the rollout's staging gives them
+#pragma unroll
+        for (int k = 0; k < NA; ++k) ctrl[k] = active ? (R)act[k] : R(0);
+        R pre[NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) pre[k] = s[k];
+        typename Body::Warm warm{};
+        for (int k = 0; k < freq_rate; ++k) body_substep<Body, RK4>(s, ctrl, m, semi != 0, trig, warm);
+        float o[NO];
+        R rew;
+        bool term;
+        Body::outputs(s, pre, ctrl, m, freq_rate, o, rew, term, trig);
+        // selects, not a block under `live`: with ret, g and len in spill registers hipcc ended the block with their stores in front
+        // of the EXEC restore, the shape tools/isa_scan.py flags (correct there, but not distinguishable from the miscompile)
+        const double counted = ret + g * (double)(float)rew, g_next = g * discount;
+        ret = live ? counted : ret;
+        g = live ? g_next : g;
+        len = live ? t + 1 : len;
+        live = live & !(term | (t == horizon - 1));
+        if (__ballot(live) == 0ull) break;  // wave-uniform
+        policy_eval_t<NO, NA, false, true>(pol, nz, nz.seed + (uint64_t)t + 1u, genv, o, act, kc, kc != 0u);  // wave-uniform: the next step's action
+    }
+    plan_reduce_wave(j, nk, i, n_cand, ret, len, partials);
+    if (active) ret_out[j] = ret;
+}
+
 // emei_evaluate_policies_deep for the bodies: body_policy_eval_kernel's loop under the network with two hidden layers, as ONE-WAVE
 // blocks (the block's dynamic LDS is the wave's h1 tile): with env_waves = ceil(n_envs / 64), block b serves policy p = b / env_waves
 // and env wave b % env_waves, so p is still scalar, member p's offset weight bases stay wave-uniform, and wave w of a policy holds
@@ -1575,6 +1665,21 @@ static int launch_body(const BodyLaunch& L) {
                 hipLaunchKernelGGL((body_policy_eval_kernel<Body, false>), egrid, dim3(kBlock), 0, L.stream, (const R*)L.state, P.start_rows,
                                    L.n, grid.x, L.n_steps, P.discount, L.freq_rate, semi, m, (const SinCosEntry*)L.trig, L.cap_hits, L.policy,
                                    P.return_out, P.length_out, L.obs_out);
+            break;
+        }
+        case BODY_OP_POLICY_PLAN: {  // emei_plan_policy: one lane per candidate, n * n_candidates < 2^31 (checked in abi.hip)
+            const PlanLaunch& P = L.plan;
+            if (!P.partials || !P.return_out || !P.first_actions) return EMEI_ERR_INVALID;
+            const dim3 pgrid((unsigned)((L.n * P.n_candidates + kBlock - 1) / kBlock));
+            const int semi = (int)(L.integrator == EMEI_INTEG_SEMI_IMPLICIT);
+            if (L.integrator == EMEI_INTEG_RK4)
+                hipLaunchKernelGGL((body_policy_plan_kernel<Body, true>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state, P.start_rows,
+                                   L.n, P.n_candidates, L.n_steps, P.discount, L.freq_rate, 0, m, (const SinCosEntry*)L.trig, L.cap_hits,
+                                   L.policy, L.policy_noise, L.env_offset, P.return_out, P.first_actions, (PlanPartial*)P.partials);
+            else
+                hipLaunchKernelGGL((body_policy_plan_kernel<Body, false>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state, P.start_rows,
+                                   L.n, P.n_candidates, L.n_steps, P.discount, L.freq_rate, semi, m, (const SinCosEntry*)L.trig, L.cap_hits,
+                                   L.policy, L.policy_noise, L.env_offset, P.return_out, P.first_actions, (PlanPartial*)P.partials);
             break;
         }
         case BODY_OP_OCCUPANCY: {

@@ -765,9 +765,12 @@ struct PolicyNoiseArgs {  // kernel-argument form of struct emei_policy_noise
 // step t joins y last, s_q * z_q with z from the lane's own words CandidateWords(key, g, 0) — the normals candidate k = 0 draws at
 // step 0 under that key — or, on a discrete env, the epsilon-greedy draws W[0] / W[1] replace the threshold.  The log-std head's NA
 // accumulators ride the hidden-unit loop next to y.  NOISY = false is policy_eval, the code it was.
+// cand / noise_on (emei_plan_policy: the lane's candidate k in the counter word that holds 0 for the rollouts, and whether the lane
+// takes its noise at all — candidate 0 does not, by a select after the draw).  The defaults are constants the compiler folds: the
+// rollout kernels' instantiations are the code they were.
 template <int NO, int NA, bool DISCRETE, bool NOISY>
 __device__ __forceinline__ void policy_eval_t(const PolicyArgs& pa, const PolicyNoiseArgs& nz, uint64_t key, uint64_t g,
-                                              const float (&x)[NO], float (&act)[NA]) {
+                                              const float (&x)[NO], float (&act)[NA], uint32_t cand = 0u, bool noise_on = true) {
     const PolicyWeights w1 = (PolicyWeights)pa.w1, b1 = (PolicyWeights)pa.b1, w2 = (PolicyWeights)pa.w2, b2 = (PolicyWeights)pa.b2;
     const int hidden = pa.hidden;  // wave-uniform, as every index below
     [[maybe_unused]] const PolicyWeights ws = (PolicyWeights)nz.ws, bs = (PolicyWeights)nz.bs;
@@ -810,13 +813,14 @@ __device__ __forceinline__ void policy_eval_t(const PolicyArgs& pa, const Policy
         }
     }
     if constexpr (NOISY && DISCRETE) {
-        CandidateWords cw(key, g, 0u);
+        CandidateWords cw(key, g, cand);
         const bool explore = u01(cw.word(0u)) < nz.sigma, coin = u01(cw.word(1u)) < 0.5f;
         act[0] = explore ? (coin ? 1.f : 0.f) : (y[0] >= 0.0 ? 1.f : 0.f);
+        act[0] = noise_on ? act[0] : (y[0] >= 0.0 ? 1.f : 0.f);  // a select: without noise the lane never explores
         return;
     }
     if constexpr (NOISY && !DISCRETE) {
-        CandidateWords cw(key, g, 0u);
+        CandidateWords cw(key, g, cand);
         const PolicyWeights sd = (PolicyWeights)nz.std;
 #pragma unroll
         for (int p = 0; p < (NA + 1) / 2; ++p) {  // the pair (W[2p], W[2p + 1]) lies inside one Philox block
@@ -828,7 +832,8 @@ __device__ __forceinline__ void policy_eval_t(const PolicyArgs& pa, const Policy
                 float sq;
                 if (head) sq = (float)exp(fmin(fmax(l[q], (double)nz.log_std_min), (double)nz.log_std_max));
                 else sq = sd ? sd[q] : nz.sigma;
-                y[q] = fma((double)sq, (double)z[q & 1], y[q]);  // the last term of the sum
+                const double yn = fma((double)sq, (double)z[q & 1], y[q]);  // the last term of the sum
+                y[q] = noise_on ? yn : y[q];  // a select: without noise y_q keeps its bits (the sign of -0.0 included)
             }
         }
     }

@@ -7,7 +7,7 @@
 
 namespace emei {
 
-enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC, PEND_OP_MPC_CEM, PEND_OP_POLICY, PEND_OP_POLICY_EVAL, PEND_OP_POLICY_NOISY, PEND_OP_POLICY_DEEP, PEND_OP_POLICY_EVAL_DEEP };
+enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC, PEND_OP_MPC_CEM, PEND_OP_POLICY, PEND_OP_POLICY_EVAL, PEND_OP_POLICY_NOISY, PEND_OP_POLICY_DEEP, PEND_OP_POLICY_EVAL_DEEP, PEND_OP_POLICY_PLAN };
 
 // emei_set_obs_peers: the gathered buffers the staged rollout kernel also writes every observation row to
 struct ObsPeers {
@@ -35,6 +35,7 @@ struct PlanLaunch {
     CandidateSpec cand = {};
     void* partials = nullptr;
     const float* sigma_map = nullptr;  // emei_plan_cem: non-null -> the draws take their sigma per entry (CandidateSpecMap)
+    float* first_actions = nullptr;  // PEND_OP_POLICY_PLAN / BODY_OP_POLICY_PLAN: [n * K(, act_dim)] float32, every candidate's action at t = 0
 };
 
 struct PendLaunch {
@@ -97,6 +98,9 @@ struct PendLaunch {
     // PEND_OP_POLICY_DEEP (emei_rollout_policy_deep): PEND_OP_POLICY_NOISY's fields with the two-hidden-layer network in `policy_deep`
     // (policy_deep.noisy: whether `policy_noise` is the call's noise or unused)
     // PEND_OP_POLICY_EVAL_DEEP (emei_evaluate_policies_deep): PEND_OP_POLICY_EVAL's fields with the STACKED networks in `policy_deep`
+    // PEND_OP_POLICY_PLAN (emei_plan_policy): `policy` and `policy_noise` as PEND_OP_POLICY_NOISY takes them (actions_out unused),
+    // `plan` what PLAN_DRAWN_KEEP takes (cand unused: the candidates are the policy's noisy rollouts) plus plan.first_actions;
+    // n_steps = the horizon
     PolicyDeepArgs policy_deep = {};
 };
 
@@ -138,6 +142,14 @@ int launch_plan_finish(const void* partials, const CandidateSpec& sp, int64_t n_
 int launch_plan_mppi_finish(const void* partials, double* returns, const CandidateSpec& sp, int64_t n_envs, int32_t n_cand, int32_t horizon,
                             int act_dim, double temperature, float* nominal_out, double* best_return, int32_t* best_index, double* ess,
                             hipStream_t s);
+// emei_plan_policy keeps every candidate's action of step 0 in its workspace, sized without a handle: the widest action of the envs
+// (the HalfCheetah's six components); launch_plan_policy_finish refuses more
+constexpr int kPlanPolicyMaxAct = 6;
+// the second launch of emei_plan_policy: `returns` and `first` [n_envs * n_cand(, act_dim)] as the policy plan kernel left them (read
+// only); mean_out / ess null: the weights are not formed and temperature is not read
+int launch_plan_policy_finish(const void* partials, const double* returns, const float* first, int64_t n_envs, int32_t n_cand, int act_dim,
+                              double temperature, void* best_action, int action_dtype, float* mean_out, double* best_return,
+                              int32_t* best_index, int32_t* best_length, double* ess, hipStream_t s);
 // emei_sample_candidates_sigma: the Gaussian mode with a sigma per entry
 int launch_sample_candidates_sigma(const CandidateSpecMap& sp, int64_t n_envs, int32_t n_cand, int32_t horizon, int act_dim, void* actions_out,
                                    hipStream_t s);

@@ -961,6 +961,63 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
+// emei_plan_policy (the normative text: include/emei_hip.h): pend_plan_kernel's DRAWN + KEEP loop — one lane per candidate
+// (i = j / K, k = j % K), every return kept in ret_out[j], one PlanPartial per (wave, env) segment through plan_reduce_wave — with the
+// drawn action replaced by the lane's evaluation of THE policy on the float32 row it holds, as pend_policy_rollout_noisy_kernel
+// evaluates it: the noise of step t under the key nz.seed + t, with the lane's k in the counter word, and none at all for k = 0.
+// Every lane reads the same network, so the weights stay wave-uniform scalar loads.  The lane also leaves its action of step 0 in
+// first_out[j] (4 B per candidate) for plan_policy_finish_kernel; nothing else is read or written per step.
+template <class Env>
+__global__ void __launch_bounds__(kBlock)
+    pend_policy_plan_kernel(const typename Env::real* state, const double* start_rows, int64_t n_envs, int32_t n_cand, int32_t horizon,
+                            double discount, int freq_rate, typename Env::Params p, const SinCosEntry* trig, const PolicyArgs pol,
+                            const PolicyNoiseArgs nz, uint64_t env_offset, double* ret_out, float* first_out, PlanPartial* partials) {
+    using R = typename Env::real;
+    using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table(trig_s, trig, Env::trig_rot_c(), Env::trig_rot_s());
+    const int64_t nk = n_envs * n_cand;
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= nk) return;
+    const int64_t i = j / n_cand;
+    const uint32_t k = (uint32_t)(j - i * n_cand);
+    R s[4];
+    // start state: the handle's SoA, or the caller's float64 rows narrowed as emei_set_state narrows them (util_kernels.hip)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[q] = start_rows ? (R)start_rows[i * 4 + q] : state[q * n_envs + i];
+    typename Env::Carry c;
+    trig_ctx_init(c.trig, trig_s);
+    Env::prime(s, c, p);
+    float x[4];
+    {
+        R o[4];
+        Env::obs_of(s, o);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) x[q] = (float)o[q];
+    }
+    double ret = 0.0, g = 1.0;
+    int32_t len = horizon;
+    bool live = true;
+    for (int t = 0; t < horizon; ++t) {
+        float av[1];
+        policy_eval_t<4, 1, Env::kDiscrete, true>(pol, nz, nz.seed + (uint64_t)t, env_offset + (uint64_t)i, x, av, k, k != 0u);
+        if (t == 0) first_out[j] = av[0];
+        R o[4], rew;
+        bool term;
+        Env::step(s, c, Env::decode_t((DrawT)av[0]), p, freq_rate, o, rew, term);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) x[q] = (float)o[q];
+        if (live) {
+            ret = ret + g * (double)(float)rew;
+            g = g * discount;
+            if (term) live = false, len = t + 1;
+        }
+        if (__ballot(live) == 0ull) break;  // wave-uniform
+    }
+    ret_out[j] = ret;  // j < nk here
+    plan_reduce_wave(j, nk, i, n_cand, ret, len, partials);
+}
+
 // emei_evaluate_policies_deep: pend_policy_eval_kernel's loop under the network with two hidden layers, as ONE-WAVE blocks (the
 // block's dynamic LDS is the wave's h1 tile): with env_waves = ceil(n_envs / 64), block b serves policy p = b / env_waves and env
 // wave b % env_waves, so p is still scalar and member p's offset weight bases stay wave-uniform.
@@ -1773,6 +1830,15 @@ static int launch_env(const PendLaunch& L) {
             hipLaunchKernelGGL(pend_policy_eval_kernel<Env>, dim3(grid.x * (unsigned)P.n_candidates), dim3(kBlock), 0, L.stream,
                                (const R*)L.state, P.start_rows, L.n, grid.x, L.n_steps, P.discount, L.freq_rate, a.p, a.trig, L.policy,
                                P.return_out, P.length_out, (float4*)L.obs_out);
+            break;
+        }
+        case PEND_OP_POLICY_PLAN: {  // emei_plan_policy: one lane per candidate, n * n_candidates < 2^31 (checked in abi.hip)
+            const PlanLaunch& P = L.plan;
+            if (!P.partials || !P.return_out || !P.first_actions) return EMEI_ERR_INVALID;
+            const dim3 pgrid((unsigned)((L.n * P.n_candidates + kBlock - 1) / kBlock));
+            hipLaunchKernelGGL(pend_policy_plan_kernel<Env>, pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state, P.start_rows, L.n,
+                               P.n_candidates, L.n_steps, P.discount, L.freq_rate, a.p, a.trig, L.policy, L.policy_noise, L.env_offset,
+                               P.return_out, P.first_actions, (PlanPartial*)P.partials);
             break;
         }
         case PEND_OP_POLICY_DEEP: {  // one-wave blocks, the wave's h1 tile as dynamic LDS

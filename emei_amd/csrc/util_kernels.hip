@@ -250,6 +250,81 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
+// Second launch of emei_plan_policy, one wave per env, lane l owning the candidates k = l, l + 64, ... (plan_mppi_finish_kernel's
+// layout and summation tree).  The candidates' returns and their actions of step 0 are where the policy plan kernel left them, so
+// nothing is redrawn and no policy is evaluated here:
+//   1. (k*, r*, L) from the env's partials, as plan_finish_kernel finds them; best_action is candidate k*'s stored action;
+//   2. WEIGHTED (mean_out or ess wanted): the weights of emei_plan_mppi's case analysis, Z = sum w, sum w^2 and one weighted sum per
+//      action component, a lane's candidates in ascending k, then the butterfly — a tree over k alone.
+// `returns` and `first` are read only (returns may be the caller's return_out).
+template <bool WEIGHTED>
+__global__ void __launch_bounds__(kBlock)
+    plan_policy_finish_kernel(const PlanPartial* partials, const double* returns, const float* first, int64_t n_envs, int32_t n_cand,
+                              int act_dim, double temperature, void* best_action, int action_dtype, float* mean_out, double* best_return,
+                              int32_t* best_index, int32_t* best_length, double* ess) {
+    const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / kWave;  // wave-uniform
+    const int lane = (int)(threadIdx.x & (kWave - 1));
+    if (i >= n_envs) return;
+    const int64_t w0 = (i * n_cand) / kWave, w1 = ((i + 1) * n_cand - 1) / kWave;
+    double rs = __builtin_nan("");  // (NaN, INT32_MAX) loses to every partial
+    int32_t ks = INT32_MAX, len = 0;
+    for (int64_t w = w0 + lane; w <= w1; w += kWave) {
+        const PlanPartial p = partials[w + i];
+        if (plan_replaces(rs, ks, p.ret, p.k)) rs = p.ret, ks = p.k, len = p.len;
+    }
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const double r2 = __shfl_xor(rs, d, kWave);
+        const int32_t k2 = __shfl_xor(ks, d, kWave), l2 = __shfl_xor(len, d, kWave);
+        if (plan_replaces(rs, ks, r2, k2)) rs = r2, ks = k2, len = l2;
+    }
+    const int na = act_dim > 0 ? act_dim : 1;
+    const float* fa = first + i * n_cand * na;  // the env's [n_cand, na] actions of step 0
+    if (lane == 0) {
+        if (best_return) best_return[i] = rs;
+        if (best_index) best_index[i] = ks;
+        if (best_length) best_length[i] = len;
+    }
+    if (lane < na) store_action(best_action, action_dtype, i * na + lane, fa[(int64_t)ks * na + lane]);
+    if constexpr (WEIGHTED) {
+        const double* rt = returns + i * n_cand;
+        double z = 0.0, z2 = 0.0, acc[kPlanPolicyMaxAct] = {};
+        for (int32_t k = lane; k < n_cand; k += kWave) {
+            const double r = rt[k];
+            const double e = exp((r - rs) / temperature);  // r < r*: the argument is negative, -inf included
+            const double w = rs != rs ? 1.0 : (r != r ? 0.0 : (r == rs ? 1.0 : e));
+            z += w, z2 += w * w;
+#pragma unroll
+            for (int a = 0; a < kPlanPolicyMaxAct; ++a)
+                if (a < na) acc[a] += w * (double)fa[(int64_t)k * na + a];
+        }
+        z = wave_sum_all(z), z2 = wave_sum_all(z2);  // Z >= 1: candidate k* has weight 1
+#pragma unroll
+        for (int a = 0; a < kPlanPolicyMaxAct; ++a) {
+            if (a < na) {  // wave-uniform
+                const double sum = wave_sum_all(acc[a]);
+                if (lane == 0 && mean_out) mean_out[i * na + a] = (float)(sum / z);
+            }
+        }
+        if (lane == 0 && ess) ess[i] = z * z / z2;
+    }
+}
+
+int launch_plan_policy_finish(const void* partials, const double* returns, const float* first, int64_t n_envs, int32_t n_cand, int act_dim,
+                              double temperature, void* best_action, int action_dtype, float* mean_out, double* best_return,
+                              int32_t* best_index, int32_t* best_length, double* ess, hipStream_t s) {
+    if (act_dim > kPlanPolicyMaxAct) return EMEI_ERR_INVALID;
+    constexpr int kEnvsPerBlock = kBlock / kWave;  // one wave per env
+    dim3 grid((unsigned)((n_envs + kEnvsPerBlock - 1) / kEnvsPerBlock));
+    if (mean_out || ess)
+        hipLaunchKernelGGL(plan_policy_finish_kernel<true>, grid, dim3(kBlock), 0, s, (const PlanPartial*)partials, returns, first, n_envs,
+                           n_cand, act_dim, temperature, best_action, action_dtype, mean_out, best_return, best_index, best_length, ess);
+    else
+        hipLaunchKernelGGL(plan_policy_finish_kernel<false>, grid, dim3(kBlock), 0, s, (const PlanPartial*)partials, returns, first, n_envs,
+                           n_cand, act_dim, temperature, best_action, action_dtype, mean_out, best_return, best_index, best_length, ess);
+    return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;
+}
+
 // ---------------------------------------------------------------------------------------------
 // emei_plan_cem (the planner's order as a 64-bit key: emei_device.h:plan_key).
 

@@ -531,6 +531,64 @@ class Engine:
                                        _ptr(st), _ptr(ws), _ptr(out), _ptr(ret), _ptr(idx), _ptr(es), _stream()))
         return (out, ret, idx) + ((es,) if ess else ())
 
+    # -- planning around a feedback policy (emei_plan_policy) ---------------------------------------------------
+    def _plan_policy_args(self, H, K, policy, noise, discount, temperature):
+        """validated (H, K, policy struct, noise struct, discount, temperature or None) of plan_policy; policy and noise are bound to
+        this engine (shapes against the env, the noise mode against the env kind).  Needs no handle."""
+        from .policy import DeepMLPPolicy, MLPPolicy, PolicyNoise
+
+        H, K = int(H), int(K)
+        if H < 1 or K < 1:
+            raise ValueError(f"horizon={H} and n_candidates={K} must be >= 1")
+        if not isinstance(policy, MLPPolicy):
+            raise TypeError("plan_policy takes an emei_amd.MLPPolicy")
+        if isinstance(policy, DeepMLPPolicy):
+            raise ValueError("plan_policy: the two-hidden-layer network (DeepMLPPolicy) is not served by this call yet; "
+                             "it takes an MLPPolicy with one hidden layer or none")
+        if not isinstance(noise, PolicyNoise):
+            raise TypeError("plan_policy takes an emei_amd.PolicyNoise (the exploration noise that makes the candidates differ)")
+        discount = float(discount)
+        if not 0.0 < discount <= 1.0:
+            raise ValueError(f"discount={discount} is outside (0, 1]")
+        if temperature is not None:
+            temperature = float(temperature)
+            if not (0.0 < temperature < float("inf")):
+                raise ValueError(f"temperature={temperature} must be finite and > 0 (None: no weighted mean, no ess)")
+        policy.bind(self)
+        ns = noise.bind(self).struct(policy.hidden if policy.hidden else policy.obs_dim)
+        return H, K, policy.struct(), ns, discount, temperature
+
+    @_on_device
+    def plan_policy(self, H, K, policy, noise, discount=1.0, temperature=None, start_state=None, returns=False, length=False, ess=False):
+        """Shooting and MPPI around a feedback policy in two launches (emei_plan_policy): per env, K closed-loop rollouts of `policy`
+        (a policy.MLPPolicy) for H steps from the current state (or `start_state` [N, state_dim] float64), candidate k under the
+        exploration noise of `noise` (a policy.PolicyNoise) drawn in the lanes with k in the counter word — candidate 0 takes no noise:
+        it is the policy itself — scored as evaluate_sequences scores, and arg-maxed on the device.  The loop "observe,
+        policy(obs, noise, t, candidate=k) (policy(obs) for k = 0), step" takes candidate k's actions.
+        -> (best_action [N(, act_dim)] int64 / float32: the winner's action at t = 0, best_return float64 [N], best_index int32 [N]
+        [, mean_action float32 [N(, act_dim)]: the mean of the K first actions weighted by exp((return - best) / temperature), as
+        plan_mppi weighs (on a discrete env the weighted share of action 1) — with a temperature]
+        [, returns float64 [N, K]][, best_length int32 [N]][, ess float64 [N]: (sum w)^2 / sum w^2, needs a temperature]).
+        The handle is left as it is.  A policy.DeepMLPPolicy is refused: the two-hidden-layer network is not served by this call yet."""
+        H, K, ps, ns, discount, temperature = self._plan_policy_args(H, K, policy, noise, discount, temperature)
+        if ess and temperature is None:
+            raise ValueError("ess=True needs a temperature")
+        st = self._start_rows(start_state)
+        ws = self._workspace("_plan_policy_ws", L.lib().emei_plan_policy_workspace_bytes, K)
+        dtype = torch.int64 if self.act_dim == 0 else torch.float32
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        act = new((self.n_envs,) + self._act_tail, dtype)
+        mean = new((self.n_envs,) + self._act_tail, torch.float32) if temperature is not None else None
+        ret, idx = new(self.n_envs, torch.float64), new(self.n_envs, torch.int32)
+        ln = new(self.n_envs, torch.int32) if length else None
+        rets = new((self.n_envs, K), torch.float64) if returns else None
+        es = new(self.n_envs, torch.float64) if ess else None
+        L.check(L.lib().emei_plan_policy(self._h, H, K, C.byref(ps), C.byref(ns), discount, 1.0 if temperature is None else temperature,
+                                         _ptr(st), _ptr(ws), _ptr(act), _ACT_DTYPES[dtype], _ptr(mean), _ptr(ret), _ptr(idx), _ptr(ln),
+                                         _ptr(rets), _ptr(es), _stream()))
+        return (act, ret, idx) + ((mean,) if mean is not None else ()) + ((rets,) if returns else ()) + ((ln,) if length else ()) \
+            + ((es,) if ess else ())
+
     @_on_device
     def mpc_mppi(self, T, H, K, seed, temperature, nominal, discount=1.0, sigma=None, refill=None, clamp=None, auto_reset=False,
                  out=None, diagnostics=False):

@@ -96,13 +96,15 @@ class MLPPolicy:
         p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
         return L.EmeiPolicy(C.sizeof(L.EmeiPolicy), self.hidden, _OUT_MODES[self.out], 0, p(self.w1), p(self.b1), p(self.w2), p(self.b2))
 
-    def __call__(self, obs, noise=None, t=None):
+    def __call__(self, obs, noise=None, t=None, candidate=0):
         """obs [N, obs_dim] -> actions [N] int64 (discrete), [N] float32 (one control) or [N, act_dim] float32: the normative
         arithmetic of emei_rollout_policy in torch float64 (products of float32 values are exact there; the sums run in ascending
         index order, one elementwise operation per term).  Needs bind(engine) first (Engine.rollout_policy does it).
         noise, t: a bound PolicyNoise and the step index — the action step t of emei_rollout_policy_noisy takes on these rows
         (row n is env n of the engine `noise` is bound to), the exploration term from noise.draws(engine, t): the same actions as the launch,
-        bit for bit under out="clip" with a given std and on the discrete envs."""
+        bit for bit under out="clip" with a given std and on the discrete envs.
+        candidate: whose word stream the exploration term is drawn from — k > 0: the action candidate k of Engine.plan_policy takes at
+        step t on these rows (its candidate 0 takes no noise at all: policy(obs)); the default 0 is the rollout's own stream."""
         if self.discrete is None:
             raise ValueError("MLPPolicy: bind(engine) first (which env's action space is this for?)")
         if (noise is None) != (t is None):
@@ -121,19 +123,19 @@ class MLPPolicy:
         w2 = self.w2.to(torch.float64)
         for j in range(h.shape[1]):
             y = y + w2[None, :, j] * h[:, j:j + 1]
-        return self._output(x, h, y, noise, t)
+        return self._output(x, h, y, noise, t, candidate)
 
-    def _output(self, x, h, y, noise, t):
+    def _output(self, x, h, y, noise, t, candidate=0):
         """what follows y: the threshold / epsilon-greedy of the discrete envs, or the noise term and the clip / tanh clause; h is what
         the output layer read (the log-std head reads it too)"""
         if self.discrete:
             greedy = (y[:, 0] >= 0).to(torch.int64)
             if noise is None:
                 return greedy
-            explore, coin = noise.draws(noise.bound_engine(), t)
+            explore, coin = noise.draws(noise.bound_engine(), t, candidate)
             return torch.where(explore != 0, coin.to(torch.int64), greedy)
         if noise is not None:  # the last term of the sum: y_q + (double)s_q * (double)z_q
-            z = noise.draws(noise.bound_engine(), t).reshape(x.shape[0], self.n_out)
+            z = noise.draws(noise.bound_engine(), t, candidate).reshape(x.shape[0], self.n_out)
             y = y + noise.scale(h).to(torch.float64) * z.to(torch.float64)
         if self.out == "tanh":
             a = (0.5 * (self.hi + self.lo) + 0.5 * (self.hi - self.lo) * torch.tanh(y)).to(torch.float32)
@@ -189,7 +191,7 @@ class DeepMLPPolicy(MLPPolicy):
         return L.EmeiPolicyDeep(C.sizeof(L.EmeiPolicyDeep), self.hidden1, self.hidden2, _OUT_MODES[self.out], p(self.w1), p(self.b1),
                                 p(self.w2), p(self.b2), p(self.w3), p(self.b3), 0)
 
-    def __call__(self, obs, noise=None, t=None):
+    def __call__(self, obs, noise=None, t=None, candidate=0):
         """MLPPolicy.__call__ for the two-hidden-layer network: the normative arithmetic of emei_rollout_policy_deep in torch float64,
         one elementwise operation per term, every sum in ascending index order; the same actions as the launch (bit for bit where
         MLPPolicy's are)."""
@@ -210,7 +212,7 @@ class DeepMLPPolicy(MLPPolicy):
         w3 = self.w3.to(torch.float64)
         for i in range(h.shape[1]):
             y = y + w3[None, :, i] * h[:, i:i + 1]
-        return self._output(x, h, y, noise, t)
+        return self._output(x, h, y, noise, t, candidate)
 
 
 class PolicyNoise:
@@ -281,19 +283,22 @@ class PolicyNoise:
         return L.EmeiPolicyNoise(C.sizeof(L.EmeiPolicyNoise), self.mode, self.seed & (2**64 - 1), self.sigma, p(self.std), p(self.ws),
                                  p(self.bs), self.log_std_min, self.log_std_max, 0)
 
-    def draws(self, engine, t):
+    def draws(self, engine, t, candidate=0):
         """what step t draws for every env of `engine`, obtained from the DEVICE through Engine.sample_candidates (candidate 0
-        under the key seed + t is the noise stream).  Continuous envs: z float32 [N(, act_dim)] = 8 * (the clipped Gaussian candidate
+        under the key seed + t is the noise stream; candidate k > 0 is the stream of Engine.plan_policy's candidate k).  Continuous envs: z float32 [N(, act_dim)] = 8 * (the clipped Gaussian candidate
         with mean 0 and sigma 0.125) — exact: |z| <= 5.77, so 0.125 z never reaches a ctrlrange of +-1 or +-3, and scaling by a power
         of two is exact.  Discrete envs: (explore, coin) [N] int64, the Bernoulli draws with p = epsilon at t = 0 and p = 0.5 at t = 1."""
         eng = engine
         key = self.seed + int(t)
+        k = int(candidate)
+        if k < 0:
+            raise ValueError(f"candidate={candidate} must be >= 0")
         if eng.act_dim == 0:
             nominal = torch.tensor([self.sigma, 0.5], dtype=torch.float32, device=eng.device)[:, None].repeat(1, eng.n_envs).contiguous()
-            d = eng.sample_candidates(2, 1, key, nominal=nominal)
-            return d[0, :, 0], d[1, :, 0]
+            d = eng.sample_candidates(2, k + 1, key, nominal=nominal)
+            return d[0, :, k], d[1, :, k]
         zeros = torch.zeros((1, eng.n_envs) + eng._act_tail, dtype=torch.float32, device=eng.device)
-        return 8.0 * eng.sample_candidates(1, 1, key, nominal=zeros, sigma=0.125)[0, :, 0]
+        return 8.0 * eng.sample_candidates(1, k + 1, key, nominal=zeros, sigma=0.125)[0, :, k]
 
     def scale(self, h):
         """s [N, n_out] float32 for the rows whose hidden activations (float64 [N, hidden], or the inputs without a hidden layer)

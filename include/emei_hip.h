@@ -58,7 +58,10 @@ extern "C" {
  *    EMEI_KERNEL_PEND_POLICY_NOISY / EMEI_KERNEL_BODY_POLICY_NOISY / EMEI_KERNEL_BODY_POLICY_NOISY_RK4;
  *    emei_rollout_policy_deep and emei_evaluate_policies_deep with struct emei_policy_deep (the three policy calls for a network with
  *    two ReLU hidden layers of up to EMEI_POLICY_DEEP_MAX_HIDDEN units each; struct emei_policy and its entry points are unchanged),
- *    EMEI_KERNEL_PEND_POLICY_DEEP / EMEI_KERNEL_BODY_POLICY_DEEP / EMEI_KERNEL_BODY_POLICY_DEEP_RK4. */
+ *    EMEI_KERNEL_PEND_POLICY_DEEP / EMEI_KERNEL_BODY_POLICY_DEEP / EMEI_KERNEL_BODY_POLICY_DEEP_RK4;
+ *    emei_plan_policy_workspace_bytes, emei_plan_policy (shooting and MPPI around a feedback policy: n_candidates closed-loop rollouts
+ *    of one struct emei_policy per env under struct emei_policy_noise, the policy evaluated in the lanes that score them; the handle
+ *    is untouched, no kernel id). */
 #define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
@@ -730,6 +733,75 @@ EMEI_API int emei_rollout_policy_noisy(emei_env* h, int32_t n_steps, const emei_
 EMEI_API int emei_evaluate_policies(emei_env* h, int32_t horizon, int32_t n_policies, const emei_policy* stacked, double discount,
                                     const double* start_state, double* return_out, int32_t* length_out, float* final_obs_out,
                                     void* stream);
+
+/* Planning around a feedback policy, the planner of model-based offline RL (MBOP, LOOP, POLO; the policy-prior half of POPLIN and
+ * TD-MPC): per env, n_candidates CLOSED-LOOP rollouts of one policy under exploration noise from the env's start state, scored on the
+ * true dynamics, and the best or the return-weighted first action.  emei_plan_shooting and emei_plan_mppi draw their candidates around
+ * an open-loop nominal; here the candidate is the policy itself reacting to every observation of its own rollout, evaluated in the
+ * lane that scores it: the [horizon, n_envs, n_candidates] actions never exist in memory.  `policy` and `noise` are
+ * emei_rollout_policy_noisy's structs with DEVICE pointers, read during the launches and not retained; they must not overlap any
+ * output or the workspace.
+ *
+ * Semantics (normative).  Candidate (i, k), i < n_envs, k < n_candidates, g = env_index_offset + i, is a rollout of `horizon` steps:
+ *   1. Start and observe.  Clauses 1 and 2 of emei_evaluate_policies: the start is the handle's current state (start_state NULL) or
+ *      row i of start_state [n_envs, state_dim] float64, narrowed as emei_set_state narrows it; x_0 is the float32 observation of that
+ *      state, x_t the float32 observation row that step t - 1 emits.
+ *   2. Policy.  a_t = clause 2 ("Policy") of emei_rollout_policy with the noise clause of emei_rollout_policy_noisy, where step t of
+ *      candidate k owns the word stream
+ *          W[m] = philox4x32_10(key = seed + t (mod 2^64), counter = (g lo, g hi, k, m >> 2)).v[m & 3]
+ *      — the noisy rollout's stream with k in the counter word that holds 0 there.  All three noise modes are served: GAUSS with std
+ *      or sigma, GAUSS_HEAD, EPS_GREEDY.
+ *      Candidate 0 takes NO noise: its y_q is the deterministic one (selected after the draw, not by a zero std: a y_q of -0.0 keeps
+ *      its sign, a non-finite std does not reach it), and on a discrete env it never explores.  Candidate 0 is the prior itself, so
+ *      the plan is never worse than the policy under the model.  (The words of candidate 0 are the ones emei_rollout_policy_noisy
+ *      would consume under the same seed; this call does not use them.)
+ *   3. Step and score.  Clause 4 of emei_evaluate_policies: the per-step arithmetic emei_rollout runs for this handle; ret(i, k) = sum
+ *      over t < L of discount^t * (double)(float)r_t, float64 in step order, discount^t a float64 running product from 1.0; L(i, k) =
+ *      the first terminal step + 1, or horizon.  No observation noise, no TimeLimit, no auto-reset.  A candidate past its terminal
+ *      step keeps stepping without accumulating; a wave leaves once none of its lanes is live.
+ *   4. Select.  (k*, r*) is the first candidate under the planner's order (emei_plan_shooting): ret_a > ret_b wins, NaN comes last,
+ *      ties go to the lower k.
+ *   5. Weights.  emei_plan_mppi's case analysis with `temperature` on r_k = ret(i, k), and its summation tree: lane l adds the
+ *      candidates k = l, l + 64, .. in ascending order, then a butterfly over the lanes with d = 1, 2, .., 32 — a function of k alone.
+ * Outputs, per env i:
+ *   best_action_out[i(, :)]  candidate k*'s action at t = 0, in action_dtype (U8 / I32 / I64 discrete, F32 continuous).  Required.
+ *   mean_action_out[i(, a)]  float32 [n_envs(, act_dim)]: (float)(sum_k w_k * (double)a_k[0, a] / Z), a_k[0, :] candidate k's float32
+ *                            action at t = 0 (0.f / 1.f on the discrete envs: the weighted share of action 1); sums and quotient in
+ *                            float64, one rounding.  NULL: skipped.
+ *   best_return_out[i], best_index_out[i], best_length_out[i]   r*, k*, L(i, k*).  Each may be NULL.
+ *   return_out[i, k]         float64 [n_envs, n_candidates]: ret(i, k).  May be NULL.
+ *   ess_out[i]               Z^2 / sum_k w_k^2, float64.  May be NULL.
+ * With mean_action_out and ess_out both NULL no weights are formed and `temperature` is neither consulted nor checked.
+ * Consequences.  Sharding: results depend on g, not on the shard (up to the lane dependence of r_k the HalfCheetah documents, 1e-9
+ * relative).  Stream: the call neither allocates nor synchronises (capturable); repeated calls and graph replays give the same bits.
+ * Candidate 0 equals emei_evaluate_policies with n_policies = 1 on the same policy, start and discount (return and length; bit for bit
+ * except for the HalfCheetah's lane lending).  n_candidates = 1 is legal: the deterministic policy's first action, return and length.
+ * The actions of candidate k are those the per-step loop "observe, evaluate the policy with candidate k's noise, emei_step" takes;
+ * fed to emei_evaluate_sequences they give return_out and the lengths.  The handle is untouched: state, counters, reset key, frozen
+ * snapshot, the done mask and emei_last_rollout_kernel.  Newton solves that end at the iteration cap count into
+ * emei_get_solver_cap_hits, as for the other queries.
+ * Kernels: pend_policy_plan_kernel / body_policy_plan_kernel — the DRAWN + KEEP loop of the family's plan kernel, one lane per
+ * candidate j = i * n_candidates + k, the weights read through wave-uniform addresses (scalar loads) — then
+ * plan_policy_finish_kernel, one wave per env.  EMEI_POLICY_OUT_TANH and EMEI_POLICY_NOISE_GAUSS_HEAD are not pinned bit for bit, as
+ * in the rollouts.
+ * workspace: emei_plan_policy_workspace_bytes(n_envs, n_candidates) bytes of device memory, 16-byte aligned, contents irrelevant
+ * before and after.  The first launch STORES every candidate's action of step 0 (the finish launch reads them back instead of
+ * evaluating the policy again), so the workspace is emei_plan_mppi's plus 24 bytes per candidate (six float32 slots, the widest
+ * action of the envs: the function takes no handle).
+ * EMEI_ERR_INVALID before any HIP call, each message naming the argument, in this order: horizon < 1; n_candidates < 1; discount
+ * outside (0, 1]; with a non-NULL mean_action_out or ess_out, temperature not finite or <= 0; emei_rollout_policy's struct checks up
+ * to and including policy.reserved; NULL noise, then emei_rollout_policy_noisy's noise checks in their order; a NULL handle; NULL w2 or
+ * b2, hidden > 0 with NULL w1 or b1; n_envs * n_candidates > 2^31 - 1; a wrong action_dtype; NULL workspace, then NULL
+ * best_action_out; a GAUSS mode on a discrete env or EPS_GREEDY on a continuous one.  EMEI_ERR_STATE without a state and without
+ * start_state. */
+/* bytes of device scratch emei_plan_policy needs for this shape; host only, no handle, no HIP call.
+ * Negative (EMEI_ERR_INVALID) where emei_plan_shooting_workspace_bytes is. */
+EMEI_API int64_t emei_plan_policy_workspace_bytes(int64_t n_envs, int32_t n_candidates);
+EMEI_API int emei_plan_policy(emei_env* h, int32_t horizon, int32_t n_candidates, const emei_policy* policy,
+                              const emei_policy_noise* noise, double discount, double temperature, const double* start_state,
+                              void* workspace, void* best_action_out, int action_dtype, float* mean_action_out,
+                              double* best_return_out, int32_t* best_index_out, int32_t* best_length_out, double* return_out,
+                              double* ess_out, void* stream);
 
 /* emei_rollout_policy / emei_rollout_policy_noisy / emei_evaluate_policies for a network with TWO ReLU hidden layers — the shape of
  * the actors the reference's zoo trains (stable-baselines3 MlpPolicy: 256-256 ReLU, SAC with a mean head, a log-std head and a tanh
