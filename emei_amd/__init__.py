@@ -28,7 +28,7 @@ from .envs import (  # noqa: F401
 
 
 def __getattr__(name):  # the policy classes need torch: imported on first use, like the engine
-    if name in ("MLPPolicy", "DeepMLPPolicy", "PolicyNoise", "PolicyPopulation", "DeepPolicyPopulation"):
+    if name in ("MLPPolicy", "DeepMLPPolicy", "PolicyNoise", "PolicyPopulation", "DeepPolicyPopulation", "DeepValueFunction"):
         from . import policy
 
         return getattr(policy, name)

@@ -223,6 +223,8 @@ SYMBOLS = {
     "emei_rollout_policy_deep": (C.c_int, [_vp, _i32, C.POINTER(EmeiPolicyDeep), C.POINTER(EmeiPolicyNoise), _vp, C.c_int, _vp, _vp, _vp, _u32,
                                            _vp]),
     "emei_evaluate_policies_deep": (C.c_int, [_vp, _i32, _i32, C.POINTER(EmeiPolicyDeep), _dbl, _vp, _vp, _vp, _vp, _vp]),
+    "emei_plan_policy_deep": (C.c_int, [_vp, _i32, _i32, C.POINTER(EmeiPolicyDeep), C.POINTER(EmeiPolicyNoise), C.POINTER(EmeiPolicyDeep),
+                                        _dbl, _dbl, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "emei_compact_done": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emei_get_counters": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emei_episode_init_obs": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),

@@ -1334,7 +1334,8 @@ extern "C" EMEI_API int emei_plan_policy(emei_env* h, int32_t horizon, int32_t n
 // emei_rollout_policy_deep / emei_evaluate_policies_deep: the policy calls above for struct emei_policy_deep (two hidden layers), on
 // kernels of their own (pend_policy_rollout_deep_kernel / body_policy_rollout_deep_kernel, pend_policy_eval_deep_kernel /
 // body_policy_eval_deep_kernel).  The refusals mirror check_policy_struct / check_policy_weights.
-static int check_policy_deep_struct(const char* fn, const char* arg, const emei_policy_deep* policy) {
+// with_out_mode false: the terminal value network of emei_plan_policy_deep, whose out_mode is ignored
+static int check_policy_deep_struct(const char* fn, const char* arg, const emei_policy_deep* policy, bool with_out_mode = true) {
     if (!policy) return fail(EMEI_ERR_INVALID, "%s: null %s", fn, arg);
     if (policy->struct_size != sizeof(emei_policy_deep))
         return fail(EMEI_ERR_INVALID, "%s: %s.struct_size=%u != sizeof(emei_policy_deep)=%zu", fn, arg, policy->struct_size,
@@ -1345,7 +1346,7 @@ static int check_policy_deep_struct(const char* fn, const char* arg, const emei_
     if (policy->hidden2 < 1 || policy->hidden2 > EMEI_POLICY_DEEP_MAX_HIDDEN)
         return fail(EMEI_ERR_INVALID, "%s: %s.hidden2=%d is outside [1, EMEI_POLICY_DEEP_MAX_HIDDEN=%d]", fn, arg, policy->hidden2,
                     EMEI_POLICY_DEEP_MAX_HIDDEN);
-    if (policy->out_mode != EMEI_POLICY_OUT_CLIP && policy->out_mode != EMEI_POLICY_OUT_TANH)
+    if (with_out_mode && policy->out_mode != EMEI_POLICY_OUT_CLIP && policy->out_mode != EMEI_POLICY_OUT_TANH)
         return fail(EMEI_ERR_INVALID, "%s: unknown %s.out_mode=%d", fn, arg, policy->out_mode);
     if (policy->reserved != 0) return fail(EMEI_ERR_INVALID, "%s: %s.reserved=%lld must be 0", fn, arg, (long long)policy->reserved);
     return EMEI_OK;
@@ -1451,6 +1452,75 @@ extern "C" EMEI_API int emei_evaluate_policies_deep(emei_env* h, int32_t horizon
         L.n_steps = horizon, L.obs_out = final_obs_out;
         rc = body_launch(L);
     }
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+}
+
+// emei_plan_policy_deep: emei_plan_policy for struct emei_policy_deep, with an optional terminal value network.  First launch: the
+// family's deep policy plan kernel (pendulum_kernels.h:pend_policy_plan_deep_kernel, body_kernels.h:body_policy_plan_deep_kernel),
+// one-wave blocks over the same lanes j = i * n_candidates + k; second launch: plan_policy_finish_kernel, as it is.  The workspace
+// is emei_plan_policy's, laid out as there.  Nothing of the handle is written (h->last_kernel included).
+extern "C" EMEI_API int emei_plan_policy_deep(emei_env* h, int32_t horizon, int32_t n_candidates, const emei_policy_deep* policy,
+                                              const emei_policy_noise* noise, const emei_policy_deep* value, double discount,
+                                              double temperature, const double* start_state, void* workspace, void* best_action_out,
+                                              int action_dtype, float* mean_action_out, double* best_return_out, int32_t* best_index_out,
+                                              int32_t* best_length_out, double* return_out, double* ess_out, void* stream) {
+    const char* fn = "emei_plan_policy_deep";
+    if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
+    if (mean_action_out || ess_out)
+        if (int rc = check_temperature(fn, temperature)) return rc;
+    if (int rc = check_policy_deep_struct(fn, "policy", policy)) return rc;
+    if (int rc = check_policy_noise(fn, noise)) return rc;
+    if (value)
+        if (int rc = check_policy_deep_struct(fn, "value", value, false)) return rc;
+    if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = check_policy_deep_weights(fn, "policy", policy)) return rc;
+    if (value)
+        if (int rc = check_policy_deep_weights(fn, "value", value)) return rc;
+    if (int rc = check_plan_lanes(fn, h, n_candidates)) return rc;
+    if (action_dtype < EMEI_ACT_U8 || action_dtype > EMEI_ACT_F32 || (h->act_dim > 0) != (action_dtype == EMEI_ACT_F32))
+        return fail(EMEI_ERR_INVALID, "%s: action_dtype=%d: best_action_out is uint8 / int32 / int64 for the discrete envs, float32 for the "
+                                      "continuous ones", fn, action_dtype);
+    if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
+    if (!best_action_out) return fail(EMEI_ERR_INVALID, "%s: null best_action_out", fn);
+    if ((h->act_dim > 0) == (noise->mode == EMEI_POLICY_NOISE_EPS_GREEDY))
+        return fail(EMEI_ERR_INVALID, "%s: noise.mode=%d: the Gaussian modes are for the continuous envs, EMEI_POLICY_NOISE_EPS_GREEDY for "
+                                      "the discrete ones", fn, noise->mode);
+    EMEI_ON_DEVICE(h, fn);
+    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    PolicyDeepArgs pa = policy_deep_args(h, policy);
+    pa.action_dtype = action_dtype, pa.noisy = 1;
+    PolicyDeepArgs va{};  // w1 null: no terminal value
+    if (value) {
+        va.w1 = value->w1, va.b1 = value->b1, va.w2 = value->w2, va.b2 = value->b2, va.w3 = value->w3, va.b3 = value->b3;
+        va.hidden1 = value->hidden1, va.hidden2 = value->hidden2;
+    }
+    PolicyNoiseArgs na{};
+    na.seed = noise->seed, na.mode = noise->mode, na.sigma = (float)noise->sigma;
+    if (noise->mode == EMEI_POLICY_NOISE_GAUSS) na.std = noise->std;
+    if (noise->mode == EMEI_POLICY_NOISE_GAUSS_HEAD)
+        na.ws = noise->ws, na.bs = noise->bs, na.log_std_min = noise->log_std_min, na.log_std_max = noise->log_std_max;
+    const int64_t nk = h->cfg.n_envs * (int64_t)n_candidates;
+    PlanLaunch p;
+    p.mode = PLAN_DRAWN_KEEP, p.start_rows = start_state, p.n_candidates = n_candidates, p.discount = discount;
+    p.partials = workspace;
+    p.return_out = return_out ? return_out : plan_returns(h, n_candidates, workspace);
+    p.first_actions = (float*)(plan_returns(h, n_candidates, workspace) + nk);
+    int rc;
+    if (!steps_as_body(h->cfg)) {
+        PendLaunch L = pend_base(h, stream);
+        L.op = PEND_OP_POLICY_PLAN_DEEP, L.plan = p, L.policy_deep = pa, L.policy_noise = na, L.policy_value = va;
+        L.n_steps = horizon;
+        rc = pend_launch(L);
+    } else {
+        BodyLaunch L = body_base(h, stream);
+        L.op = BODY_OP_POLICY_PLAN_DEEP, L.plan = p, L.policy_deep = pa, L.policy_noise = na, L.policy_value = va;
+        L.n_steps = horizon;
+        rc = body_launch(L);
+    }
+    if (rc == EMEI_OK)
+        rc = launch_plan_policy_finish(workspace, p.return_out, p.first_actions, h->cfg.n_envs, n_candidates, h->act_dim, temperature,
+                                       best_action_out, action_dtype, mean_action_out, best_return_out, best_index_out, best_length_out,
+                                       ess_out, (hipStream_t)stream);
     return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
 }
 

@@ -173,7 +173,8 @@ enum BodyOp { BODY_OP_ROLLOUT = 0, BODY_OP_RESET, BODY_OP_GET_OBS, BODY_OP_INIT_
               BODY_OP_POLICY_NOISY /* emei_rollout_policy_noisy: body_policy_rollout_noisy_kernel */,
               BODY_OP_POLICY_DEEP /* emei_rollout_policy_deep: body_policy_rollout_deep_kernel */,
               BODY_OP_POLICY_EVAL_DEEP /* emei_evaluate_policies_deep: body_policy_eval_deep_kernel */,
-              BODY_OP_POLICY_PLAN /* emei_plan_policy: body_policy_plan_kernel */ };
+              BODY_OP_POLICY_PLAN /* emei_plan_policy: body_policy_plan_kernel */,
+              BODY_OP_POLICY_PLAN_DEEP /* emei_plan_policy_deep: body_policy_plan_deep_kernel */ };
 
 // What BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM take beyond the base descriptor: n_steps control steps of the planner with plan.n_candidates
 // candidates over `horizon` steps under plan.discount; plan.cand carries the call's seed, sigma and the ctrlrange (its nominal is
@@ -240,6 +241,9 @@ struct BodyLaunch {
                                       // BODY_OP_POLICY_EVAL_DEEP: BODY_OP_POLICY_EVAL's fields with the STACKED networks here
     // BODY_OP_POLICY_PLAN (emei_plan_policy): `policy` and `policy_noise` as BODY_OP_POLICY_NOISY takes them (actions_out unused), `plan`
     // what PLAN_DRAWN_KEEP takes (cand unused) plus plan.first_actions; n_steps = the horizon
+    PolicyDeepArgs policy_value = {};  // BODY_OP_POLICY_PLAN_DEEP (emei_plan_policy_deep): BODY_OP_POLICY_PLAN's fields with the network
+                                       // in `policy_deep` (noisy set) and the terminal value network here (w1 null: no bootstrap;
+                                       // out_mode, lo, hi and noisy unused)
 };
 int body_launch(const BodyLaunch& L);  // body_dispatch.hip
 
@@ -1511,6 +1515,107 @@ __global__ void __launch_bounds__(kWave)
     }
 }
 
+// emei_plan_policy_deep (the normative text: include/emei_hip.h) for the bodies: body_policy_plan_kernel's loop — the action of step
+// t + 1 evaluated at the end of step t under nz.seed + t + 1, the padding lanes parked, i divided in 32 bits, the score kept with
+// selects (the comments there say why) — under the network with two hidden layers, as ONE-WAVE blocks with body_policy_eval_deep_kernel's
+// static LDS (the trig table, the body's scratch at stride kWave); the block's dynamic LDS is the wave's h1 tile, sized by the wider
+// first layer of `pol` and `val`.  Lane l of block b holds candidate j = 64 b + l: plan_reduce_wave's slot (j >> 6) + i is the one
+// the 256-thread kernel writes.
+// Terminal value (val.w1 non-null, wave-uniform): `live` also falls at t == horizon - 1, so the terminal bits have a flag of their
+// own, `noterm` ("no terminal bit so far"; a lane's later bits change nothing once it has fallen, a padding lane starts with it
+// down).  The loop leaves before step horizon - 1 only once every lane has terminated; otherwise every lane has stepped to x_H,
+// which `o` still holds: the wave evaluates `val` on it in the same tile, raw (no output clause), and the lanes with the flag up take
+// ret + g_H * (double)v by a select.
+template <class Body, bool RK4>
+__global__ void __launch_bounds__(kWave)
+    body_policy_plan_deep_kernel(const typename Body::real* state, const double* start_rows, int64_t n_envs, int32_t n_cand,
+                                 int32_t horizon, double discount, int freq_rate, int semi, typename Body::Model m,
+                                 const SinCosEntry* trig_tab, unsigned long long* cap_hits, const PolicyDeepArgs pol,
+                                 const PolicyNoiseArgs nz, const PolicyDeepArgs val, uint64_t env_offset, double* ret_out, float* first_out,
+                                 PlanPartial* partials) {
+    using R = typename Body::real;
+    constexpr int NS = Body::NS, NO = Body::NO, NA = Body::NA;
+    extern __shared__ __attribute__((aligned(16))) float4 deep_h1_s[];
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table<kWave>(trig_s, trig_tab);  // every thread reaches the barrier
+    TrigCtx trig;
+    trig.tab = trig_s;
+    if constexpr (Body::kScratchPerLane > 0) {
+        __shared__ __attribute__((aligned(16))) R scratch_s[Body::kScratchPerLane * kWave];
+        trig.scratch = scratch_s;
+    }
+    trig.scratch_stride = kWave;
+    trig.cap_hits = cap_hits;
+    const int lane = threadIdx.x;
+    const int64_t nk = n_envs * n_cand;
+    const int64_t j = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const bool active = j < nk;
+    // no divergent branch around the loads, and a 32-bit division (nk <= 2^31 - 1, abi.hip): see body_policy_plan_kernel
+    const uint32_t ju = active ? (uint32_t)j : 0u, iu = ju / (uint32_t)n_cand;
+    const int64_t i = iu;
+    static_assert(NA <= kPlanPolicyMaxAct, "first_out holds kPlanPolicyMaxAct float32 slots per candidate (abi.hip sizes the workspace)");
+    const uint32_t kc = ju - iu * (uint32_t)n_cand;
+    const uint64_t genv = env_offset + (uint64_t)i;
+    R s[NS], parked[NS];
+    if (start_rows) {  // wave-uniform; the caller's float64 rows are narrowed as emei_set_state narrows them (util_kernels.hip)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = (R)start_rows[i * NS + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = state[(int64_t)k * n_envs + i];
+    }
+    Body::park(parked);  // as body_rollout_kernel's padding lanes
+    float act[NA];
+    float o[NO];  // the float32 row the lane holds: x_0, then what each step emits (x_H after the last one, for the value)
+    {  // x_0: the float32 observation of the START state (a padding lane: env 0's), as emei_get_obs rounds it
+        double od[NO];
+        Body::obs_of(s, od, m);
+#pragma unroll
+        for (int k = 0; k < NO; ++k) o[k] = (float)od[k];
+        policy_eval_deep_t<NO, NA, false>(pol, nz, nz.seed, genv, o, act, deep_h1_s, lane, kc, kc != 0u);
+    }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) s[k] = active ? s[k] : parked[k];
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < NA; ++k) first_out[j * NA + k] = act[k];
+    }
+    double ret = 0.0, g = 1.0;
+    int32_t len = 0;  // steps counted so far (ret and len stop changing with the lane's last counted step)
+    bool live = active, noterm = active;
+    for (int t = 0; t < horizon; ++t) {
+        R ctrl[NA];  // padding lanes: zero, as the rollout's staging gives them
+#pragma unroll
+        for (int k = 0; k < NA; ++k) ctrl[k] = active ? (R)act[k] : R(0);
+        R pre[NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) pre[k] = s[k];
+        typename Body::Warm warm{};
+        for (int k = 0; k < freq_rate; ++k) body_substep<Body, RK4>(s, ctrl, m, semi != 0, trig, warm);
+        R rew;
+        bool term;
+        Body::outputs(s, pre, ctrl, m, freq_rate, o, rew, term, trig);
+        // selects, not a block under `live`: see body_policy_plan_kernel
+        const double counted = ret + g * (double)(float)rew, g_next = g * discount;
+        ret = live ? counted : ret;
+        g = live ? g_next : g;
+        len = live ? t + 1 : len;
+        noterm = noterm & !term;
+        live = live & !(term | (t == horizon - 1));
+        if (__ballot(live) == 0ull) break;  // wave-uniform
+        policy_eval_deep_t<NO, NA, false>(pol, nz, nz.seed + (uint64_t)t + 1u, genv, o, act, deep_h1_s, lane, kc, kc != 0u);  // wave-uniform
+    }
+    if (val.w1 && __ballot(noterm) != 0ull) {  // wave-uniform: some lane never terminated, so the loop ran to x_H
+        float v[1];
+        policy_eval_deep_t<NO, 1, false, true>(val, nz, 0, 0, o, v, deep_h1_s, lane);  // val.noisy == 0: nz is never read
+        const double tail = g * (double)v[0];  // rounded to float64, then added
+        const double boot = ret + tail;
+        ret = noterm ? boot : ret;
+    }
+    plan_reduce_wave(j, nk, i, n_cand, ret, len, partials);
+    if (active) ret_out[j] = ret;
+}
+
 // the one launch of body_plan_kernel: DRAWN kernels read no actions and write no lengths or final observations, and only KEEP
 // gives them a return_out; one lane per candidate, n * n_candidates < 2^31 (checked in abi.hip)
 template <class Body, bool RK4, bool DRAWN, bool KEEP, class Spec>
@@ -1680,6 +1785,28 @@ static int launch_body(const BodyLaunch& L) {
                 hipLaunchKernelGGL((body_policy_plan_kernel<Body, false>), pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state, P.start_rows,
                                    L.n, P.n_candidates, L.n_steps, P.discount, L.freq_rate, semi, m, (const SinCosEntry*)L.trig, L.cap_hits,
                                    L.policy, L.policy_noise, L.env_offset, P.return_out, P.first_actions, (PlanPartial*)P.partials);
+            break;
+        }
+        case BODY_OP_POLICY_PLAN_DEEP: {  // emei_plan_policy_deep: BODY_OP_POLICY_PLAN's lanes as one-wave blocks, the tile as dynamic LDS
+            const PlanLaunch& P = L.plan;
+            if (!P.partials || !P.return_out || !P.first_actions) return EMEI_ERR_INVALID;
+            const dim3 pgrid((unsigned)((L.n * P.n_candidates + kWave - 1) / kWave));
+            const int semi = (int)(L.integrator == EMEI_INTEG_SEMI_IMPLICIT);
+            const int h1 = L.policy_value.w1 && L.policy_value.hidden1 > L.policy_deep.hidden1 ? L.policy_value.hidden1 : L.policy_deep.hidden1;
+            const uint32_t tile = policy_deep_tile_bytes(h1);
+            if (L.integrator == EMEI_INTEG_RK4) {
+                if (int rc = policy_deep_lds_opt_in<body_policy_plan_deep_kernel<Body, true>>()) return rc;
+                hipLaunchKernelGGL((body_policy_plan_deep_kernel<Body, true>), pgrid, dim3(kWave), tile, L.stream, (const R*)L.state,
+                                   P.start_rows, L.n, P.n_candidates, L.n_steps, P.discount, L.freq_rate, 0, m, (const SinCosEntry*)L.trig,
+                                   L.cap_hits, L.policy_deep, L.policy_noise, L.policy_value, L.env_offset, P.return_out, P.first_actions,
+                                   (PlanPartial*)P.partials);
+            } else {
+                if (int rc = policy_deep_lds_opt_in<body_policy_plan_deep_kernel<Body, false>>()) return rc;
+                hipLaunchKernelGGL((body_policy_plan_deep_kernel<Body, false>), pgrid, dim3(kWave), tile, L.stream, (const R*)L.state,
+                                   P.start_rows, L.n, P.n_candidates, L.n_steps, P.discount, L.freq_rate, semi, m, (const SinCosEntry*)L.trig,
+                                   L.cap_hits, L.policy_deep, L.policy_noise, L.policy_value, L.env_offset, P.return_out, P.first_actions,
+                                   (PlanPartial*)P.partials);
+            }
             break;
         }
         case BODY_OP_OCCUPANCY: {

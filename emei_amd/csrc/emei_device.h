@@ -886,9 +886,17 @@ constexpr int kDeepBlockI = 4;  // units of h2 whose float64 accumulators share 
 // clamped to hidden2 - 1 and its surplus results dropped.  h2_i then joins y (and the log-std head's l) in ascending i, so nothing
 // of size hidden2 is ever live.  Every accumulator adds its terms in ascending index order with fma() on exact products: the
 // specification's sums, bit for bit.  The weights are wave-uniform scalar loads, as policy_eval_t's.
-template <int NO, int NA, bool DISCRETE>
+// cand / noise_on (emei_plan_policy_deep), as policy_eval_t's: the lane's candidate k in the counter word that holds 0 for the
+// rollouts, and whether the lane takes its noise at all — candidate 0 does not, by a select after the draw.  The defaults are
+// constants the compiler folds: the rollout and population kernels' instantiations are the code they were.
+// RAW (kernel-internal, no out_mode of the ABI selects it; DISCRETE = false, pa.noisy = 0): act[q] = (float)y_q with no output
+// clause at all — the terminal value of emei_plan_policy_deep, a NaN kept.  A template argument, not a runtime mode, so that the
+// existing instantiations carry no test for it.
+template <int NO, int NA, bool DISCRETE, bool RAW = false>
 __device__ __forceinline__ void policy_eval_deep_t(const PolicyDeepArgs& pa, const PolicyNoiseArgs& nz, uint64_t key, uint64_t g,
-                                                   const float (&x)[NO], float (&act)[NA], float4* tile, int lane) {
+                                                   const float (&x)[NO], float (&act)[NA], float4* tile, int lane, uint32_t cand = 0u,
+                                                   bool noise_on = true) {
+    static_assert(!(RAW && DISCRETE), "the raw output is the continuous evaluation without its output clause");
     const PolicyWeights w1 = (PolicyWeights)pa.w1, b1 = (PolicyWeights)pa.b1, w2 = (PolicyWeights)pa.w2, b2 = (PolicyWeights)pa.b2;
     const PolicyWeights w3 = (PolicyWeights)pa.w3, b3 = (PolicyWeights)pa.b3;
     const int h1n = pa.hidden1, h2n = pa.hidden2;  // wave-uniform, as every index below
@@ -969,18 +977,22 @@ __device__ __forceinline__ void policy_eval_deep_t(const PolicyDeepArgs& pa, con
     }
     wave_lds_fence();  // the next evaluation's stores stay behind these reads
 
-    if constexpr (DISCRETE) {
+    if constexpr (RAW) {
+#pragma unroll
+        for (int q = 0; q < NA; ++q) act[q] = (float)y[q];
+        return;
+    } else if constexpr (DISCRETE) {
         bool one = y[0] >= 0.0;  // NaN -> 0
         if (noisy) {
-            CandidateWords cw(key, g, 0u);
+            CandidateWords cw(key, g, cand);
             const bool explore = u01(cw.word(0u)) < nz.sigma, coin = u01(cw.word(1u)) < 0.5f;
-            one = explore ? coin : one;
+            one = (explore & noise_on) ? coin : one;  // a select: without noise the lane never explores
         }
         act[0] = one ? 1.f : 0.f;
         return;
     } else {
         if (noisy) {
-            CandidateWords cw(key, g, 0u);
+            CandidateWords cw(key, g, cand);
             const PolicyWeights sd = (PolicyWeights)nz.std;
 #pragma unroll
             for (int p = 0; p < (NA + 1) / 2; ++p) {  // the pair (W[2p], W[2p + 1]) lies inside one Philox block
@@ -992,7 +1004,8 @@ __device__ __forceinline__ void policy_eval_deep_t(const PolicyDeepArgs& pa, con
                     float sq;
                     if (head) sq = (float)exp(fmin(fmax(l[q], (double)nz.log_std_min), (double)nz.log_std_max));
                     else sq = sd ? sd[q] : nz.sigma;
-                    y[q] = fma((double)sq, (double)zn[q & 1], y[q]);  // the last term of the sum
+                    const double yn = fma((double)sq, (double)zn[q & 1], y[q]);  // the last term of the sum
+                    y[q] = noise_on ? yn : y[q];  // a select: without noise y_q keeps its bits (the sign of -0.0 included)
                 }
             }
         }

@@ -7,7 +7,7 @@
 
 namespace emei {
 
-enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC, PEND_OP_MPC_CEM, PEND_OP_POLICY, PEND_OP_POLICY_EVAL, PEND_OP_POLICY_NOISY, PEND_OP_POLICY_DEEP, PEND_OP_POLICY_EVAL_DEEP, PEND_OP_POLICY_PLAN };
+enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC, PEND_OP_MPC_CEM, PEND_OP_POLICY, PEND_OP_POLICY_EVAL, PEND_OP_POLICY_NOISY, PEND_OP_POLICY_DEEP, PEND_OP_POLICY_EVAL_DEEP, PEND_OP_POLICY_PLAN, PEND_OP_POLICY_PLAN_DEEP };
 
 // emei_set_obs_peers: the gathered buffers the staged rollout kernel also writes every observation row to
 struct ObsPeers {
@@ -35,7 +35,7 @@ struct PlanLaunch {
     CandidateSpec cand = {};
     void* partials = nullptr;
     const float* sigma_map = nullptr;  // emei_plan_cem: non-null -> the draws take their sigma per entry (CandidateSpecMap)
-    float* first_actions = nullptr;  // PEND_OP_POLICY_PLAN / BODY_OP_POLICY_PLAN: [n * K(, act_dim)] float32, every candidate's action at t = 0
+    float* first_actions = nullptr;  // PEND_OP_POLICY_PLAN(_DEEP) / BODY_OP_POLICY_PLAN(_DEEP): [n * K(, act_dim)] float32, every candidate's action at t = 0
 };
 
 struct PendLaunch {
@@ -102,6 +102,9 @@ struct PendLaunch {
     // `plan` what PLAN_DRAWN_KEEP takes (cand unused: the candidates are the policy's noisy rollouts) plus plan.first_actions;
     // n_steps = the horizon
     PolicyDeepArgs policy_deep = {};
+    // PEND_OP_POLICY_PLAN_DEEP (emei_plan_policy_deep): PEND_OP_POLICY_PLAN's fields with the two-hidden-layer network in `policy_deep`
+    // (noisy set) and the terminal value network in `policy_value` (w1 null: no bootstrap; out_mode, lo, hi and noisy unused)
+    PolicyDeepArgs policy_value = {};
 };
 
 // The deep policy kernels keep h1 in dynamic LDS (emei_device.h:policy_deep_tile_bytes, up to 64 KiB): the opt-in HIP wants of a

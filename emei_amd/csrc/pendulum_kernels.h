@@ -1079,6 +1079,74 @@ __global__ void __launch_bounds__(kWave)
     }
 }
 
+// emei_plan_policy_deep (the normative text: include/emei_hip.h): pend_policy_plan_kernel's loop under the network with two hidden
+// layers, as ONE-WAVE blocks (the block's dynamic LDS is the wave's h1 tile, sized by the wider first layer of `pol` and `val`): lane
+// l of block b holds candidate j = 64 b + l, so plan_reduce_wave's slot (j >> 6) + i is the one the 256-thread kernel writes.
+// Terminal value (val.w1 non-null, wave-uniform): `live` falls only at a terminal bit here, so after the loop it says "never
+// terminated"; the loop leaves early only once no lane is live, and otherwise every lane has stepped to x_H — the wave then
+// evaluates `val` in the same tile on the rows it holds, raw (no output clause), and the live lanes take ret + g_H * (double)v by a
+// select.
+template <class Env>
+__global__ void __launch_bounds__(kWave)
+    pend_policy_plan_deep_kernel(const typename Env::real* state, const double* start_rows, int64_t n_envs, int32_t n_cand,
+                                 int32_t horizon, double discount, int freq_rate, typename Env::Params p, const SinCosEntry* trig,
+                                 const PolicyDeepArgs pol, const PolicyNoiseArgs nz, const PolicyDeepArgs val, uint64_t env_offset,
+                                 double* ret_out, float* first_out, PlanPartial* partials) {
+    using R = typename Env::real;
+    using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
+    extern __shared__ __attribute__((aligned(16))) float4 deep_h1_s[];
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table<kWave>(trig_s, trig, Env::trig_rot_c(), Env::trig_rot_s());
+    const int64_t nk = n_envs * n_cand;
+    const int64_t j = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    if (j >= nk) return;
+    const int64_t i = j / n_cand;
+    const uint32_t k = (uint32_t)(j - i * n_cand);
+    R s[4];
+    // start state: the handle's SoA, or the caller's float64 rows narrowed as emei_set_state narrows them (util_kernels.hip)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[q] = start_rows ? (R)start_rows[i * 4 + q] : state[q * n_envs + i];
+    typename Env::Carry c;
+    trig_ctx_init(c.trig, trig_s);
+    Env::prime(s, c, p);
+    float x[4];
+    {
+        R o[4];
+        Env::obs_of(s, o);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) x[q] = (float)o[q];
+    }
+    double ret = 0.0, g = 1.0;
+    int32_t len = horizon;
+    bool live = true;
+    for (int t = 0; t < horizon; ++t) {
+        float av[1];
+        policy_eval_deep_t<4, 1, Env::kDiscrete>(pol, nz, nz.seed + (uint64_t)t, env_offset + (uint64_t)i, x, av, deep_h1_s,
+                                                 (int)threadIdx.x, k, k != 0u);
+        if (t == 0) first_out[j] = av[0];
+        R o[4], rew;
+        bool term;
+        Env::step(s, c, Env::decode_t((DrawT)av[0]), p, freq_rate, o, rew, term);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) x[q] = (float)o[q];
+        if (live) {
+            ret = ret + g * (double)(float)rew;
+            g = g * discount;
+            if (term) live = false, len = t + 1;
+        }
+        if (__ballot(live) == 0ull) break;  // wave-uniform
+    }
+    if (val.w1 && __ballot(live) != 0ull) {  // wave-uniform: some lane never terminated, so every lane holds its x_H
+        float v[1];
+        policy_eval_deep_t<4, 1, false, true>(val, nz, 0, 0, x, v, deep_h1_s, (int)threadIdx.x);  // val.noisy == 0: nz is never read
+        const double tail = g * (double)v[0];  // rounded to float64, then added
+        const double boot = ret + tail;
+        ret = live ? boot : ret;
+    }
+    ret_out[j] = ret;  // j < nk here
+    plan_reduce_wave(j, nk, i, n_cand, ret, len, partials);
+}
+
 // ---------------------------------------------------------------------------------------------
 // emei_mpc_mppi: receding-horizon MPPI control episodes in ONE launch (the normative text: include/emei_hip.h).
 // The draws read the nominal from the wave's LDS slice: CandidateSpecLds (emei_device.h, shared with the body kernels' controllers).
@@ -1839,6 +1907,17 @@ static int launch_env(const PendLaunch& L) {
             hipLaunchKernelGGL(pend_policy_plan_kernel<Env>, pgrid, dim3(kBlock), 0, L.stream, (const R*)L.state, P.start_rows, L.n,
                                P.n_candidates, L.n_steps, P.discount, L.freq_rate, a.p, a.trig, L.policy, L.policy_noise, L.env_offset,
                                P.return_out, P.first_actions, (PlanPartial*)P.partials);
+            break;
+        }
+        case PEND_OP_POLICY_PLAN_DEEP: {  // emei_plan_policy_deep: PEND_OP_POLICY_PLAN's lanes as one-wave blocks, the tile as dynamic LDS
+            const PlanLaunch& P = L.plan;
+            if (!P.partials || !P.return_out || !P.first_actions) return EMEI_ERR_INVALID;
+            if (int rc = policy_deep_lds_opt_in<pend_policy_plan_deep_kernel<Env>>()) return rc;
+            const dim3 pgrid((unsigned)((L.n * P.n_candidates + kWave - 1) / kWave));
+            const int h1 = L.policy_value.w1 && L.policy_value.hidden1 > L.policy_deep.hidden1 ? L.policy_value.hidden1 : L.policy_deep.hidden1;
+            hipLaunchKernelGGL(pend_policy_plan_deep_kernel<Env>, pgrid, dim3(kWave), policy_deep_tile_bytes(h1), L.stream, (const R*)L.state,
+                               P.start_rows, L.n, P.n_candidates, L.n_steps, P.discount, L.freq_rate, a.p, a.trig, L.policy_deep,
+                               L.policy_noise, L.policy_value, L.env_offset, P.return_out, P.first_actions, (PlanPartial*)P.partials);
             break;
         }
         case PEND_OP_POLICY_DEEP: {  // one-wave blocks, the wave's h1 tile as dynamic LDS

@@ -558,8 +558,35 @@ class Engine:
         ns = noise.bind(self).struct(policy.hidden if policy.hidden else policy.obs_dim)
         return H, K, policy.struct(), ns, discount, temperature
 
+    def _plan_policy_deep_args(self, H, K, policy, noise, value, discount, temperature):
+        """validated (H, K, policy struct, noise struct, value struct or None, discount, temperature or None) of plan_policy with a
+        policy.DeepMLPPolicy (emei_plan_policy_deep); policy, noise and value are bound to this engine.  Needs no handle."""
+        from .policy import DeepMLPPolicy, DeepValueFunction, PolicyNoise
+
+        H, K = int(H), int(K)
+        if H < 1 or K < 1:
+            raise ValueError(f"horizon={H} and n_candidates={K} must be >= 1")
+        if not isinstance(policy, DeepMLPPolicy):
+            raise TypeError("the two-hidden-layer plan_policy takes an emei_amd.DeepMLPPolicy")
+        if not isinstance(noise, PolicyNoise):
+            raise TypeError("plan_policy takes an emei_amd.PolicyNoise (the exploration noise that makes the candidates differ)")
+        if value is not None and not isinstance(value, DeepValueFunction):
+            raise TypeError("plan_policy takes an emei_amd.DeepValueFunction as value= (the terminal value network), or None")
+        discount = float(discount)
+        if not 0.0 < discount <= 1.0:
+            raise ValueError(f"discount={discount} is outside (0, 1]")
+        if temperature is not None:
+            temperature = float(temperature)
+            if not (0.0 < temperature < float("inf")):
+                raise ValueError(f"temperature={temperature} must be finite and > 0 (None: no weighted mean, no ess)")
+        policy.bind(self)
+        ns = noise.bind(self).struct(policy.hidden2)  # a log-std head reads h2
+        vs = value.bind(self).struct() if value is not None else None
+        return H, K, policy.struct(), ns, vs, discount, temperature
+
     @_on_device
-    def plan_policy(self, H, K, policy, noise, discount=1.0, temperature=None, start_state=None, returns=False, length=False, ess=False):
+    def plan_policy(self, H, K, policy, noise, discount=1.0, temperature=None, start_state=None, returns=False, length=False, ess=False,
+                    value=None):
         """Shooting and MPPI around a feedback policy in two launches (emei_plan_policy): per env, K closed-loop rollouts of `policy`
         (a policy.MLPPolicy) for H steps from the current state (or `start_state` [N, state_dim] float64), candidate k under the
         exploration noise of `noise` (a policy.PolicyNoise) drawn in the lanes with k in the counter word — candidate 0 takes no noise:
@@ -569,8 +596,22 @@ class Engine:
         [, mean_action float32 [N(, act_dim)]: the mean of the K first actions weighted by exp((return - best) / temperature), as
         plan_mppi weighs (on a discrete env the weighted share of action 1) — with a temperature]
         [, returns float64 [N, K]][, best_length int32 [N]][, ess float64 [N]: (sum w)^2 / sum w^2, needs a temperature]).
-        The handle is left as it is.  A policy.DeepMLPPolicy is refused: the two-hidden-layer network is not served by this call yet."""
-        H, K, ps, ns, discount, temperature = self._plan_policy_args(H, K, policy, noise, discount, temperature)
+        The handle is left as it is.
+        A policy.DeepMLPPolicy (two hidden layers, e.g. a 256-256 actor) goes to emei_plan_policy_deep: the same call, candidates,
+        noise streams and outputs on kernels of their own.  With it, value= (a policy.DeepValueFunction) adds a TERMINAL VALUE: every
+        candidate that never terminated in its H steps gets discount^H * float64(V(final obs)) on top of its return (a candidate that
+        terminated gets nothing), and the arg-max, the weights, the mean, `returns` and the ess all use the bootstrapped returns —
+        the planner of MBOP, LOOP, POLO and TD-MPC.  value= with a one-layer MLPPolicy is refused."""
+        from .policy import DeepMLPPolicy
+
+        deep = isinstance(policy, DeepMLPPolicy)
+        if value is not None and not deep:
+            raise ValueError("plan_policy: value= (the terminal value) comes with the two-hidden-layer call: pass a DeepMLPPolicy (a "
+                             "one-layer policy embeds in one exactly: include/emei_hip.h, emei_rollout_policy_deep)")
+        if deep:
+            H, K, ps, ns, vs, discount, temperature = self._plan_policy_deep_args(H, K, policy, noise, value, discount, temperature)
+        else:
+            H, K, ps, ns, discount, temperature = self._plan_policy_args(H, K, policy, noise, discount, temperature)
         if ess and temperature is None:
             raise ValueError("ess=True needs a temperature")
         st = self._start_rows(start_state)
@@ -583,9 +624,12 @@ class Engine:
         ln = new(self.n_envs, torch.int32) if length else None
         rets = new((self.n_envs, K), torch.float64) if returns else None
         es = new(self.n_envs, torch.float64) if ess else None
-        L.check(L.lib().emei_plan_policy(self._h, H, K, C.byref(ps), C.byref(ns), discount, 1.0 if temperature is None else temperature,
-                                         _ptr(st), _ptr(ws), _ptr(act), _ACT_DTYPES[dtype], _ptr(mean), _ptr(ret), _ptr(idx), _ptr(ln),
-                                         _ptr(rets), _ptr(es), _stream()))
+        tail = (discount, 1.0 if temperature is None else temperature, _ptr(st), _ptr(ws), _ptr(act), _ACT_DTYPES[dtype], _ptr(mean),
+                _ptr(ret), _ptr(idx), _ptr(ln), _ptr(rets), _ptr(es), _stream())
+        if deep:
+            L.check(L.lib().emei_plan_policy_deep(self._h, H, K, C.byref(ps), C.byref(ns), C.byref(vs) if vs is not None else None, *tail))
+        else:
+            L.check(L.lib().emei_plan_policy(self._h, H, K, C.byref(ps), C.byref(ns), *tail))
         return (act, ret, idx) + ((mean,) if mean is not None else ()) + ((rets,) if returns else ()) + ((ln,) if length else ()) \
             + ((es,) if ess else ())
 

@@ -365,7 +365,7 @@ class HipEnv(EmeiEnv):
         return tuple(t.cpu().numpy() for t in res) if as_numpy else res
 
     def plan_policy(self, horizon, n_candidates, policy, noise, discount=1.0, temperature=None, start_state=None, returns=False,
-                    length=False, ess=False):
+                    length=False, ess=False, value=None):
         """Planning around a feedback policy in two launches (Engine.plan_policy, ABI emei_plan_policy), the planner of model-based
         offline RL (MBOP, LOOP, POLO): per env, `n_candidates` closed-loop rollouts of `policy` (an emei_amd.MLPPolicy) for `horizon`
         steps under the exploration noise of `noise` (an emei_amd.PolicyNoise; candidate 0 takes none: it is the policy itself),
@@ -373,13 +373,15 @@ class HipEnv(EmeiEnv):
         (best_action [num_envs(, act_dim)], best_return float64 [num_envs], best_index int32 [num_envs][, mean_action float32
         [num_envs(, act_dim)] with a `temperature`: the first actions weighted as plan_mppi weighs][, returns float64 [num_envs,
         n_candidates]][, best_length int32 [num_envs]][, ess float64 [num_envs]]).  best_action is what step() takes.  A NumPy
-        `start_state` gives NumPy arrays; otherwise tensors.  The env's state is left as it is."""
+        `start_state` gives NumPy arrays; otherwise tensors.  The env's state is left as it is.
+        An emei_amd.DeepMLPPolicy (two hidden layers) is served by emei_plan_policy_deep; with it, `value` (an
+        emei_amd.DeepValueFunction) adds discount^horizon * V(final obs) to every candidate that never terminated."""
         import torch
 
         assert self.state is not None, "Call reset before using step method."  # base_control.py:67
         st = self._as_device(start_state, torch.float64)
         res = self.engine.plan_policy(horizon, n_candidates, policy, noise, discount=discount, temperature=temperature, start_state=st,
-                                      returns=returns, length=length, ess=ess)
+                                      returns=returns, length=length, ess=ess, value=value)
         return tuple(t.cpu().numpy() for t in res) if isinstance(start_state, np.ndarray) else res
 
     def mpc_mppi(self, n_steps, horizon, n_candidates, seed, temperature, nominal, discount=1.0, sigma=None, refill=None, clamp=None,

@@ -6,6 +6,8 @@ Engine.rollout_policy hands their pointers to the kernel (with noise=PolicyNoise
 inside the kernel); calling the object, `policy(obs)`, evaluates the same normative
 arithmetic (float64 sums in ascending index order) with torch operations, so the one object also serves the per-step path
 (`datasets.collect(env, n, policy=lambda o: policy(o))`) and gives the same actions there.
+DeepValueFunction holds a two-hidden-layer network with one output, the terminal value of Engine.plan_policy(..., value=)
+(emei_plan_policy_deep).
 """
 import ctypes as C
 
@@ -213,6 +215,65 @@ class DeepMLPPolicy(MLPPolicy):
         for i in range(h.shape[1]):
             y = y + w3[None, :, i] * h[:, i:i + 1]
         return self._output(x, h, y, noise, t, candidate)
+
+
+class DeepValueFunction:
+    """V(obs) with TWO ReLU hidden layers and one output: the terminal value of Engine.plan_policy(..., value=)
+    (emei_plan_policy_deep, include/emei_hip.h) — h1 = relu(w1 @ obs + b1), h2 = relu(w2 @ h1 + b2), v = float32(w3 @ h2 + b3), with
+    no output clause.  w3 [1, hidden2], b3 [1], w2 [hidden2, hidden1], b2 [hidden2], w1 [hidden1, obs_dim], b1 [hidden1]; the widths
+    are its own, each in 1 .. 256.  Kept as contiguous float32 tensors; calling it evaluates the normative arithmetic in torch
+    float64."""
+
+    _WEIGHTS = DeepMLPPolicy._WEIGHTS
+
+    def __init__(self, w3, b3, w2, b2, w1, b1):
+        f = lambda t: torch.as_tensor(t).detach().to(torch.float32).contiguous()
+        self.w1, self.b1, self.w2, self.b2, self.w3, self.b3 = f(w1), f(b1), f(w2), f(b2), f(w3), f(b3)
+        for w, b, name in ((self.w1, self.b1, "1"), (self.w2, self.b2, "2"), (self.w3, self.b3, "3")):
+            if w.dim() != 2 or b.dim() != 1 or b.shape[0] != w.shape[0]:
+                raise ValueError(f"w{name} {tuple(w.shape)} must be [n, n_in] and b{name} {tuple(b.shape)} [n]")
+        if self.w2.shape[1] != self.w1.shape[0]:
+            raise ValueError(f"w2 {tuple(self.w2.shape)} must be [hidden2, hidden1] with hidden1 = {int(self.w1.shape[0])} (w1's rows)")
+        if self.w3.shape[1] != self.w2.shape[0]:
+            raise ValueError(f"w3 {tuple(self.w3.shape)} must be [1, hidden2] with hidden2 = {int(self.w2.shape[0])} (w2's rows)")
+        if self.w3.shape[0] != 1:
+            raise ValueError(f"w3 {tuple(self.w3.shape)} must be [1, hidden2]: a value function has one output")
+        self.hidden1, self.hidden2 = int(self.w1.shape[0]), int(self.w2.shape[0])
+        for name, v in (("hidden1", self.hidden1), ("hidden2", self.hidden2)):
+            if not 1 <= v <= L.POLICY_DEEP_MAX_HIDDEN:
+                raise ValueError(f"{name}={v} is outside [1, {L.POLICY_DEEP_MAX_HIDDEN}]")
+        self.obs_dim = int(self.w1.shape[1])
+
+    to = DeepMLPPolicy.to
+
+    def bind(self, engine):
+        """check obs_dim against `engine`'s env and move the weights to its device"""
+        if self.obs_dim != engine.obs_dim:
+            raise ValueError(f"value function reads {self.obs_dim} inputs but {engine.env_name} has obs_dim={engine.obs_dim}")
+        return self.to(engine.device)
+
+    def struct(self):
+        """struct emei_policy_deep over the weights (which the caller keeps alive for the launch); out_mode is ignored for a value"""
+        p = lambda t: C.c_void_p(t.data_ptr())
+        return L.EmeiPolicyDeep(C.sizeof(L.EmeiPolicyDeep), self.hidden1, self.hidden2, L.POLICY_OUT_CLIP, p(self.w1), p(self.b1),
+                                p(self.w2), p(self.b2), p(self.w3), p(self.b3), 0)
+
+    def __call__(self, obs):
+        """obs [N, obs_dim] -> v float32 [N]: the value clause of emei_plan_policy_deep in torch float64, one elementwise operation
+        per term, every sum in ascending index order; v = float32(y_0) with no output clause (a NaN stays a NaN)."""
+        h = torch.as_tensor(obs, device=self.w3.device).to(torch.float32).to(torch.float64)
+        for w, b in ((self.w1, self.b1), (self.w2, self.b2)):
+            z = b.to(torch.float64)[None, :].repeat(h.shape[0], 1)
+            w = w.to(torch.float64)
+            for k in range(h.shape[1]):
+                z = z + w[None, :, k] * h[:, k:k + 1]
+            h = z.to(torch.float32)
+            h = torch.where(h > 0, h, torch.zeros_like(h)).to(torch.float64)
+        y = self.b3.to(torch.float64)[None, :].repeat(h.shape[0], 1)
+        w3 = self.w3.to(torch.float64)
+        for i in range(h.shape[1]):
+            y = y + w3[None, :, i] * h[:, i:i + 1]
+        return y[:, 0].to(torch.float32).contiguous()
 
 
 class PolicyNoise:

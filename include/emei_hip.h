@@ -61,7 +61,10 @@ extern "C" {
  *    EMEI_KERNEL_PEND_POLICY_DEEP / EMEI_KERNEL_BODY_POLICY_DEEP / EMEI_KERNEL_BODY_POLICY_DEEP_RK4;
  *    emei_plan_policy_workspace_bytes, emei_plan_policy (shooting and MPPI around a feedback policy: n_candidates closed-loop rollouts
  *    of one struct emei_policy per env under struct emei_policy_noise, the policy evaluated in the lanes that score them; the handle
- *    is untouched, no kernel id). */
+ *    is untouched, no kernel id);
+ *    emei_plan_policy_deep (emei_plan_policy around a struct emei_policy_deep network, with an optional terminal value — a second
+ *    struct emei_policy_deep with one output, added to the return of every candidate that never terminated; the workspace is
+ *    emei_plan_policy_workspace_bytes'; the handle is untouched, no kernel id). */
 #define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
@@ -860,6 +863,54 @@ EMEI_API int emei_rollout_policy_deep(emei_env* h, int32_t n_steps, const emei_p
 EMEI_API int emei_evaluate_policies_deep(emei_env* h, int32_t horizon, int32_t n_policies, const emei_policy_deep* stacked,
                                          double discount, const double* start_state, double* return_out, int32_t* length_out,
                                          float* final_obs_out, void* stream);
+
+/* emei_plan_policy for a network with TWO ReLU hidden layers, with an optional TERMINAL VALUE: the whole planner of MBOP, LOOP, POLO
+ * and TD-MPC — n_candidates closed-loop rollouts of a trained 256-256 actor per env under exploration noise, each scored on the true
+ * dynamics for `horizon` steps plus a learned value of the observation it ends in, then the best or the return-weighted first
+ * action.  `policy` and `noise` are emei_rollout_policy_deep's structs, `value` is a second struct emei_policy_deep or NULL; all with
+ * DEVICE pointers, read during the launches and not retained; they must not overlap any output or the workspace.
+ *
+ * Semantics (normative).  emei_plan_policy's text clause for clause — 1. Start and observe, 3. Step and score, 4. Select, 5. Weights,
+ * the outputs, the consequences — with two changes:
+ *   2. Policy.  The network is emei_rollout_policy_deep's: h1, h2 and y_q with float64 ascending sums, h1 and h2 rounded to float32
+ *      before the ReLU, NaN gives 0; what follows y_q is its noise clause — the term (double)s_q * (double)z_q added last, the
+ *      EMEI_POLICY_NOISE_GAUSS_HEAD head ws [n_out, hidden2] on h2, epsilon-greedy on the discrete envs — and its output clauses.
+ *      Step t of candidate k draws from the word stream of emei_plan_policy,
+ *          W[m] = philox4x32_10(key = seed + t (mod 2^64), counter = (g lo, g hi, k, m >> 2)).v[m & 3].
+ *      Candidate 0 takes NO noise, selected after the draw: a y_q of -0.0 keeps its sign, a non-finite std does not reach it, and on a
+ *      discrete env it never explores.
+ *   3b. Terminal value, with `value` non-NULL.  `value` names a network of emei_rollout_policy_deep's arithmetic with n_out = 1 —
+ *      w1 [hidden1, obs_dim], b1 [hidden1], w2 [hidden2, hidden1], b2 [hidden2], w3 [1, hidden2], b3 [1] — whose widths are its own
+ *      (each in [1, EMEI_POLICY_DEEP_MAX_HIDDEN]); its out_mode is ignored.  A candidate that set no terminal bit in any of its
+ *      `horizon` steps gets one more term,
+ *          ret = ret + g_H * (double)v,
+ *      where g_H is the running product discount^t after `horizon` multiplications (the float64 variable clause 3 carries) and
+ *      v = (float)y_0 of the value network on x_H, the float32 observation row that step horizon - 1 emits.  There is no output
+ *      clause: a NaN y_0 stays NaN, the return becomes NaN and the planner's order puts it last.  The product is rounded to float64
+ *      and then added (no fused multiply-add).  A candidate that terminated gets nothing, at whichever step, the last one included.
+ *      L(i, k) is unchanged by the value.  return_out, (k*, r*), the weights, the mean and the ESS all use the bootstrapped returns.
+ *      `value` NULL: no bootstrap, and every consequence of emei_plan_policy holds with the deep network — candidate 0 equals
+ *      emei_evaluate_policies_deep with n_policies = 1; the returns equal emei_evaluate_sequences on the actions of the per-step loop.
+ * A one-layer struct emei_policy is served exactly through the embedding emei_rollout_policy_deep documents (first layer (e_k, -e_k)
+ * rows with zero biases, second layer (w1[i,k], -w1[i,k])).
+ * Kernels: pend_policy_plan_deep_kernel / body_policy_plan_deep_kernel — the loop of the family's one-layer plan kernel, one lane per
+ * candidate j = i * n_candidates + k, launched as ONE-WAVE blocks whose dynamic LDS is the wave's h1 tile, sized by the wider first
+ * layer of `policy` and `value` (64 KiB at the cap); the value is evaluated in the same tile after the loop, skipped by a wave all of
+ * whose candidates terminated — then plan_policy_finish_kernel, unchanged.  EMEI_POLICY_OUT_TANH and EMEI_POLICY_NOISE_GAUSS_HEAD are
+ * not pinned bit for bit, as in the rollouts.
+ * workspace: emei_plan_policy_workspace_bytes(n_envs, n_candidates) bytes, as emei_plan_policy's.
+ * EMEI_ERR_INVALID before any HIP call, each message naming the argument, in this order: horizon < 1; n_candidates < 1; discount
+ * outside (0, 1]; with a non-NULL mean_action_out or ess_out, temperature not finite or <= 0; NULL policy, then policy.struct_size,
+ * policy.hidden1, then policy.hidden2, outside [1, EMEI_POLICY_DEEP_MAX_HIDDEN], policy.out_mode, policy.reserved; NULL noise, then
+ * emei_rollout_policy_noisy's noise checks in their order; with a non-NULL value, value.struct_size, value.hidden1, value.hidden2,
+ * value.reserved; a NULL handle; NULL policy w1, b1, w2, b2, w3 or b3, in this order, then the value's likewise; n_envs * n_candidates
+ * > 2^31 - 1; a wrong action_dtype; NULL workspace, then NULL best_action_out; a GAUSS mode on a discrete env or EPS_GREEDY on a
+ * continuous one.  EMEI_ERR_STATE without a state and without start_state. */
+EMEI_API int emei_plan_policy_deep(emei_env* h, int32_t horizon, int32_t n_candidates, const emei_policy_deep* policy,
+                                   const emei_policy_noise* noise, const emei_policy_deep* value, double discount, double temperature,
+                                   const double* start_state, void* workspace, void* best_action_out, int action_dtype,
+                                   float* mean_action_out, double* best_return_out, int32_t* best_index_out, int32_t* best_length_out,
+                                   double* return_out, double* ess_out, void* stream);
 
 /* Which kernel the LAST emei_step / emei_rollout of this handle launched (enum emei_kernel_id): a debug /
  * test getter, so that a parity test can assert that the path it checked is the path bench.py times. */
