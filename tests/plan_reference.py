@@ -110,16 +110,17 @@ def _terminal(env_name, kw, rows):
     return np.zeros(len(rows), bool)  # half_cheetah.py: never terminal
 
 
-def undecidable(env_name, obs, L, kw=None):
+def undecidable(env_name, obs, L, kw=None, tol=TOL_OBS, floor=1e-3):
     """Candidates [M] for which the oracle's own terminal function changes its answer at some counted step t < L when the
     observation moves by the project's per-step observation tolerance, 1e-5 * max(|v|, 1e-3) per component (rel_err's floor):
     all components outward, all inward, and each component alone outward and inward (the double pendulum's tip height depends on
-    th1 + th2, which the joint move can leave unchanged).  The only candidates a test may leave out."""
+    th1 + th2, which the joint move can leave unchanged).  The only candidates a test may leave out.  tol, floor: another observation
+    tolerance than the project's 1e-5 with its 1e-3 floor (a float32 mode's: tests/test_gpu_kernel_matrix.py)."""
     kw = kw or {}
     obs = np.asarray(obs, np.float64)
     H, M, D = obs.shape
     rows = obs.reshape(H * M, D)
-    step = 1e-5 * np.maximum(np.abs(rows), 1e-3) * np.where(rows >= 0, 1.0, -1.0)
+    step = tol * np.maximum(np.abs(rows), floor) * np.where(rows >= 0, 1.0, -1.0)
     base = _terminal(env_name, kw, rows)
     flip = np.zeros(H * M, bool)
     masks = [np.ones(D)] + [np.eye(D)[d] for d in range(D)]

@@ -158,6 +158,20 @@ def test_compact_done_sorted_indices():
     assert eng.compact_done().numel() == 0  # nobody is done one step after reset
 
 
+def test_compact_done_beyond_one_pass_of_the_compaction_kernel():
+    """above 65 536 envs the compaction kernel's loop runs a second pass: the indices (not only their count) against
+    torch.nonzero, with a ragged last wave"""
+    N = 65536 + 64 + 3
+    eng = _engine("CartPoleBalancing", N, max_episode_steps=0, seed=3)
+    eng.reset(3)
+    acts = torch.randint(0, 2, (40, N), device=eng.device, dtype=torch.uint8)
+    _, _, done = eng.rollout(acts)
+    idx = eng.compact_done()
+    want = torch.nonzero(done[-1]).flatten().to(torch.int32)
+    assert torch.equal(idx, want)
+    assert int((want >= 65536).sum()) > 0 and int((want < 65536).sum()) > 0  # done envs in both passes
+
+
 def test_freeze_unfreeze_restores_state():
     eng = _engine("CartPoleSwingUp", 256, seed=1)
     eng.reset(1)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+from start_states import cheetah_states as _states
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -14,16 +15,6 @@ def _engine(*a, **k):
     from emei_amd.engine import Engine
 
     return Engine(*a, **k)
-
-
-def _states(rng, n):
-    """flight, standing, crouched into the floor (many contacts), joints pushed past their limits"""
-    q = rng.normal(0, 0.15, (n, 9))
-    q[:, 1] = rng.uniform(-0.35, 0.3, n)
-    q[:, 2] = rng.normal(0, 0.4, n)
-    q[: n // 4, 3:] = rng.uniform(-1.3, 1.3, (n // 4, 6))
-    v = rng.normal(0, 1.5, (n, 9))
-    return np.concatenate([q, v], axis=1)
 
 
 @pytest.mark.parametrize("fr,dt", [(1, 0.002), (4, 0.002), (2, 0.01)])

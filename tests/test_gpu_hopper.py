@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+from start_states import hopper_states as _states
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -16,19 +17,6 @@ def _engine(*a, **k):
     from emei_amd.engine import Engine
 
     return Engine(*a, **k)
-
-
-def _states(rng, n):
-    """flight, standing on the foot, pressed into the floor (several contacts), joints past their limits, lying"""
-    q = rng.normal(0, 0.1, (n, 6))
-    q[:, 1] = 1.25 + rng.uniform(-0.08, 0.3, n)
-    q[:, 3:5] = -np.abs(rng.normal(0, 0.3, (n, 2)))
-    k = n // 5
-    q[:k, 3:] = rng.uniform(-3.0, 0.5, (k, 3))           # limits
-    q[k : 2 * k, 1] = rng.uniform(0.0, 0.3, k)           # lying / deep contact
-    q[k : 2 * k, 2] = rng.uniform(-1.7, 1.7, k)
-    v = rng.normal(0, 1.5, (n, 6))
-    return np.concatenate([q, v], axis=1)
 
 
 @pytest.mark.parametrize("integrator", INTEGRATORS)

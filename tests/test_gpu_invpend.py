@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+from start_states import invpend_states as _states
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -22,16 +23,6 @@ def _engine(*a, **k):
     from emei_amd.engine import Engine
 
     return Engine(*a, **k)
-
-
-def _states(rng, n):
-    s = np.empty((n, 4))
-    s[:, 0] = rng.uniform(-2.3, 2.3, n)  # beyond the +-2 rail on purpose: limit force engaged
-    s[:, 1] = rng.uniform(-12, 12, n)
-    s[:, 2] = rng.normal(0, 2, n)
-    s[:, 3] = rng.normal(0, 5, n)
-    s[: n // 4] = rng.standard_normal((n // 4, 4)) * 5e-3
-    return s
 
 
 @pytest.mark.parametrize("variant", sorted(VARIANTS))

@@ -211,19 +211,24 @@ def _tree_sum(v):
     return lanes[:, 0]
 
 
+def _mean_and_ess(returns, best_return, exp, first):
+    """(mean float32 [N, n_out], ess float64 [N]) of the header from the call's own returns [N, K], its best returns [N], the device's
+    exp((r_k - r*) / temperature) [N, K] and the candidates' first actions [N, K, n_out] as float64"""
+    rs = best_return[:, None]
+    # tests/mppi_reference.py's case analysis, with the device's exp in its last branch
+    with np.errstate(all="ignore"):
+        w = np.where(np.isnan(rs), 1.0, np.where(np.isnan(returns), 0.0, np.where(returns == rs, 1.0, exp)))
+    Z, Z2 = _tree_sum(w), _tree_sum(w * w)
+    mean = np.stack([(_tree_sum(w * first[:, :, a]) / Z).astype(np.float32) for a in range(first.shape[2])], axis=1)
+    return mean, Z * Z / Z2
+
+
 @pytest.mark.parametrize("case,N,K,H,hidden", SHAPES, ids=IDS)
 def test_mean_and_ess_by_the_headers_weights_and_tree(case, N, K, H, hidden):
     r = _run(case, N, K, H, hidden)
-    ret = r["returns"]
-    rs = r["best_return"][:, None]
-    # tests/mppi_reference.py's case analysis, with the device's exp in its last branch
-    with np.errstate(all="ignore"):
-        w = np.where(np.isnan(rs), 1.0, np.where(np.isnan(ret), 0.0, np.where(ret == rs, 1.0, r["exp"])))
-    Z, Z2 = _tree_sum(w), _tree_sum(w * w)
     first = r["acts"][0].reshape(N, K, -1).astype(np.float32).astype(np.float64)
-    mean = np.stack([(_tree_sum(w * first[:, :, a]) / Z).astype(np.float32) for a in range(first.shape[2])], axis=1)
+    mean, ess = _mean_and_ess(r["returns"], r["best_return"], r["exp"], first)
     got = r["mean_action"].reshape(N, -1)
-    ess = Z * Z / Z2
     print(f"{case} N={N} K={K} H={H} T={r['T']:.4g}: max |mean - ref| = {np.abs(got.astype(np.float64) - mean).max():.3e}, "
           f"ess rel err {np.abs(r['ess'] - ess).max():.3e}, ess {ess.min():.3f} .. {ess.max():.3f}")
     assert r["mean_action"].dtype == np.float32 and r["ess"].dtype == np.float64
