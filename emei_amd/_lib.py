@@ -49,11 +49,13 @@ POLICY_NOISY_KERNEL_NAMES = {18: "pend_policy_rollout_noisy_kernel", 19: "body_p
 # ... and those of emei_rollout_policy_deep (one kernel per family, with or without noise), likewise
 POLICY_DEEP_KERNEL_NAMES = {21: "pend_policy_rollout_deep_kernel", 22: "body_policy_rollout_deep_kernel",
                             23: "body_policy_rollout_deep_kernel<rk4>"}
+# ... and those of emei_mpc_policy (enum emei_kernel_id_mpc_policy), likewise
+MPC_POLICY_KERNEL_NAMES = {24: "pend_mpc_policy_kernel", 25: "body_mpc_policy_kernel"}
 
 
 def kernel_name(kernel_id):
     """name of an enum emei_kernel_id value (emei_last_rollout_kernel)"""
-    for table in (KERNEL_NAMES, POLICY_KERNEL_NAMES, POLICY_NOISY_KERNEL_NAMES, POLICY_DEEP_KERNEL_NAMES):
+    for table in (KERNEL_NAMES, POLICY_KERNEL_NAMES, POLICY_NOISY_KERNEL_NAMES, POLICY_DEEP_KERNEL_NAMES, MPC_POLICY_KERNEL_NAMES):
         if kernel_id in table:
             return table[kernel_id]
     raise KeyError(kernel_id)
@@ -72,6 +74,8 @@ POLICY_NOISE_GAUSS, POLICY_NOISE_GAUSS_HEAD, POLICY_NOISE_EPS_GREEDY = 0, 1, 2  
 POLICY_MAX_HIDDEN = 1024  # EMEI_POLICY_MAX_HIDDEN
 KERNEL_PEND_POLICY_DEEP, KERNEL_BODY_POLICY_DEEP, KERNEL_BODY_POLICY_DEEP_RK4 = 21, 22, 23  # emei_rollout_policy_deep
 POLICY_DEEP_MAX_HIDDEN = 256  # EMEI_POLICY_DEEP_MAX_HIDDEN
+KERNEL_PEND_MPC_POLICY, KERNEL_BODY_MPC_POLICY = 24, 25  # enum emei_kernel_id_mpc_policy (emei_mpc_policy)
+MPC_POLICY_ACT_BEST, MPC_POLICY_ACT_MEAN = 0, 1  # enum emei_mpc_policy_act
 MPC_MAX_HORIZON = 256  # EMEI_MPC_MAX_HORIZON
 MAX_OBS_PEERS = 8  # EMEI_MAX_OBS_PEERS
 # enum emei_ode_method: `method` of ODE_approximation (base_control.py:133-173), classic control only
@@ -225,6 +229,9 @@ SYMBOLS = {
     "emei_evaluate_policies_deep": (C.c_int, [_vp, _i32, _i32, C.POINTER(EmeiPolicyDeep), _dbl, _vp, _vp, _vp, _vp, _vp]),
     "emei_plan_policy_deep": (C.c_int, [_vp, _i32, _i32, C.POINTER(EmeiPolicyDeep), C.POINTER(EmeiPolicyNoise), C.POINTER(EmeiPolicyDeep),
                                         _dbl, _dbl, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "emei_mpc_policy_workspace_bytes": (_i64, [_i64, _i32]),
+    "emei_mpc_policy": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(EmeiPolicy), C.POINTER(EmeiPolicyNoise), _u64, _i32, _dbl, _dbl, _vp, _vp,
+                                  C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "emei_compact_done": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emei_get_counters": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emei_episode_init_obs": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),

@@ -1331,6 +1331,87 @@ extern "C" EMEI_API int emei_plan_policy(emei_env* h, int32_t horizon, int32_t n
 }
 
 // ---------------------------------------------------------------------------------------------
+// emei_mpc_policy: n_steps control steps of "emei_plan_policy under the key seed + t * seed_stride, act, emei_step" in one kernel of one
+// wave per env (pendulum_kernels.h:pend_mpc_policy_kernel; the InvertedDoublePendulum: body_mpc_kernels.h:body_mpc_policy_kernel), then
+// emei_mpc_mppi's done-mask launch.  Workspace: every candidate's float64 return, [n_envs, n_candidates] — word 0 of env i's row is
+// where the kernel leaves the env's last done code — then one float32 first-action slot per candidate.
+extern "C" EMEI_API int64_t emei_mpc_policy_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
+    const int64_t nk = check_plan_shape("emei_mpc_policy_workspace_bytes", n_envs, n_candidates);
+    return nk < 0 ? nk : ((int64_t)(sizeof(double) + sizeof(float)) * nk + 7) / 8 * 8;
+}
+
+extern "C" EMEI_API int emei_mpc_policy(emei_env* h, int32_t n_steps, int32_t horizon, int32_t n_candidates, const emei_policy* policy,
+                                        const emei_policy_noise* noise, uint64_t seed_stride, int32_t act_mode, double discount,
+                                        double temperature, void* workspace, void* actions_out, int action_dtype, float* obs_out,
+                                        float* reward_out, uint8_t* done_out, double* plan_return_out, int32_t* plan_index_out,
+                                        double* ess_out, uint32_t flags, void* stream) {
+    const char* fn = "emei_mpc_policy";
+    if (n_steps < 1) return fail(EMEI_ERR_INVALID, "%s: n_steps=%d < 1", fn, n_steps);
+    if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
+    if (act_mode != EMEI_MPC_POLICY_ACT_BEST && act_mode != EMEI_MPC_POLICY_ACT_MEAN)
+        return fail(EMEI_ERR_INVALID, "%s: unknown act_mode=%d", fn, act_mode);
+    if (act_mode == EMEI_MPC_POLICY_ACT_MEAN || ess_out)
+        if (int rc = check_temperature(fn, temperature)) return rc;
+    if (int rc = check_policy_struct(fn, "policy", policy)) return rc;
+    if (int rc = check_policy_noise(fn, noise)) return rc;
+    if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = check_policy_weights(fn, "policy", policy)) return rc;
+    if (int rc = check_plan_lanes(fn, h, n_candidates)) return rc;
+    if (action_dtype < EMEI_ACT_U8 || action_dtype > EMEI_ACT_F32 || (h->act_dim > 0) != (action_dtype == EMEI_ACT_F32))
+        return fail(EMEI_ERR_INVALID, "%s: action_dtype=%d: actions_out is uint8 / int32 / int64 for the discrete envs, float32 for the "
+                                      "continuous ones", fn, action_dtype);
+    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "%s: unknown flags 0x%x", fn, flags);
+    if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
+    if (!actions_out) return fail(EMEI_ERR_INVALID, "%s: null actions_out", fn);
+    if ((h->act_dim > 0) == (noise->mode == EMEI_POLICY_NOISE_EPS_GREEDY))
+        return fail(EMEI_ERR_INVALID, "%s: noise.mode=%d: the Gaussian modes are for the continuous envs, EMEI_POLICY_NOISE_EPS_GREEDY for "
+                                      "the discrete ones", fn, noise->mode);
+    EMEI_ON_DEVICE(h, fn);
+    if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    if (int rc = check_mpc_handle(fn, h)) return rc;
+    PolicyArgs pa{};
+    pa.w1 = policy->w1, pa.b1 = policy->b1, pa.w2 = policy->w2, pa.b2 = policy->b2;
+    pa.hidden = policy->hidden, pa.out_mode = policy->out_mode, pa.action_dtype = action_dtype;
+    ctrl_range(h->cfg.env_id, pa.lo, pa.hi);
+    PolicyNoiseArgs na{};
+    na.seed = noise->seed, na.mode = noise->mode, na.sigma = (float)noise->sigma;
+    if (noise->mode == EMEI_POLICY_NOISE_GAUSS) na.std = noise->std;
+    if (noise->mode == EMEI_POLICY_NOISE_GAUSS_HEAD)
+        na.ws = noise->ws, na.bs = noise->bs, na.log_std_min = noise->log_std_min, na.log_std_max = noise->log_std_max;
+    const bool weighted = act_mode == EMEI_MPC_POLICY_ACT_MEAN || ess_out;
+    int rc;
+    if (steps_as_body(h->cfg)) {  // continuous actions: actions_out is float32
+        BodyLaunch L = body_base(h, stream);
+        L.op = BODY_OP_MPC_POLICY;
+        L.mpc.horizon = horizon, L.mpc.actions_out = (float*)actions_out;
+        L.mpc.plan_return_out = plan_return_out, L.mpc.plan_index_out = plan_index_out, L.mpc.ess_out = ess_out;
+        L.mpc.temperature = weighted ? temperature : 1.0, L.mpc.act_mode = act_mode, L.mpc.seed_stride = seed_stride;
+        L.n_steps = n_steps;
+        L.plan.n_candidates = n_candidates, L.plan.discount = discount, L.plan.return_out = (double*)workspace;
+        L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
+        L.flags = flags;
+        L.policy = pa, L.policy_noise = na;
+        L.selected = &h->last_kernel;
+        rc = body_launch(L);
+    } else {
+        PendLaunch L = pend_base(h, stream);
+        L.op = PEND_OP_MPC_POLICY;
+        L.n_steps = n_steps, L.horizon = horizon, L.temperature = weighted ? temperature : 1.0;
+        L.act_mode = act_mode, L.seed_stride = seed_stride;
+        L.plan.n_candidates = n_candidates, L.plan.discount = discount, L.plan.return_out = (double*)workspace;
+        L.mpc_actions_out = actions_out, L.action_dtype = action_dtype;
+        L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
+        L.plan_return_out = plan_return_out, L.plan_index_out = plan_index_out, L.ess_out = ess_out;
+        L.flags = flags;
+        L.policy = pa, L.policy_noise = na;
+        L.selected = &h->last_kernel;
+        rc = pend_launch(L);
+    }
+    if (rc == EMEI_OK) rc = launch_mpc_done_pack((const double*)workspace, n_candidates, h->cfg.n_envs, h->done_mask, (hipStream_t)stream);
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+}
+
+// ---------------------------------------------------------------------------------------------
 // emei_rollout_policy_deep / emei_evaluate_policies_deep: the policy calls above for struct emei_policy_deep (two hidden layers), on
 // kernels of their own (pend_policy_rollout_deep_kernel / body_policy_rollout_deep_kernel, pend_policy_eval_deep_kernel /
 // body_policy_eval_deep_kernel).  The refusals mirror check_policy_struct / check_policy_weights.

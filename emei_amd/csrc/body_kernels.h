@@ -174,7 +174,8 @@ enum BodyOp { BODY_OP_ROLLOUT = 0, BODY_OP_RESET, BODY_OP_GET_OBS, BODY_OP_INIT_
               BODY_OP_POLICY_DEEP /* emei_rollout_policy_deep: body_policy_rollout_deep_kernel */,
               BODY_OP_POLICY_EVAL_DEEP /* emei_evaluate_policies_deep: body_policy_eval_deep_kernel */,
               BODY_OP_POLICY_PLAN /* emei_plan_policy: body_policy_plan_kernel */,
-              BODY_OP_POLICY_PLAN_DEEP /* emei_plan_policy_deep: body_policy_plan_deep_kernel */ };
+              BODY_OP_POLICY_PLAN_DEEP /* emei_plan_policy_deep: body_policy_plan_deep_kernel */,
+              BODY_OP_MPC_POLICY /* emei_mpc_policy: body_mpc_policy_kernel (Body::kFusedMpc) */ };
 
 // What BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM take beyond the base descriptor: n_steps control steps of the planner with plan.n_candidates
 // candidates over `horizon` steps under plan.discount; plan.cand carries the call's seed, sigma and the ctrlrange (its nominal is
@@ -193,6 +194,12 @@ struct MpcLaunch {
     int32_t n_elites = 1, iterations = 1;
     float sigma_min = 0.f;
     double* elite_return_out = nullptr;  // [n_steps, n] or null
+    // BODY_OP_MPC_POLICY (emei_mpc_policy): horizon, actions_out, plan_return_out, ess_out and temperature as above, no nominal;
+    // `policy` and `policy_noise` as BODY_OP_POLICY_PLAN takes them, control step t under the key policy_noise.seed + t * seed_stride;
+    // plan.return_out = the workspace: [n * K] float64 returns, then [n * K] float32 first actions
+    int32_t act_mode = 0;  // enum emei_mpc_policy_act
+    uint64_t seed_stride = 0;
+    int32_t* plan_index_out = nullptr;  // [n_steps, n] or null
 };
 
 // host-side launch descriptor (abi.hip -> body_dispatch.hip -> body_tu.hip)
@@ -1631,7 +1638,7 @@ static void launch_body_plan(const BodyLaunch& L, const typename Body::Model& m,
 }
 
 }  // namespace emei
-#include "body_mpc_kernels.h"  // body_mpc_mppi_kernel / body_mpc_cem_kernel and launch_body_mpc
+#include "body_mpc_kernels.h"  // body_mpc_mppi_kernel / body_mpc_cem_kernel / body_mpc_policy_kernel and their launches
 namespace emei {
 
 // every launch of one Body type (one translation unit instantiates exactly one Body: body_tu.hip)
@@ -1916,6 +1923,13 @@ static int launch_body(const BodyLaunch& L) {
         case BODY_OP_MPC_CEM:
             if constexpr (Body::kFusedMpc) {
                 if (int rc = launch_body_mpc<Body>(L, m)) return rc;
+                break;
+            } else {
+                return EMEI_ERR_UNSUPPORTED;  // abi.hip refuses these handles with a message of its own
+            }
+        case BODY_OP_MPC_POLICY:
+            if constexpr (Body::kFusedMpc) {
+                if (int rc = launch_body_mpc_policy<Body>(L, m)) return rc;
                 break;
             } else {
                 return EMEI_ERR_UNSUPPORTED;  // abi.hip refuses these handles with a message of its own

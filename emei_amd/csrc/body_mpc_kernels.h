@@ -427,6 +427,230 @@ __global__ void __launch_bounds__(kBlock) body_mpc_cem_kernel(const BodyMpcArgs<
     body_mpc_write_back<Body>(s, steps, episode, done, nom, n_comp, i, lane, wt, a);
 }
 
+// ---------------------------------------------------------------------------------------------
+// emei_mpc_policy for the opted-in bodies: the skeleton above around emei_plan_policy.  No nominal: nothing in LDS beyond the trig table.
+template <class Body>
+struct BodyMpcPolicyArgs {
+    typename Body::real* state;  // SoA: NS arrays of n
+    int32_t* steps;
+    uint32_t* episode;
+    const SinCosEntry* trig;
+    unsigned long long* cap_hits;
+    double* work;  // [n, n_cand] returns, then [n, n_cand] float32 first actions; word 0 of env i's row of returns ends as its last
+                   // done code (mpc_done_pack_kernel)
+    float* actions_out;
+    float* obs_out;
+    float* reward_out;
+    uint8_t* done_out;
+    double* plan_return_out;
+    int32_t* plan_index_out;
+    double* ess_out;
+    int64_t n;
+    int32_t n_steps, horizon, n_cand, freq_rate, max_episode_steps, semi, act_mode;
+    uint32_t flags;
+    uint64_t reset_seed, env_offset, seed_stride;
+    double discount, temperature;
+    NoiseArgs<Body::NS> noise;
+    typename Body::Model m;
+};
+
+// Per control step t, under the key key_t = nz.seed + t * seed_stride:
+//   1., 2. every lane scores its candidates with body_policy_plan_kernel's loop, expression for expression — x_0 is the float32
+//      observation of the state (Body::obs_of, as emei_get_obs rounds it), formed in front of the loop and at the end of every
+//      control step, behind the reset; the
+//      action of step 0 from x_0 under key_t, the action of step h + 1 from the row step h emits under key_t + h + 1, the lane's k in the counter word, no
+//      noise for k = 0, the weights wave-uniform scalar loads; a fresh Warm, freq_rate substeps and Body::outputs per step;
+//      ret = ret + g * (double)(float)rew — keeps its return and its action of step 0 in `work` (a lane reads back only what it
+//      wrote) and folds (k*, r*, a*) in ascending k, then over the lanes;
+//   3. with ACT_MEAN or an ess_out (wave-uniform): plan_policy_finish_kernel<true>'s lines, copied rather than shared;
+//   4. the action — the winner's, or the mean — then body_mpc_act_step's step part: body_rollout_kernel's step without observation
+//      noise, TimeLimit, and body_init of (reset key, global env index, episode) under auto-reset; lane 0 stores the outputs.
+template <class Body, bool RK4>
+__global__ void __launch_bounds__(kBlock)
+    body_mpc_policy_kernel(const BodyMpcPolicyArgs<Body> a, const PolicyArgs pol, const PolicyNoiseArgs nz) {
+    static_assert(Body::kFusedMpc && Body::kScratchPerLane == 0, "a body without block scratch that opted in");
+    static_assert(Body::NA == 1, "one float32 first-action slot per candidate (abi.hip sizes the workspace)");
+    using R = typename Body::real;
+    constexpr int kWavesPerBlock = kBlock / kWave;
+    constexpr int NS = Body::NS, NO = Body::NO, NA = Body::NA;
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table(trig_s, a.trig);
+    TrigCtx trig;
+    trig.tab = trig_s;
+    trig.scratch_stride = kBlock;
+    trig.cap_hits = a.cap_hits;
+    const int lane = (int)(threadIdx.x & (kWave - 1));
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    const int64_t i = (int64_t)blockIdx.x * kWavesPerBlock + wv;  // wave-uniform
+    if (i >= a.n) return;
+    const int64_t n = a.n;
+    const int32_t n_cand = a.n_cand;
+
+    R s[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) s[k] = a.state[(int64_t)k * n + i];
+    int32_t steps = a.steps[i];
+    uint32_t episode = a.episode[i];
+    const bool weighted = a.act_mode == EMEI_MPC_POLICY_ACT_MEAN || a.ess_out != nullptr;  // wave-uniform
+    const uint64_t g = a.env_offset + (uint64_t)i;
+    double* wt = a.work + i * n_cand;
+    float* fa = (float*)(a.work + n * n_cand) + i * n_cand;  // the env's first actions
+    uint32_t done = 0;
+    // x_0 of the first control step; every later one observes at the end of the step in front of it, behind the reset
+    float x0[NO];
+    {
+        double od[NO];
+        Body::obs_of(s, od, a.m);
+#pragma unroll
+        for (int q = 0; q < NO; ++q) x0[q] = (float)od[q];
+    }
+
+    for (int32_t t = 0; t < a.n_steps; ++t) {
+        // 1., 2.
+        const uint64_t key_t = nz.seed + (uint64_t)t * a.seed_stride;
+        double rs = __builtin_nan("");  // (NaN, INT32_MAX) loses to every candidate
+        int32_t ks = INT32_MAX;
+        float as = 0.f;
+        for (int32_t k0 = 0; k0 < n_cand; k0 += kWave) {  // wave-uniform trip count: every lane takes part in the ballot
+            const int32_t k = k0 + lane;
+            R cs[NS];
+#pragma unroll
+            for (int q = 0; q < NS; ++q) cs[q] = s[q];
+            float act[NA];
+            policy_eval_t<NO, NA, false, true>(pol, nz, key_t, g, x0, act, (uint32_t)k, k != 0);
+            const float first = act[0];
+            double ret = 0.0, gd = 1.0;
+            bool live = k < n_cand;
+            for (int32_t h = 0; h < a.horizon; ++h) {
+                R ctrl[NA];
+#pragma unroll
+                for (int q = 0; q < NA; ++q) ctrl[q] = (R)act[q];
+                R pre[NS];
+#pragma unroll
+                for (int q = 0; q < NS; ++q) pre[q] = cs[q];
+                typename Body::Warm warm{};
+                for (int f = 0; f < a.freq_rate; ++f) body_substep<Body, RK4>(cs, ctrl, a.m, a.semi != 0, trig, warm);
+                float o[NO];
+                R rew;
+                bool term;
+                Body::outputs(cs, pre, ctrl, a.m, a.freq_rate, o, rew, term, trig);
+                if (live) {
+                    ret = ret + gd * (double)(float)rew;
+                    gd = gd * a.discount;
+                    if (term) live = false;
+                }
+                if (__ballot(live) == 0ull || h == a.horizon - 1) break;  // wave-uniform
+                policy_eval_t<NO, NA, false, true>(pol, nz, key_t + (uint64_t)h + 1u, g, o, act, (uint32_t)k, k != 0);  // the next step's action
+            }
+            if (k < n_cand) {
+                wt[k] = ret;
+                fa[k] = first;
+                if (plan_replaces(rs, ks, ret, k)) rs = ret, ks = k, as = first;
+            }
+        }
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const double r2 = __shfl_xor(rs, d, kWave);
+            const int32_t k2 = __shfl_xor(ks, d, kWave);
+            const float a2 = __shfl_xor(as, d, kWave);
+            if (plan_replaces(rs, ks, r2, k2)) rs = r2, ks = k2, as = a2;
+        }
+        // 3.
+        float mean = 0.f;
+        if (weighted) {
+            double z = 0.0, z2 = 0.0, acc = 0.0;
+            for (int32_t k = lane; k < n_cand; k += kWave) {
+                const double r = wt[k];
+                const double e = exp((r - rs) / a.temperature);  // r < r*: the argument is negative, -inf included
+                const double w = rs != rs ? 1.0 : (r != r ? 0.0 : (r == rs ? 1.0 : e));
+                z += w, z2 += w * w;
+                acc += w * (double)fa[k];
+            }
+            z = wave_sum_all(z), z2 = wave_sum_all(z2);  // Z >= 1: candidate k* has weight 1
+            const double sum = wave_sum_all(acc);
+            mean = (float)(sum / z);
+            if (lane == 0 && a.ess_out) a.ess_out[(int64_t)t * n + i] = z * z / z2;
+        }
+        const int64_t at = (int64_t)t * n + i;
+        if (lane == 0) {
+            if (a.plan_return_out) a.plan_return_out[at] = rs;
+            if (a.plan_index_out) a.plan_index_out[at] = ks;
+        }
+        // 4.
+        const float av = a.act_mode == EMEI_MPC_POLICY_ACT_MEAN ? mean : as;  // wave-uniform
+        R ctrl[NA] = {(R)av};
+        if (lane == 0) a.actions_out[at] = av;
+        R pre[NS];
+#pragma unroll
+        for (int q = 0; q < NS; ++q) pre[q] = s[q];
+        typename Body::Warm warm{};
+        for (int f = 0; f < a.freq_rate; ++f) body_substep<Body, RK4>(s, ctrl, a.m, a.semi != 0, trig, warm);
+        float o[NO];
+        R rew;
+        bool term;
+        Body::outputs(s, pre, ctrl, a.m, a.freq_rate, o, rew, term, trig);
+        ++steps;
+        const bool trunc = (a.max_episode_steps > 0) & (steps >= a.max_episode_steps);
+        done = (term ? EMEI_DONE_TERMINAL : 0u) | (trunc ? EMEI_DONE_TRUNCATED : 0u);
+        if (lane == 0) {
+            if (a.obs_out) {
+#pragma unroll
+                for (int q = 0; q < NO; ++q) a.obs_out[at * NO + q] = o[q];
+            }
+            if (a.reward_out) a.reward_out[at] = (float)rew;
+            if (a.done_out) a.done_out[at] = (uint8_t)done;
+        }
+        const bool reset_now = (a.flags & EMEI_FLAG_AUTO_RESET) != 0 && __builtin_amdgcn_readfirstlane(done) != 0u;  // wave-uniform
+        if (reset_now) {
+            ++episode;
+            steps = 0;
+            body_init<Body>(s, a.reset_seed, g, episode, a.noise);
+        }
+        {  // the next control step's x_0
+            double od[NO];
+            Body::obs_of(s, od, a.m);
+#pragma unroll
+            for (int q = 0; q < NO; ++q) x0[q] = (float)od[q];
+        }
+    }
+
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < NS; ++q) a.state[(int64_t)q * n + i] = s[q];
+        a.steps[i] = steps;
+        a.episode[i] = episode;
+        ((unsigned long long*)wt)[0] = (unsigned long long)done;  // lane 0's own slot, after its last use
+    }
+}
+
+// the one launch of emei_mpc_policy's body route (BODY_OP_MPC_POLICY), one wave per env
+template <class Body>
+static int launch_body_mpc_policy(const BodyLaunch& L, const typename Body::Model& m) {
+    const MpcLaunch& M = L.mpc;
+    if (M.horizon < 1 || L.plan.n_candidates < 1 || !L.plan.return_out || !M.actions_out) return EMEI_ERR_INVALID;
+    if (NoiseArgs<Body::NS>(L.noise).obs_on) return EMEI_ERR_UNSUPPORTED;  // the plan's model steps without observation noise
+    BodyMpcPolicyArgs<Body> a;
+    a.state = (typename Body::real*)L.state, a.steps = L.steps, a.episode = L.episode;
+    a.trig = (const SinCosEntry*)L.trig, a.cap_hits = L.cap_hits;
+    a.work = L.plan.return_out, a.actions_out = M.actions_out;
+    a.obs_out = L.obs_out, a.reward_out = L.reward_out, a.done_out = L.done_out;
+    a.plan_return_out = M.plan_return_out, a.plan_index_out = M.plan_index_out, a.ess_out = M.ess_out;
+    a.n = L.n, a.n_steps = L.n_steps, a.horizon = M.horizon, a.n_cand = L.plan.n_candidates;
+    a.freq_rate = L.freq_rate, a.max_episode_steps = L.max_episode_steps;
+    a.semi = L.integrator == EMEI_INTEG_SEMI_IMPLICIT, a.act_mode = M.act_mode, a.flags = L.flags;
+    a.reset_seed = L.seed, a.env_offset = L.env_offset, a.seed_stride = M.seed_stride;
+    a.discount = L.plan.discount, a.temperature = M.temperature;
+    a.noise = NoiseArgs<Body::NS>(L.noise), a.m = m;
+    constexpr int kWavesPerBlock = kBlock / kWave;
+    const dim3 mgrid((unsigned)((L.n + kWavesPerBlock - 1) / kWavesPerBlock));
+    if (L.integrator == EMEI_INTEG_RK4)
+        hipLaunchKernelGGL((body_mpc_policy_kernel<Body, true>), mgrid, dim3(kBlock), 0, L.stream, a, L.policy, L.policy_noise);
+    else
+        hipLaunchKernelGGL((body_mpc_policy_kernel<Body, false>), mgrid, dim3(kBlock), 0, L.stream, a, L.policy, L.policy_noise);
+    if (L.selected) *L.selected = EMEI_KERNEL_BODY_MPC_POLICY;
+    return EMEI_OK;
+}
+
 // the one launch of either controller (BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM), one wave per env
 template <class Body>
 static int launch_body_mpc(const BodyLaunch& L, const typename Body::Model& m) {

@@ -171,6 +171,14 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// The butterfly sum of the planners' finish kernels (util_kernels.hip) and of the fused policy controller (emei_mpc_policy).
+// all lanes of the wave end with the same bits: x + y is commutative, so both partners of a butterfly step compute the same sum
+__device__ __forceinline__ double wave_sum_all(double v) {
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) v += __shfl_xor(v, d, kWave);
+    return v;
+}
+
 // 16-byte output stores of the staged rollout kernels with the NON-TEMPORAL hint (global_store_dwordx4 ... nt).  The rollout's
 // outputs are written once and read by nobody on this GPU during the launch; without the hint the reward / done flushes in particular
 // (256 B and 64 B pieces of a row per wave) sit in the L2 as partly written lines.  Same-box A/B (tools/ab.sh, kernel ms per pass):

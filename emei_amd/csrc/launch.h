@@ -7,7 +7,7 @@
 
 namespace emei {
 
-enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC, PEND_OP_MPC_CEM, PEND_OP_POLICY, PEND_OP_POLICY_EVAL, PEND_OP_POLICY_NOISY, PEND_OP_POLICY_DEEP, PEND_OP_POLICY_EVAL_DEEP, PEND_OP_POLICY_PLAN, PEND_OP_POLICY_PLAN_DEEP };
+enum PendOp { PEND_OP_ROLLOUT = 0, PEND_OP_RESET, PEND_OP_GET_OBS, PEND_OP_REWARD_TERMINAL, PEND_OP_NEXT_OBS, PEND_OP_INIT_OBS, PEND_OP_PLAN, PEND_OP_MPC, PEND_OP_MPC_CEM, PEND_OP_POLICY, PEND_OP_POLICY_EVAL, PEND_OP_POLICY_NOISY, PEND_OP_POLICY_DEEP, PEND_OP_POLICY_EVAL_DEEP, PEND_OP_POLICY_PLAN, PEND_OP_POLICY_PLAN_DEEP, PEND_OP_MPC_POLICY };
 
 // emei_set_obs_peers: the gathered buffers the staged rollout kernel also writes every observation row to
 struct ObsPeers {
@@ -105,6 +105,13 @@ struct PendLaunch {
     // PEND_OP_POLICY_PLAN_DEEP (emei_plan_policy_deep): PEND_OP_POLICY_PLAN's fields with the two-hidden-layer network in `policy_deep`
     // (noisy set) and the terminal value network in `policy_value` (w1 null: no bootstrap; out_mode, lo, hi and noisy unused)
     PolicyDeepArgs policy_value = {};
+    // PEND_OP_MPC_POLICY (emei_mpc_policy): n_steps control steps of "plan around the policy, act, step" — PEND_OP_MPC's n_steps,
+    // horizon, mpc_actions_out, plan_return_out, ess_out, temperature, flags and `seed` (the handle's reset key) without a nominal;
+    // `policy` and `policy_noise` as PEND_OP_POLICY_PLAN takes them, control step t under the key policy_noise.seed + t * seed_stride;
+    // plan.n_candidates, plan.discount; plan.return_out = the workspace: [n * K] float64 returns, then [n * K] float32 first actions
+    int32_t act_mode = 0;                  // enum emei_mpc_policy_act
+    uint64_t seed_stride = 0;
+    int32_t* plan_index_out = nullptr;     // [n_steps, n] or null
 };
 
 // The deep policy kernels keep h1 in dynamic LDS (emei_device.h:policy_deep_tile_bytes, up to 64 KiB): the opt-in HIP wants of a

@@ -1359,6 +1359,187 @@ __global__ void __launch_bounds__(kBlock) pend_mpc_mppi_kernel(const MpcArgs<Env
 }
 
 // ---------------------------------------------------------------------------------------------
+// emei_mpc_policy: policy-guided control episodes in ONE launch (the normative text: include/emei_hip.h).  There is no nominal: the
+// policy is the warm start, so the kernel keeps nothing in LDS beyond the trig table and the horizon has no cap.
+
+template <class Env>
+struct MpcPolicyArgs {
+    typename Env::real* state;  // SoA: 4 arrays of n
+    int32_t* steps;
+    uint32_t* episode;
+    const SinCosEntry* trig;
+    double* work;  // [n, n_cand] returns, then [n, n_cand] float32 first actions; word 0 of env i's row of returns ends as its last
+                   // done code (mpc_done_pack_kernel)
+    void* actions_out;
+    float4* obs_out;
+    float* reward_out;
+    uint8_t* done_out;
+    double* plan_return_out;
+    int32_t* plan_index_out;
+    double* ess_out;
+    int64_t n;
+    int32_t n_steps, horizon, n_cand, freq_rate, action_dtype, max_episode_steps, act_mode;
+    uint32_t flags;
+    uint64_t reset_seed, env_offset, seed_stride;
+    double discount, temperature;
+    typename Env::Params p;
+};
+
+// pend_mpc_mppi_kernel's skeleton — one WAVE per env for all n_steps control steps, lane l owning the candidates k = l, l + 64, ..., the
+// real state and its counters wave-uniform values in registers — around emei_plan_policy.  Per control step t, under the key
+// key_t = nz.seed + t * seed_stride:
+//   1. the carry is primed from the state and x_0 is its float32 observation (pend_policy_plan_kernel's start);
+//   2. every lane scores its candidates with pend_policy_plan_kernel's loop, expression for expression: the policy on the row the
+//      lane holds under the key key_t + h with the lane's k in the counter word, no noise for k = 0, the weights wave-uniform scalar
+//      loads; ret = ret + g * (double)(float)rew in step order; the wave leaves a pass once a ballot finds no lane live (padding
+//      lanes k >= n_cand take part and are never live).  The lane keeps its return (8 B) and its action of step 0 (4 B) in `work`
+//      — a lane reads back only what it wrote — and folds (k*, r*, a*) in ascending k, then over the lanes: the planner's order is
+//      total, so this is plan_policy_finish_kernel's winner and its best_action;
+//   3. with ACT_MEAN or an ess_out (wave-uniform): Z, sum w^2, the weighted sum of the first actions and the quotient are
+//      plan_policy_finish_kernel<true>'s lines, copied rather than shared (that kernel's instruction stream stays what it is);
+//   4. the action — the winner's, or the mean (discrete envs: mean >= 0.5f) — then pend_mpc_mppi_kernel's step 4: emei_step's step
+//      on the real state, TimeLimit and auto-reset; lane 0 stores the step's outputs.
+// stage_trig_table's block barrier is taken by every wave, also by those past n; after it there is NO block barrier.
+template <class Env>
+__global__ void __launch_bounds__(kBlock) pend_mpc_policy_kernel(const MpcPolicyArgs<Env> a, const PolicyArgs pol, const PolicyNoiseArgs nz) {
+    using R = typename Env::real;
+    using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
+    static_assert(Env::kActDim == 1, "one float32 first-action slot per candidate (abi.hip sizes the workspace)");
+    constexpr int kWavesPerBlock = kBlock / kWave;
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table(trig_s, a.trig, Env::trig_rot_c(), Env::trig_rot_s());
+    const int lane = (int)(threadIdx.x & (kWave - 1));
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    const int64_t i = (int64_t)blockIdx.x * kWavesPerBlock + wv;  // wave-uniform
+    if (i >= a.n) return;
+    const int64_t n = a.n;
+    const int32_t n_cand = a.n_cand, horizon = a.horizon;
+
+    R s[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = a.state[k * n + i];
+    int32_t steps = a.steps[i];
+    uint32_t episode = a.episode[i];
+    typename Env::Carry c;
+    trig_ctx_init(c.trig, trig_s);
+    const bool auto_reset = (a.flags & EMEI_FLAG_AUTO_RESET) != 0;
+    const bool weighted = a.act_mode == EMEI_MPC_POLICY_ACT_MEAN || a.ess_out != nullptr;  // wave-uniform
+    const uint64_t g = a.env_offset + (uint64_t)i;
+    double* wt = a.work + i * n_cand;
+    float* fa = (float*)(a.work + n * n_cand) + i * n_cand;  // the env's first actions
+    uint32_t done = 0;
+
+    for (int32_t t = 0; t < a.n_steps; ++t) {
+        // 1.
+        const uint64_t key_t = nz.seed + (uint64_t)t * a.seed_stride;
+        Env::prime(s, c, a.p);
+        float x0[4];
+        {
+            R o[4];
+            Env::obs_of(s, o);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) x0[q] = (float)o[q];
+        }
+        // 2.
+        double rs = __builtin_nan("");  // (NaN, INT32_MAX) loses to every candidate
+        int32_t ks = INT32_MAX;
+        float as = 0.f;
+        for (int32_t k0 = 0; k0 < n_cand; k0 += kWave) {  // wave-uniform trip count: every lane takes part in the ballot
+            const int32_t k = k0 + lane;
+            R cs[4] = {s[0], s[1], s[2], s[3]};
+            typename Env::Carry cc = c;
+            float x[4] = {x0[0], x0[1], x0[2], x0[3]};
+            double ret = 0.0, gd = 1.0;
+            float first = 0.f;
+            bool live = k < n_cand;
+            for (int32_t h = 0; h < horizon; ++h) {
+                float av[1];
+                policy_eval_t<4, 1, Env::kDiscrete, true>(pol, nz, key_t + (uint64_t)h, g, x, av, (uint32_t)k, k != 0);
+                if (h == 0) first = av[0];
+                R o[4], rew;
+                bool term;
+                Env::step(cs, cc, Env::decode_t((DrawT)av[0]), a.p, a.freq_rate, o, rew, term);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) x[q] = (float)o[q];
+                if (live) {
+                    ret = ret + gd * (double)(float)rew;
+                    gd = gd * a.discount;
+                    if (term) live = false;
+                }
+                if (__ballot(live) == 0ull) break;  // wave-uniform
+            }
+            if (k < n_cand) {
+                wt[k] = ret;
+                fa[k] = first;
+                if (plan_replaces(rs, ks, ret, k)) rs = ret, ks = k, as = first;
+            }
+        }
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const double r2 = __shfl_xor(rs, d, kWave);
+            const int32_t k2 = __shfl_xor(ks, d, kWave);
+            const float a2 = __shfl_xor(as, d, kWave);
+            if (plan_replaces(rs, ks, r2, k2)) rs = r2, ks = k2, as = a2;
+        }
+        // 3.
+        float mean = 0.f;
+        if (weighted) {
+            double z = 0.0, z2 = 0.0, acc = 0.0;
+            for (int32_t k = lane; k < n_cand; k += kWave) {
+                const double r = wt[k];
+                const double e = exp((r - rs) / a.temperature);  // r < r*: the argument is negative, -inf included
+                const double w = rs != rs ? 1.0 : (r != r ? 0.0 : (r == rs ? 1.0 : e));
+                z += w, z2 += w * w;
+                acc += w * (double)fa[k];
+            }
+            z = wave_sum_all(z), z2 = wave_sum_all(z2);  // Z >= 1: candidate k* has weight 1
+            const double sum = wave_sum_all(acc);
+            mean = (float)(sum / z);
+            if (lane == 0 && a.ess_out) a.ess_out[(int64_t)t * n + i] = z * z / z2;
+        }
+        if (lane == 0) {
+            if (a.plan_return_out) a.plan_return_out[(int64_t)t * n + i] = rs;
+            if (a.plan_index_out) a.plan_index_out[(int64_t)t * n + i] = ks;
+        }
+        // 4.
+        float av = as;
+        if (a.act_mode == EMEI_MPC_POLICY_ACT_MEAN) {  // wave-uniform
+            av = mean;
+            if constexpr (Env::kDiscrete) av = av >= 0.5f ? 1.f : 0.f;
+        }
+        if (lane == 0) store_action(a.actions_out, a.action_dtype, (int64_t)t * n + i, av);
+        {
+            R o[4], rew;
+            bool term;
+            Env::step(s, c, Env::decode_t((DrawT)av), a.p, a.freq_rate, o, rew, term);
+            ++steps;
+            const bool trunc = (a.max_episode_steps > 0) & (steps >= a.max_episode_steps);
+            done = (term ? EMEI_DONE_TERMINAL : 0u) | (trunc ? EMEI_DONE_TRUNCATED : 0u);
+            if (lane == 0) {
+                const int64_t at = (int64_t)t * n + i;
+                if (a.obs_out) a.obs_out[at] = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
+                if (a.reward_out) a.reward_out[at] = (float)rew;
+                if (a.done_out) a.done_out[at] = (uint8_t)done;
+            }
+        }
+        const bool reset_now = auto_reset && __builtin_amdgcn_readfirstlane(done) != 0u;  // wave-uniform
+        if (reset_now) {
+            ++episode;
+            steps = 0;
+            Env::init(s, a.reset_seed, g, episode, a.p);
+        }
+    }
+
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a.state[k * n + i] = s[k];
+        a.steps[i] = steps;
+        a.episode[i] = episode;
+        ((unsigned long long*)wt)[0] = (unsigned long long)done;  // lane 0's own slot, after its last use
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // emei_mpc_cem: receding-horizon CEM control episodes in ONE launch (the normative text: include/emei_hip.h).
 // The draws of the continuous envs read the mean AND the sigma from LDS: CandidateSpecLdsMap (emei_device.h); the discrete ones keep
 // CandidateSpecLds: the sigma-map path of draw_action has no coin-flip branch.
@@ -1881,6 +2062,24 @@ static int launch_env(const PendLaunch& L) {
             const dim3 mgrid((unsigned)((L.n + kWavesPerBlock - 1) / kWavesPerBlock));
             hipLaunchKernelGGL(pend_mpc_cem_kernel<Env>, mgrid, dim3(kBlock), 0, L.stream, m);
             if (L.selected) *L.selected = EMEI_KERNEL_PEND_MPC_CEM;
+            break;
+        }
+        case PEND_OP_MPC_POLICY: {
+            MpcPolicyArgs<Env> m;
+            m.state = (R*)L.state, m.steps = L.steps, m.episode = L.episode, m.trig = a.trig;
+            m.work = L.plan.return_out, m.actions_out = L.mpc_actions_out;
+            m.obs_out = (float4*)L.obs_out, m.reward_out = L.reward_out, m.done_out = L.done_out;
+            m.plan_return_out = L.plan_return_out, m.plan_index_out = L.plan_index_out, m.ess_out = L.ess_out;
+            m.n = L.n, m.n_steps = L.n_steps, m.horizon = L.horizon, m.n_cand = L.plan.n_candidates, m.freq_rate = L.freq_rate;
+            m.action_dtype = L.action_dtype, m.max_episode_steps = L.max_episode_steps, m.act_mode = L.act_mode, m.flags = L.flags;
+            m.reset_seed = L.seed, m.env_offset = L.env_offset, m.seed_stride = L.seed_stride;
+            m.discount = L.plan.discount, m.temperature = L.temperature;
+            m.p = a.p;
+            if (L.horizon < 1 || L.plan.n_candidates < 1 || !m.work || !m.actions_out) return EMEI_ERR_INVALID;
+            constexpr int kWavesPerBlock = kBlock / kWave;  // one wave per env
+            const dim3 mgrid((unsigned)((L.n + kWavesPerBlock - 1) / kWavesPerBlock));
+            hipLaunchKernelGGL(pend_mpc_policy_kernel<Env>, mgrid, dim3(kBlock), 0, L.stream, m, L.policy, L.policy_noise);
+            if (L.selected) *L.selected = EMEI_KERNEL_PEND_MPC_POLICY;
             break;
         }
         case PEND_OP_POLICY:

@@ -170,13 +170,6 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
-// all lanes of the wave end with the same bits: x + y is commutative, so both partners of a butterfly step compute the same sum
-__device__ __forceinline__ double wave_sum_all(double v) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
-
 // Second launch of emei_plan_mppi, one wave per env, lane l owning the candidates k = l, l + 64, ...:
 //   1. (k*, r*) from the env's partials, as plan_finish_kernel finds them;
 //   2. the lane turns its candidates' returns (left by the plan kernel, 8 B each) into the weights of the header's case analysis

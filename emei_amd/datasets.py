@@ -52,7 +52,10 @@ def collect(env, n_steps, actions=None, seed=0, device_rng=True, policy=None, mp
     InvertedDoublePendulum — a continuous env needs sigma=; seed defaults to `seed`, nominal to `refill` everywhere).  With
     planner="cem" in the dict a CEM controller acts instead (Engine.mpc_cem):
     dict(planner="cem", horizon=, n_candidates=, n_elites=[, iterations=, sigma=, sigma_min=, seed=, discount=, refill=, clamp=,
-    nominal=]); planner defaults to "mppi"."""
+    nominal=]); planner defaults to "mppi".  With planner="policy" a policy-guided controller acts (Engine.mpc_policy: plan around
+    a feedback policy under exploration noise, then the best or the weighted-mean first action):
+    dict(planner="policy", horizon=, n_candidates=, policy=, noise=[, act=, temperature=, seed_stride=, discount=]) — policy an
+    emei_amd.MLPPolicy and noise an emei_amd.PolicyNoise, both inside the dict."""
     if noise is not None and not (actions is None and mpc is None and isinstance(policy, MLPPolicy)):
         raise ValueError("collect: noise= goes with policy=MLPPolicy alone (the fused launch draws it)")
     eng = env.engine
@@ -65,21 +68,24 @@ def collect(env, n_steps, actions=None, seed=0, device_rng=True, policy=None, mp
             raise ValueError("collect: mpc= is an action source of its own; give neither actions= nor policy=")
         kw = dict(mpc)
         planner = kw.pop("planner", "mppi")
-        if planner not in ("mppi", "cem"):
-            raise ValueError(f"collect: mpc planner {planner!r}: 'mppi' or 'cem'")
+        if planner not in ("mppi", "cem", "policy"):
+            raise ValueError(f"collect: mpc planner {planner!r}: 'mppi', 'cem' or 'policy'")
         H, K = int(kw.pop("horizon")), int(kw.pop("n_candidates"))
-        plan_arg = float(kw.pop("temperature")) if planner == "mppi" else int(kw.pop("n_elites"))
-        refill = kw.get("refill")
-        if refill is None:
-            refill = kw["refill"] = 0.5 if eng.act_dim == 0 else 0.0
-        nominal = kw.pop("nominal", None)
-        if nominal is None:
-            shape = (H, N) + ((eng.act_dim,) if eng.act_dim > 1 else ())
-            nominal = torch.full(shape, float(refill), dtype=torch.float32, device=eng.device)
-        if planner == "mppi":
-            actions, next_obs, rew, done = eng.mpc_mppi(T, H, K, kw.pop("seed", seed), plan_arg, nominal, auto_reset=True, **kw)
+        if planner == "policy":  # the policy and its noise travel in the dict; there is no nominal and no refill
+            actions, next_obs, rew, done = eng.mpc_policy(T, H, K, kw.pop("policy"), kw.pop("noise"), auto_reset=True, **kw)
         else:
-            actions, next_obs, rew, done = eng.mpc_cem(T, H, K, plan_arg, kw.pop("seed", seed), nominal, auto_reset=True, **kw)
+            plan_arg = float(kw.pop("temperature")) if planner == "mppi" else int(kw.pop("n_elites"))
+            refill = kw.get("refill")
+            if refill is None:
+                refill = kw["refill"] = 0.5 if eng.act_dim == 0 else 0.0
+            nominal = kw.pop("nominal", None)
+            if nominal is None:
+                shape = (H, N) + ((eng.act_dim,) if eng.act_dim > 1 else ())
+                nominal = torch.full(shape, float(refill), dtype=torch.float32, device=eng.device)
+            if planner == "mppi":
+                actions, next_obs, rew, done = eng.mpc_mppi(T, H, K, kw.pop("seed", seed), plan_arg, nominal, auto_reset=True, **kw)
+            else:
+                actions, next_obs, rew, done = eng.mpc_cem(T, H, K, plan_arg, kw.pop("seed", seed), nominal, auto_reset=True, **kw)
     elif actions is None and isinstance(policy, MLPPolicy):  # the policy is evaluated inside the rollout kernel: ONE launch
         actions, next_obs, rew, done = eng.rollout_policy(T, policy, auto_reset=True, noise=noise)
     elif actions is None and policy is not None:

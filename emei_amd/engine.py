@@ -708,6 +708,49 @@ class Engine:
                                      _ptr(done), _ptr(pr), _ptr(er), L.FLAG_AUTO_RESET if auto_reset else 0, _stream()))
         return (act, obs, rew, done) + ((pr, er) if diagnostics else ())
 
+    @_on_device
+    def mpc_policy(self, T, H, K, policy, noise, act="best", temperature=None, seed_stride=None, discount=1.0, auto_reset=False,
+                   out=None, diagnostics=False):
+        """T control steps of policy-guided MPC in one launch (emei_mpc_policy; the envs mpc_mppi serves): per step t,
+        plan_policy(H, K, policy, noise_t, discount, temperature) from the current states with noise_t = `noise` under the seed
+        noise.seed + t * seed_stride, then the action — act="best": the best candidate's first action; act="mean": the
+        return-weighted mean of the K first actions (discrete envs: mean >= 0.5), which needs a temperature — and
+        step(action, auto_reset): bit for bit what that loop of plan_policy and step computes, state, counters and compact_done()
+        included.  policy: a policy.MLPPolicy with one hidden layer or none (a DeepMLPPolicy is not served by this call: plan_policy
+        serves it); noise: a policy.PolicyNoise.  seed_stride: default H, so that the noise keys of consecutive control steps do not
+        overlap; T = a + b steps equal a call with (a, noise) and one with (b, the noise under seed + a * seed_stride).
+        out: (obs, reward, done) as rollout's.
+        -> (actions [T, N(, act_dim)] int64 / float32, obs [T, N, obs_dim] f32, reward [T, N] f32, done [T, N] u8
+        [, plan_return float64 [T, N], plan_index int32 [T, N][, ess float64 [T, N]: with a temperature]])."""
+        from .policy import DeepMLPPolicy
+
+        T = int(T)
+        if T < 1:
+            raise ValueError(f"n_steps={T} must be >= 1")
+        if isinstance(policy, DeepMLPPolicy):
+            raise NotImplementedError("mpc_policy: the two-hidden-layer network (DeepMLPPolicy) is not served by the fused controller; "
+                                      "plan_policy serves it (one plan_policy and one step per control step)")
+        if act not in ("best", "mean"):
+            raise ValueError(f"act={act!r}: 'best' or 'mean'")
+        if act == "mean" and temperature is None:
+            raise ValueError("act='mean' needs a temperature")
+        H, K, ps, ns, discount, temperature = self._plan_policy_args(H, K, policy, noise, discount, temperature)
+        stride = H if seed_stride is None else int(seed_stride)
+        obs, rew, done = self._check_outputs(out, (T,)) if out is not None else self.alloc_outputs(T)
+        ws = self._workspace("_mpc_policy_ws", L.lib().emei_mpc_policy_workspace_bytes, K)
+        dtype = torch.int64 if self.act_dim == 0 else torch.float32
+        new = lambda dt: torch.empty((T, self.n_envs), dtype=dt, device=self.device)
+        actions = torch.empty((T, self.n_envs) + self._act_tail, dtype=dtype, device=self.device)
+        pr = new(torch.float64) if diagnostics else None
+        pi = new(torch.int32) if diagnostics else None
+        es = new(torch.float64) if diagnostics and temperature is not None else None
+        L.check(L.lib().emei_mpc_policy(self._h, T, H, K, C.byref(ps), C.byref(ns), _seed64(stride),
+                                        L.MPC_POLICY_ACT_MEAN if act == "mean" else L.MPC_POLICY_ACT_BEST, discount,
+                                        1.0 if temperature is None else temperature, _ptr(ws), _ptr(actions), _ACT_DTYPES[dtype],
+                                        _ptr(obs), _ptr(rew), _ptr(done), _ptr(pr), _ptr(pi), _ptr(es),
+                                        L.FLAG_AUTO_RESET if auto_reset else 0, _stream()))
+        return (actions, obs, rew, done) + ((pr, pi) + ((es,) if es is not None else ()) if diagnostics else ())
+
     def _check_plan_out(self, name, out, shape, source, source_name):
         """an output tensor of plan_mppi / plan_cem: float32 [H, N(, act_dim)], `source` itself (in place) or clear of it"""
         if not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous() \

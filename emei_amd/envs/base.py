@@ -384,6 +384,22 @@ class HipEnv(EmeiEnv):
                                       returns=returns, length=length, ess=ess, value=value)
         return tuple(t.cpu().numpy() for t in res) if isinstance(start_state, np.ndarray) else res
 
+    def mpc_policy(self, n_steps, horizon, n_candidates, policy, noise, act="best", temperature=None, seed_stride=None, discount=1.0,
+                   auto_reset=None, diagnostics=False):
+        """n_steps control steps of policy-guided MPC in one launch (Engine.mpc_policy, ABI emei_mpc_policy; the 4-state envs and the
+        InvertedDoublePendulum): per step plan_policy(horizon, n_candidates, policy, noise under the seed noise.seed + t * seed_stride,
+        discount, temperature), the best candidate's first action (act="best") or the weighted mean of the first actions (act="mean",
+        needs a temperature; discrete envs: >= 0.5), and step() — the same bits as that loop —
+        (actions [n_steps, num_envs(, act_dim)], obs float32 [n_steps, num_envs, obs_dim], reward float32, terminal bool, truncated
+        bool [, plan_return float64 [n_steps, num_envs], plan_index int32 [n_steps, num_envs][, ess float64 with a temperature]]),
+        tensors on the env's device.  auto_reset: the env's own setting unless given.  Other arguments as Engine.mpc_policy."""
+        assert self.state is not None, "Call reset before using step method."  # base_control.py:67
+        res = self.engine.mpc_policy(n_steps, horizon, n_candidates, policy, noise, act=act, temperature=temperature,
+                                     seed_stride=seed_stride, discount=discount,
+                                     auto_reset=self.auto_reset if auto_reset is None else auto_reset, diagnostics=diagnostics)
+        act_t, obs, rew, done = res[:4]
+        return (act_t, obs, rew, (done & 1).bool(), (done & 2).bool()) + tuple(res[4:])
+
     def mpc_mppi(self, n_steps, horizon, n_candidates, seed, temperature, nominal, discount=1.0, sigma=None, refill=None, clamp=None,
                  auto_reset=None, diagnostics=False):
         """n_steps control steps of receding-horizon MPPI in one launch (Engine.mpc_mppi, ABI emei_mpc_mppi; the 4-state envs and the

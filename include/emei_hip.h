@@ -64,7 +64,11 @@ extern "C" {
  *    is untouched, no kernel id);
  *    emei_plan_policy_deep (emei_plan_policy around a struct emei_policy_deep network, with an optional terminal value — a second
  *    struct emei_policy_deep with one output, added to the return of every candidate that never terminated; the workspace is
- *    emei_plan_policy_workspace_bytes'; the handle is untouched, no kernel id). */
+ *    emei_plan_policy_workspace_bytes'; the handle is untouched, no kernel id);
+ *    emei_mpc_policy_workspace_bytes, emei_mpc_policy (policy-guided control episodes in one launch: per control step emei_plan_policy
+ *    around a one-layer struct emei_policy under a noise seed that advances by seed_stride, the best or the weighted-mean first
+ *    action, emei_step and auto-reset, for the envs emei_mpc_mppi serves), EMEI_KERNEL_PEND_MPC_POLICY / EMEI_KERNEL_BODY_MPC_POLICY
+ *    in an enum of their own (enum emei_kernel_id_mpc_policy). */
 #define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
@@ -912,6 +916,63 @@ EMEI_API int emei_plan_policy_deep(emei_env* h, int32_t horizon, int32_t n_candi
                                    float* mean_action_out, double* best_return_out, int32_t* best_index_out, int32_t* best_length_out,
                                    double* return_out, double* ess_out, void* stream);
 
+/* Policy-guided receding-horizon control, whole episodes in ONE launch (plus the small one that packs the done mask): what the loop
+ * "emei_plan_policy with a fresh noise seed, best or weighted-mean first action, emei_step" does in three launches and a new noise
+ * struct per control step — the controller of MBOP, LOOP and POLO run on the true dynamics.  The envs are emei_mpc_mppi's: the
+ * 4-state family on its own kernels and the four InvertedDoublePendulum envs (any integrator, either precision, no observation
+ * noise; obs_out is [n_steps, n_envs, 6]) on the body family.  Unlike emei_mpc_mppi there is no nominal to carry from one control
+ * step to the next — the policy is the warm start — so there is no horizon cap.  `policy` and `noise` are emei_plan_policy's structs
+ * (one-layer struct emei_policy only; all three noise modes, both output modes) with DEVICE pointers, read during the launch and not
+ * retained; they must not overlap any output or the workspace.
+ *
+ * Semantics (normative).  For every env i, g = env_index_offset + i, and t = 0 .. n_steps - 1:
+ *   1. Plan.  Exactly emei_plan_policy(h, horizon, n_candidates, policy, noise_t, discount, temperature, start_state = NULL, ...) for
+ *      env i, where noise_t is `noise` with seed = noise.seed + t * seed_stride (mod 2^64): step h of candidate k draws from
+ *          W[m] = philox4x32_10(key = noise.seed + t * seed_stride + h (mod 2^64), counter = (g lo, g hi, k, m >> 2)).v[m & 3].
+ *      Candidate 0 takes NO noise.  The start is the env's current state, x_0 its float32 observation.  Scoring, the planner's order,
+ *      the weight case analysis and the summation tree are emei_plan_policy's: lane l adds the candidates k = l, l + 64, .. in
+ *      ascending order, then the butterfly d = 1 .. 32.
+ *      plan_return_out[t, i] = r*, plan_index_out[t, i] = k* (int32), ess_out[t, i] as emei_plan_policy's ess_out; float64 / int32
+ *      [n_steps, n_envs], each may be NULL.
+ *   2. Act.  EMEI_MPC_POLICY_ACT_BEST: a_t is what best_action_out would hold, candidate k*'s action at step 0.
+ *      EMEI_MPC_POLICY_ACT_MEAN: on the continuous envs a_t is the float32 mean_action_out value; on the discrete envs
+ *      a_t = (mean >= 0.5f) ? 1 : 0.  actions_out[t, i(, :)] in action_dtype (U8 / I32 / I64 discrete, F32 continuous),
+ *      [n_steps, n_envs(, act_dim)].  Required.  `temperature` is consulted and checked only with ACT_MEAN or a non-NULL ess_out.
+ *   3. Step.  Clause 4 of emei_mpc_mppi: exactly emei_step(a_t, flags) for env i, with emei_rollout's arithmetic: the TimeLimit
+ *      counter, the EMEI_DONE_* bits and EMEI_FLAG_AUTO_RESET with the handle's reset key and episode counter.  obs_out / reward_out /
+ *      done_out at [t, i] as emei_rollout writes them; any of the three may be NULL.  After a reset the next plan observes the new
+ *      episode's state.
+ * After the call the handle is as after the equivalent loop: state, step and episode counters, the done mask emei_compact_done
+ * reads.  Every output is bit-identical to that loop's.
+ * Consequences.  Chunking: n_steps = a + b in one call equals a call with (a, noise.seed) followed by one with
+ * (b, noise.seed + a * seed_stride).  Replay: actions_out fed to emei_rollout from the same start reproduces obs_out, reward_out and
+ * done_out.  Sharding: results depend on g only, not on n_envs or the shard.  Stream: the call neither allocates nor synchronises
+ * (capturable).  n_candidates = 1 is the deterministic policy: the actions of emei_rollout_policy.  Seed stride: any value is legal;
+ * with seed_stride >= horizon the keys of consecutive control steps do not overlap (with seed_stride = 1 step h + 1 of control step t
+ * and step h of control step t + 1 draw from the same key).
+ * Work split: one wave per env, its candidates spread over the 64 lanes (pend_mpc_policy_kernel / body_mpc_policy_kernel); many
+ * candidates with few envs favour emei_plan_policy's route, which spreads all candidates over the device.
+ * workspace: emei_mpc_policy_workspace_bytes(n_envs, n_candidates) = 12 * n_envs * n_candidates bytes rounded up to a multiple of 8,
+ * device memory, 8-byte aligned, contents irrelevant before and after: every candidate's float64 return [n_envs, n_candidates], then
+ * its float32 action of step 0 (every env served has one action component).
+ * EMEI_ERR_INVALID before any HIP call, each message naming the argument, in this order: n_steps < 1; horizon < 1; n_candidates < 1;
+ * discount outside (0, 1]; unknown act_mode; with ACT_MEAN or a non-NULL ess_out, temperature not finite or <= 0;
+ * emei_rollout_policy's struct checks up to and including policy.reserved; NULL noise, then emei_rollout_policy_noisy's noise checks
+ * in their order; a NULL handle; NULL w2 or b2, hidden > 0 with NULL w1 or b1; n_envs * n_candidates > 2^31 - 1; a wrong
+ * action_dtype; unknown flags; NULL workspace, then NULL actions_out; a GAUSS mode on a discrete env or EPS_GREEDY on a continuous
+ * one.  EMEI_ERR_STATE without a state.  EMEI_ERR_UNSUPPORTED where emei_mpc_mppi gives it, with its messages: the other handles
+ * that step on the body kernels (HalfCheetah, Hopper; InvertedPendulum with another integrator or observation noise), an
+ * InvertedDoublePendulum handle with observation noise, a handle with observation peers set. */
+enum emei_mpc_policy_act { EMEI_MPC_POLICY_ACT_BEST = 0, EMEI_MPC_POLICY_ACT_MEAN = 1 };
+/* bytes of device scratch emei_mpc_policy needs for this shape; host only, no handle, no HIP call.
+ * Negative (EMEI_ERR_INVALID) where emei_plan_mppi_workspace_bytes is. */
+EMEI_API int64_t emei_mpc_policy_workspace_bytes(int64_t n_envs, int32_t n_candidates);
+EMEI_API int emei_mpc_policy(emei_env* h, int32_t n_steps, int32_t horizon, int32_t n_candidates, const emei_policy* policy,
+                             const emei_policy_noise* noise, uint64_t seed_stride, int32_t act_mode, double discount,
+                             double temperature, void* workspace, void* actions_out, int action_dtype, float* obs_out,
+                             float* reward_out, uint8_t* done_out, double* plan_return_out, int32_t* plan_index_out, double* ess_out,
+                             uint32_t flags, void* stream);
+
 /* Which kernel the LAST emei_step / emei_rollout of this handle launched (enum emei_kernel_id): a debug /
  * test getter, so that a parity test can assert that the path it checked is the path bench.py times. */
 enum emei_kernel_id {
@@ -941,6 +1002,13 @@ enum emei_kernel_id {
     EMEI_KERNEL_BODY_POLICY_DEEP_RK4 = 23    /* body_policy_rollout_deep_kernel<Body, true> */
 };
 EMEI_API int emei_last_rollout_kernel(emei_env* h);
+/* The ids of emei_mpc_policy's kernels, which emei_last_rollout_kernel reports as well (the call steps the handle).  An enum of their
+ * own: enum emei_kernel_id is the closed list 0 .. 23 that the bindings of the earlier entry points mirror value for value, and it
+ * stays that list; these continue its numbering. */
+enum emei_kernel_id_mpc_policy {
+    EMEI_KERNEL_PEND_MPC_POLICY = 24, /* pend_mpc_policy_kernel<Env>: emei_mpc_policy on the 4-state kernels */
+    EMEI_KERNEL_BODY_MPC_POLICY = 25  /* body_mpc_policy_kernel<Body, RK4>: emei_mpc_policy on an InvertedDoublePendulum handle */
+};
 
 /* --- Multi-GPU observation return by PEER WRITES (one process per GPU; north_star: "shards env instances across up to 8 GPUs of one node
  * ... only for the batched observation return"; SURVEY §5: "hipIpc peer writes from the step kernel's epilogue").  The reference has no

@@ -14,8 +14,11 @@ the InvertedDoublePendulum 400 and 40, so that its MPPI windows exceed 10 ms).
 --planner cem: the same comparison for Engine.mpc_cem (emei_mpc_cem) against the README's CEM loop — per control step a roll, a
 refill, a fresh std, ITERATIONS = 3 times (a clamp of the mean on the discrete envs, plan_cem in place: two launches, a floor of the
 std on the continuous ones), and a step — with N_ELITES = 8, at the same shapes (tests/test_gpu_mpc_cem.py: the same bits).
+--planner policy: the same comparison for Engine.mpc_policy (emei_mpc_policy) against the README's policy-guided loop — per control
+step a new PolicyNoise under the seed 1 + t * H, plan_policy (two launches) and a step — around an MLPPolicy with HIDDEN = 64 units,
+act="mean" (tests/test_gpu_mpc_policy.py: the same bits); the nominal is unused.
 One JSON line per shape.  Run on the GPU box:
-    python tools/mpc_timing.py [--planner mppi|cem] [--warmup 2] [--repeats 7] [--only INDEX]"""
+    python tools/mpc_timing.py [--planner mppi|cem|policy] [--warmup 2] [--repeats 7] [--only INDEX]"""
 import argparse
 import json
 import os
@@ -38,6 +41,7 @@ SHAPES = [
 ]
 TEMPERATURE, DISCOUNT = 0.5, 0.99
 ITERATIONS, N_ELITES, SIGMA_MIN = 3, 8, 0.05  # --planner cem
+HIDDEN, NOISE_STD, EPSILON = 64, 0.2, 0.2  # --planner policy
 
 
 def loop_episode(eng, T, H, K, seed, nominal, sigma, refill, lo, hi):
@@ -66,11 +70,30 @@ def cem_loop_episode(eng, T, H, K, seed, nominal, sigma, refill, lo, hi):
         eng.step((nominal[0] >= 0.5).long() if eng.act_dim == 0 else nominal[0], auto_reset=True)
 
 
+def make_policy(eng):
+    """an MLPPolicy with HIDDEN units and the noise constructor of the env's kind (--planner policy)"""
+    from emei_amd.policy import MLPPolicy, PolicyNoise
+
+    g = torch.Generator().manual_seed(0)
+    r = lambda *s: torch.randn(*s, generator=g) * 1.5 / s[-1] ** 0.5
+    n_out = max(eng.act_dim, 1)
+    pol = MLPPolicy(r(n_out, HIDDEN), r(n_out), r(HIDDEN, eng.obs_dim), r(HIDDEN))
+    kw = dict(epsilon=EPSILON) if eng.act_dim == 0 else dict(std=NOISE_STD)
+    return pol, (lambda seed: PolicyNoise(seed, **kw))
+
+
+def policy_loop_episode(eng, T, H, K, seed, pol, noise):
+    """the README's policy-guided loop at the Engine level"""
+    for t in range(T):
+        mean = eng.plan_policy(H, K, pol, noise(seed + t * H), discount=DISCOUNT, temperature=TEMPERATURE)[3]
+        eng.step((mean >= 0.5).long() if eng.act_dim == 0 else mean, auto_reset=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--planner", choices=("mppi", "cem"), default="mppi")
+    ap.add_argument("--planner", choices=("mppi", "cem", "policy"), default="mppi")
     ap.add_argument("--only", type=int, default=None, help="index of the one shape to run")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -92,8 +115,12 @@ def main():
             nominal.fill_(refill)
             torch.cuda.synchronize()
 
+        pol, noise = make_policy(eng) if args.planner == "policy" else (None, None)
+
         def fused():
-            if args.planner == "cem":
+            if args.planner == "policy":
+                eng.mpc_policy(T, H, K, pol, noise(1), act="mean", temperature=TEMPERATURE, discount=DISCOUNT, auto_reset=True, out=outs)
+            elif args.planner == "cem":
                 eng.mpc_cem(T, H, K, N_ELITES, 1, nominal, iterations=ITERATIONS, sigma=sigma, sigma_min=SIGMA_MIN, discount=DISCOUNT,
                             refill=refill, clamp=(lo, hi), auto_reset=True, out=outs)
             else:
@@ -101,6 +128,8 @@ def main():
                              auto_reset=True, out=outs)
 
         def loop():
+            if args.planner == "policy":
+                return policy_loop_episode(eng, T, H, K, 1, pol, noise)
             (cem_loop_episode if args.planner == "cem" else loop_episode)(eng, T, H, K, 1, nominal, sigma, refill, lo, hi)
 
         def timed(fn):
