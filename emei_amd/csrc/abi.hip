@@ -304,7 +304,7 @@ extern "C" EMEI_API int emei_create(const emei_config* cfg, emei_env** out) {
     }
     if (steps_as_body(*cfg)) {  // occupancy of the rollout kernel: the automatic chunking policy (body_kernels.h:WorkQueue)
         BodyLaunch L;
-        L.op = BODY_OP_OCCUPANCY, L.env_id = cfg->env_id, L.precision = cfg->precision, L.integrator = cfg->integrator;
+        L.op = OP_OCCUPANCY, L.env_id = cfg->env_id, L.precision = cfg->precision, L.integrator = cfg->integrator;
         L.solver = (int)cfg->solver, L.selected = &h->resident_waves;
         if (body_launch(L) != EMEI_OK) h->resident_waves = 0;  // unknown: the automatic policy then stays with one-piece launches
     }
@@ -342,40 +342,37 @@ static int wrong_device(const emei_env* h, const char* fn) {
         if (int rc_ = wrong_device((h), (fn))) return rc_;      \
     } while (0)
 
-static PendLaunch pend_base(emei_env* h, void* stream) {
-    PendLaunch L;
+// The handle's part of a launch descriptor, laid under the call's own fields in `L` (L.n != 0: a count of the call's own)
+static void handle_fields(const emei_env* h, void* stream, LaunchCommon& L) {
     L.env_id = h->cfg.env_id;
     L.precision = h->cfg.precision;
-    L.ode_method = h->cfg.ode_method;
     L.state = h->state;
     L.steps = h->steps;
     L.episode = h->episode;
     L.done_mask = h->done_mask;
-    L.n = h->cfg.n_envs;
+    if (L.n == 0) L.n = h->cfg.n_envs;
     L.freq_rate = h->cfg.freq_rate;
     L.max_episode_steps = h->cfg.max_episode_steps;
     L.seed = h->cfg.seed;
     L.env_offset = h->cfg.env_index_offset;
-    L.p = h->pend;
     L.trig = h->trig;
     L.stream = (hipStream_t)stream;
+}
+
+static PendLaunch pend_base(emei_env* h, void* stream, const LaunchCommon& call = LaunchCommon()) {
+    PendLaunch L;
+    static_cast<LaunchCommon&>(L) = call;
+    handle_fields(h, stream, L);
+    L.ode_method = h->cfg.ode_method;
+    L.p = h->pend;
     L.peers = h->peers;
     return L;
 }
 
-static BodyLaunch body_base(emei_env* h, void* stream) {
+static BodyLaunch body_base(emei_env* h, void* stream, const LaunchCommon& call = LaunchCommon()) {
     BodyLaunch L;
-    L.env_id = h->cfg.env_id;
-    L.precision = h->cfg.precision;
-    L.state = h->state;
-    L.steps = h->steps;
-    L.episode = h->episode;
-    L.done_mask = h->done_mask;
-    L.n = h->cfg.n_envs;
-    L.freq_rate = h->cfg.freq_rate;
-    L.max_episode_steps = h->cfg.max_episode_steps;
-    L.seed = h->cfg.seed;
-    L.env_offset = h->cfg.env_index_offset;
+    static_cast<LaunchCommon&>(L) = call;
+    handle_fields(h, stream, L);
     L.dt = h->cfg.real_time_scale;
     L.integrator = h->cfg.integrator;
     L.solver = (int)h->cfg.solver;
@@ -384,27 +381,50 @@ static BodyLaunch body_base(emei_env* h, void* stream) {
     L.noise.shared = h->cfg.noise_layout == EMEI_NOISE_SHARED;
     L.env_params.mask = h->cfg.env_param_mask;
     memcpy(L.env_params.v, h->cfg.env_params, sizeof(L.env_params.v));
-    L.trig = h->trig;
     L.cap_hits = h->cap_hits;
     L.work = h->work, L.chunk_steps = h->cfg.rollout_chunk_steps, L.resident_waves = h->resident_waves;
-    L.stream = (hipStream_t)stream;
     return L;
+}
+
+// THE family launch: every launch on a handle but emei_step_host's goes through here.  `call` holds the op and the call's own
+// fields (launch.h: LaunchOp), action_dtype the dtype of the actions a 4-state kernel reads or writes.  The ops that step or plan go
+// to the family emei_rollout runs for this handle (steps_as_body); reset, get_obs and init_obs touch the state alone and stay with
+// the env's own family, which for an InvertedPendulum on the body kernels is the other one.  The ops that step the handle report
+// their kernel (emei_last_rollout_kernel); the queries leave the handle as it is.
+static int launch(emei_env* h, const LaunchCommon& call, void* stream, int action_dtype = 0) {
+    const int op = call.op;
+    const bool state_only = op == OP_RESET || op == OP_GET_OBS || op == OP_INIT_OBS;
+    const bool steps = op == OP_ROLLOUT || op == OP_MPC_MPPI || op == OP_MPC_CEM || op == OP_MPC_POLICY || op == OP_POLICY ||
+                       op == OP_POLICY_NOISY || op == OP_POLICY_DEEP;
+    int* const selected = steps ? &h->last_kernel : nullptr;
+    const bool on_body = state_only ? !is_pend(h->cfg.env_id) : steps_as_body(h->cfg);
+    if (!on_body) {
+        PendLaunch L = pend_base(h, stream, call);
+        L.action_dtype = action_dtype, L.selected = selected;
+        return pend_launch(L);
+    }
+    BodyLaunch L = body_base(h, stream, call);
+    L.selected = selected;
+    return body_launch(L);
+}
+
+// the tail of the entry points that launch: `rc` as the launches left it
+static int launched(const char* fn, int rc) {
+    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+}
+
+static int check_flags(const char* fn, uint32_t flags) {
+    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "%s: unknown flags 0x%x", fn, flags);
+    return EMEI_OK;
 }
 
 extern "C" EMEI_API int emei_reset(emei_env* h, uint64_t seed, void* stream) {
     if (!h) return fail(EMEI_ERR_INVALID, "emei_reset: null handle");
     EMEI_ON_DEVICE(h, "emei_reset");
     h->cfg.seed = seed;
-    int rc;
-    if (is_pend(h->cfg.env_id)) {
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_RESET;
-        rc = pend_launch(L);
-    } else {
-        BodyLaunch L = body_base(h, stream);
-        L.op = BODY_OP_RESET;
-        rc = body_launch(L);
-    }
+    LaunchCommon c;
+    c.op = OP_RESET;
+    const int rc = launch(h, c, stream);
     if (rc != EMEI_OK) return fail(rc, "emei_reset: launch failed");
     h->has_state = true;
     return EMEI_OK;
@@ -446,17 +466,9 @@ extern "C" EMEI_API int emei_get_obs(emei_env* h, double* obs_aos, void* stream)
     if (!h || !obs_aos) return fail(EMEI_ERR_INVALID, "emei_get_obs: null argument");
     EMEI_ON_DEVICE(h, "emei_get_obs");
     if (!h->has_state) return fail(EMEI_ERR_STATE, "emei_get_obs: call reset before using the state");
-    if (is_pend(h->cfg.env_id)) {
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_GET_OBS;
-        L.obs_f64 = obs_aos;
-        int rc = pend_launch(L);
-        return rc == EMEI_OK ? rc : fail(rc, "emei_get_obs: launch failed");
-    }
-    BodyLaunch L = body_base(h, stream);
-    L.op = BODY_OP_GET_OBS;
-    L.obs_f64 = obs_aos;
-    int rc = body_launch(L);
+    LaunchCommon c;
+    c.op = OP_GET_OBS, c.obs_f64 = obs_aos;
+    const int rc = launch(h, c, stream);
     return rc == EMEI_OK ? rc : fail(rc, "emei_get_obs: launch failed");
 }
 
@@ -604,43 +616,25 @@ extern "C" EMEI_API int emei_rollout(emei_env* h, int32_t n_steps, const void* a
     EMEI_ON_DEVICE(h, "emei_rollout");
     if (n_steps < 1) return fail(EMEI_ERR_INVALID, "emei_rollout: n_steps=%d < 1", n_steps);
     if (!h->has_state) return fail(EMEI_ERR_STATE, "Call reset before using step method.");  // base_control.py:67
-    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "emei_rollout: unknown flags 0x%x", flags);
+    if (int rc = check_flags("emei_rollout", flags)) return rc;
     if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
-    int rc;
     if (h->peers.count > 0 && n_steps > h->peers.max_steps)
         return fail(EMEI_ERR_INVALID, "emei_rollout: n_steps=%d but the registered observation peers hold %d rows (emei_set_obs_peers)", n_steps,
                     h->peers.max_steps);
-    if (!steps_as_body(h->cfg)) {
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_ROLLOUT;
-        L.actions = actions;
-        L.action_dtype = action_dtype;
-        L.obs_out = obs_out;
-        L.reward_out = reward_out;
-        L.done_out = done_out;
-        L.n_steps = n_steps;
-        L.flags = flags;
-        L.selected = &h->last_kernel;
-        rc = pend_launch(L);
-        if (rc == EMEI_ERR_UNSUPPORTED && h->peers.count > 0)
-            return fail(rc, "emei_rollout: observation peers are set (emei_set_obs_peers), which only the staged kernel of the CartPole family "
-                            "serves: n_envs a multiple of 64, n_steps >= 16, all three outputs, 16-byte aligned buffers (n_envs=%lld, n_steps=%d)",
-                        (long long)h->cfg.n_envs, n_steps);
-    } else {
-        if (h->peers.count > 0)
-            return fail(EMEI_ERR_UNSUPPORTED, "emei_rollout: observation peers are set (emei_set_obs_peers), which the body kernels do not serve");
-        BodyLaunch L = body_base(h, stream);
-        L.op = BODY_OP_ROLLOUT;
-        L.actions = actions;
-        L.obs_out = obs_out;
-        L.reward_out = reward_out;
-        L.done_out = done_out;
-        L.n_steps = n_steps;
-        L.flags = flags;
-        L.selected = &h->last_kernel;
-        rc = body_launch(L);
-    }
-    return rc == EMEI_OK ? rc : fail(rc, "emei_rollout: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+    if (h->peers.count > 0 && steps_as_body(h->cfg))
+        return fail(EMEI_ERR_UNSUPPORTED, "emei_rollout: observation peers are set (emei_set_obs_peers), which the body kernels do not serve");
+    LaunchCommon c;
+    c.op = OP_ROLLOUT;
+    c.actions = actions;
+    c.obs_out = obs_out, c.reward_out = reward_out, c.done_out = done_out;
+    c.n_steps = n_steps;
+    c.flags = flags;
+    const int rc = launch(h, c, stream, action_dtype);
+    if (rc == EMEI_ERR_UNSUPPORTED && h->peers.count > 0)
+        return fail(rc, "emei_rollout: observation peers are set (emei_set_obs_peers), which only the staged kernel of the CartPole family "
+                        "serves: n_envs a multiple of 64, n_steps >= 16, all three outputs, 16-byte aligned buffers (n_envs=%lld, n_steps=%d)",
+                    (long long)h->cfg.n_envs, n_steps);
+    return launched("emei_rollout", rc);
 }
 
 extern "C" EMEI_API int emei_step_host(emei_env* h, const void* actions_host, int action_dtype, double* obs64_host, float* obs32_host,
@@ -649,7 +643,7 @@ extern "C" EMEI_API int emei_step_host(emei_env* h, const void* actions_host, in
         return fail(EMEI_ERR_INVALID, "emei_step_host: null argument");
     EMEI_ON_DEVICE(h, "emei_step_host");
     if (!h->has_state) return fail(EMEI_ERR_STATE, "Call reset before using step method.");  // base_control.py:67
-    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "emei_step_host: unknown flags 0x%x", flags);
+    if (int rc = check_flags("emei_step_host", flags)) return rc;
     if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     if (!steps_as_body(h->cfg) && h->cfg.n_envs == 1) {
@@ -659,7 +653,7 @@ extern "C" EMEI_API int emei_step_host(emei_env* h, const void* actions_host, in
             *h->host_flag = 0;
         }
         PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_ROLLOUT;
+        L.op = OP_ROLLOUT;
         L.actions = actions_host;
         L.action_dtype = action_dtype;
         L.obs_out = obs32_host, L.reward_out = reward_host, L.done_out = done_host, L.obs_f64 = obs64_host;
@@ -670,7 +664,7 @@ extern "C" EMEI_API int emei_step_host(emei_env* h, const void* actions_host, in
         L.flag_value = ++h->flag_seq;
         if (L.flag_value == 0) L.flag_value = ++h->flag_seq;  // 0 is the word's initial content
         int rc = pend_launch(L);
-        if (rc != EMEI_OK) return fail(rc, "emei_step_host: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+        if (rc != EMEI_OK) return launched("emei_step_host", rc);
         // poll the word (the kernel's last store, system scope); a launch that does not finish within ~5 ms is handed to the
         // runtime's own wait, which also surfaces a device fault
         volatile uint32_t* flag = h->host_flag;
@@ -750,19 +744,12 @@ static double* plan_returns(const emei_env* h, int32_t n_candidates, void* works
     return (double*)((char*)workspace + plan_partials_bytes(h->cfg.n_envs, h->cfg.n_envs * (int64_t)n_candidates));
 }
 
-// the plan kernel of the family emei_rollout runs for this handle; actions / action_dtype / final_obs: PLAN_GIVEN only
-static int launch_plan(emei_env* h, const PlanLaunch& p, int32_t horizon, const void* actions, int action_dtype, float* final_obs,
-                       void* stream) {
-    if (!steps_as_body(h->cfg)) {
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_PLAN, L.plan = p;
-        L.actions = actions, L.action_dtype = action_dtype, L.n_steps = horizon, L.obs_out = final_obs;
-        return pend_launch(L);
-    }
-    BodyLaunch L = body_base(h, stream);
-    L.op = BODY_OP_PLAN, L.plan = p;
-    L.actions = actions, L.n_steps = horizon, L.obs_out = final_obs;
-    return body_launch(L);
+// what every OP_PLAN call sets alike (launch.h: PlanMode)
+static LaunchCommon plan_call(int mode, const double* start_rows, int32_t horizon, int32_t n_candidates, double discount) {
+    LaunchCommon c;
+    c.op = OP_PLAN, c.n_steps = horizon;
+    c.plan.mode = mode, c.plan.start_rows = start_rows, c.plan.n_candidates = n_candidates, c.plan.discount = discount;
+    return c;
 }
 
 extern "C" EMEI_API int emei_evaluate_sequences(emei_env* h, int32_t horizon, int32_t n_candidates, const void* actions, int action_dtype,
@@ -776,11 +763,10 @@ extern "C" EMEI_API int emei_evaluate_sequences(emei_env* h, int32_t horizon, in
     if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
     EMEI_ON_DEVICE(h, fn);
     if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    PlanLaunch p;
-    p.mode = PLAN_GIVEN, p.start_rows = start_state, p.n_candidates = n_candidates, p.discount = discount;
-    p.return_out = return_out, p.length_out = length_out;
-    const int rc = launch_plan(h, p, horizon, actions, action_dtype, final_obs_out, stream);
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    LaunchCommon c = plan_call(PLAN_GIVEN, start_state, horizon, n_candidates, discount);
+    c.plan.return_out = return_out, c.plan.length_out = length_out;
+    c.actions = actions, c.obs_out = final_obs_out;
+    return launched(fn, launch(h, c, stream, action_dtype));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -830,7 +816,7 @@ extern "C" EMEI_API int emei_sample_candidates(emei_env* h, int32_t horizon, int
     EMEI_ON_DEVICE(h, fn);
     const int rc = launch_sample_candidates(candidate_spec(h, seed, nominal, sigma), h->cfg.n_envs, n_candidates, horizon, h->act_dim,
                                             actions_out, action_dtype, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    return launched(fn, rc);
 }
 
 extern "C" EMEI_API int emei_plan_shooting(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal,
@@ -844,14 +830,14 @@ extern "C" EMEI_API int emei_plan_shooting(emei_env* h, int32_t horizon, int32_t
     if (!workspace || !best_action_out || !best_return_out || !best_index_out) return fail(EMEI_ERR_INVALID, "%s: null argument", fn);
     EMEI_ON_DEVICE(h, fn);
     if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    PlanLaunch p;
-    p.mode = PLAN_DRAWN, p.start_rows = start_state, p.n_candidates = n_candidates, p.discount = discount;
+    LaunchCommon c = plan_call(PLAN_DRAWN, start_state, horizon, n_candidates, discount);
+    PlanLaunch& p = c.plan;
     p.cand = candidate_spec(h, seed, nominal, sigma), p.partials = workspace;
-    int rc = launch_plan(h, p, horizon, nullptr, 0, nullptr, stream);
+    int rc = launch(h, c, stream);
     if (rc == EMEI_OK)
         rc = launch_plan_finish(workspace, p.cand, h->cfg.n_envs, n_candidates, horizon, h->act_dim, best_action_out, action_dtype,
                                 best_sequence_out, best_return_out, best_index_out, best_length_out, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    return launched(fn, rc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -877,14 +863,14 @@ extern "C" EMEI_API int emei_plan_mppi(emei_env* h, int32_t horizon, int32_t n_c
     if (!nominal_out) return fail(EMEI_ERR_INVALID, "%s: null nominal_out", fn);
     EMEI_ON_DEVICE(h, fn);
     if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    PlanLaunch p;
-    p.mode = PLAN_DRAWN_KEEP, p.start_rows = start_state, p.n_candidates = n_candidates, p.discount = discount;
+    LaunchCommon c = plan_call(PLAN_DRAWN_KEEP, start_state, horizon, n_candidates, discount);
+    PlanLaunch& p = c.plan;
     p.cand = candidate_spec(h, seed, nominal, sigma), p.partials = workspace, p.return_out = plan_returns(h, n_candidates, workspace);
-    int rc = launch_plan(h, p, horizon, nullptr, 0, nullptr, stream);
+    int rc = launch(h, c, stream);
     if (rc == EMEI_OK)
         rc = launch_plan_mppi_finish(workspace, p.return_out, p.cand, h->cfg.n_envs, n_candidates, horizon, h->act_dim, temperature, nominal_out,
                                      best_return_out, best_index_out, ess_out, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    return launched(fn, rc);
 }
 
 // emei_sample_candidates_sigma: emei_sample_candidates' Gaussian mode with the sigma read per entry (there is no scalar to check)
@@ -899,7 +885,7 @@ extern "C" EMEI_API int emei_sample_candidates_sigma(emei_env* h, int32_t horizo
     EMEI_ON_DEVICE(h, fn);
     const int rc = launch_sample_candidates_sigma(CandidateSpecMap(candidate_spec(h, seed, nominal, 0.0), sigma_map), h->cfg.n_envs,
                                                   n_candidates, horizon, h->act_dim, actions_out, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    return launched(fn, rc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -927,15 +913,15 @@ extern "C" EMEI_API int emei_plan_cem(emei_env* h, int32_t horizon, int32_t n_ca
     if (!mean_out) return fail(EMEI_ERR_INVALID, "%s: null mean_out", fn);
     EMEI_ON_DEVICE(h, fn);
     if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    PlanLaunch p;
-    p.mode = PLAN_DRAWN_KEEP, p.start_rows = start_state, p.n_candidates = n_candidates, p.discount = discount;
+    LaunchCommon c = plan_call(PLAN_DRAWN_KEEP, start_state, horizon, n_candidates, discount);
+    PlanLaunch& p = c.plan;
     p.cand = candidate_spec(h, seed, nominal, sigma), p.sigma_map = sigma_map;
     p.partials = workspace, p.return_out = plan_returns(h, n_candidates, workspace);
-    int rc = launch_plan(h, p, horizon, nullptr, 0, nullptr, stream);
+    int rc = launch(h, c, stream);
     if (rc == EMEI_OK)
         rc = launch_plan_cem_finish(workspace, p.return_out, p.cand, sigma_map, h->cfg.n_envs, n_candidates, n_elites, horizon, h->act_dim, mean_out,
                                     std_out, best_return_out, best_index_out, elite_return_out, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    return launched(fn, rc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -959,21 +945,53 @@ static int check_mpc_handle(const char* fn, const emei_env* h) {
     return EMEI_OK;
 }
 
-// the body-kernel route of both controllers (the planner's own fields come in `m`): the kernel, then the done-mask launch
-static int launch_body_mpc(emei_env* h, int op, MpcLaunch m, int32_t n_steps, int32_t n_candidates, uint64_t seed, double sigma,
-                           double discount, void* workspace, float* obs_out, float* reward_out, uint8_t* done_out, uint32_t flags,
-                           void* stream) {
-    BodyLaunch L = body_base(h, stream);
-    L.op = op, L.mpc = m;
-    L.n_steps = n_steps;
-    L.plan.n_candidates = n_candidates, L.plan.discount = discount;
-    L.plan.cand = candidate_spec(h, seed, nullptr, sigma);  // the kernel keeps the nominal in LDS
-    L.plan.return_out = (double*)workspace;
-    L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
-    L.flags = flags;
-    L.selected = &h->last_kernel;
-    const int rc = body_launch(L);
-    return rc != EMEI_OK ? rc : launch_mpc_done_pack((const double*)workspace, n_candidates, h->cfg.n_envs, h->done_mask, (hipStream_t)stream);
+// The launch of a fused controller (emei_mpc_mppi / emei_mpc_cem / emei_mpc_policy; actions_out in action_dtype), then the done mask
+// packed by a small second launch: the kernel leaves env i's last done code in word 0 of its workspace row of n_candidates doubles.
+static int launch_controller(const char* fn, emei_env* h, const LaunchCommon& c, int action_dtype, void* stream) {
+    int rc = launch(h, c, stream, action_dtype);
+    if (rc == EMEI_OK) rc = launch_mpc_done_pack(c.plan.return_out, c.plan.n_candidates, h->cfg.n_envs, h->done_mask, (hipStream_t)stream);
+    return launched(fn, rc);
+}
+
+// What emei_mpc_mppi and emei_mpc_cem refuse alike about the nominal they keep in LDS ...
+static int check_nominal_update(const char* fn, float refill, float nominal_lo, float nominal_hi) {
+    if (!std::isfinite(refill)) return fail(EMEI_ERR_INVALID, "%s: refill=%g must be finite", fn, (double)refill);
+    if (!(nominal_lo <= nominal_hi))  // also refuses a NaN bound
+        return fail(EMEI_ERR_INVALID, "%s: nominal_lo=%g, nominal_hi=%g: need nominal_lo <= nominal_hi", fn, (double)nominal_lo,
+                    (double)nominal_hi);
+    return EMEI_OK;
+}
+static int check_mpc_horizon(const char* fn, int32_t horizon, const char* in_lds) {
+    if (horizon > EMEI_MPC_MAX_HORIZON)
+        return fail(EMEI_ERR_INVALID, "%s: horizon=%d exceeds EMEI_MPC_MAX_HORIZON=%d (%s in LDS)", fn, horizon, EMEI_MPC_MAX_HORIZON, in_lds);
+    return EMEI_OK;
+}
+// ... and everything from the handle on.  They always plan around a nominal, so sigma always counts (the nominal's own NULL check
+// comes a few refusals later).
+static int check_nominal_controller(const char* fn, emei_env* h, int32_t horizon, int32_t n_candidates, double sigma, int action_dtype,
+                                    uint32_t flags, const float* nominal, const void* workspace, const void* actions_out) {
+    if (int rc = check_candidates(fn, h, horizon, n_candidates, true, sigma)) return rc;
+    if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
+    if (int rc = check_flags(fn, flags)) return rc;
+    if (!nominal) return fail(EMEI_ERR_INVALID, "%s: null nominal", fn);
+    if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
+    if (!actions_out) return fail(EMEI_ERR_INVALID, "%s: null actions_out", fn);
+    EMEI_ON_DEVICE(h, fn);
+    if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    return check_mpc_handle(fn, h);
+}
+// the fields both give their kernel alike; `c` arrives with the op and the planner's own part of c.mpc
+static int launch_nominal_controller(const char* fn, emei_env* h, LaunchCommon& c, int32_t n_steps, int32_t horizon, int32_t n_candidates,
+                                     uint64_t seed, float* nominal, double sigma, double discount, float refill, float nominal_lo,
+                                     float nominal_hi, void* workspace, void* actions_out, int action_dtype, float* obs_out, float* reward_out,
+                                     uint8_t* done_out, double* plan_return_out, uint32_t flags, void* stream) {
+    c.n_steps = n_steps, c.flags = flags;
+    c.obs_out = obs_out, c.reward_out = reward_out, c.done_out = done_out;
+    c.plan.n_candidates = n_candidates, c.plan.discount = discount, c.plan.return_out = (double*)workspace;
+    c.plan.cand = candidate_spec(h, seed, nullptr, sigma);  // the kernel keeps the nominal (CEM: the mean and the sigma) in LDS
+    c.mpc.horizon = horizon, c.mpc.nominal = nominal, c.mpc.actions_out = actions_out, c.mpc.plan_return_out = plan_return_out;
+    c.mpc.refill = refill, c.mpc.nominal_lo = nominal_lo, c.mpc.nominal_hi = nominal_hi;
+    return launch_controller(fn, h, c, action_dtype, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -994,47 +1012,14 @@ extern "C" EMEI_API int emei_mpc_mppi(emei_env* h, int32_t n_steps, int32_t hori
     if (n_steps < 1) return fail(EMEI_ERR_INVALID, "%s: n_steps=%d < 1", fn, n_steps);
     if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
     if (int rc = check_temperature(fn, temperature)) return rc;
-    if (!std::isfinite(refill)) return fail(EMEI_ERR_INVALID, "%s: refill=%g must be finite", fn, (double)refill);
-    if (!(nominal_lo <= nominal_hi))  // also refuses a NaN bound
-        return fail(EMEI_ERR_INVALID, "%s: nominal_lo=%g, nominal_hi=%g: need nominal_lo <= nominal_hi", fn, (double)nominal_lo,
-                    (double)nominal_hi);
-    if (horizon > EMEI_MPC_MAX_HORIZON)
-        return fail(EMEI_ERR_INVALID, "%s: horizon=%d exceeds EMEI_MPC_MAX_HORIZON=%d (the nominal lives in LDS)", fn, horizon,
-                    EMEI_MPC_MAX_HORIZON);
-    // the call always plans around a nominal, so sigma always counts (the nominal's own NULL check comes a few refusals later)
-    if (int rc = check_candidates(fn, h, horizon, n_candidates, true, sigma)) return rc;
-    if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
-    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "%s: unknown flags 0x%x", fn, flags);
-    if (!nominal) return fail(EMEI_ERR_INVALID, "%s: null nominal", fn);
-    if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
-    if (!actions_out) return fail(EMEI_ERR_INVALID, "%s: null actions_out", fn);
-    EMEI_ON_DEVICE(h, fn);
-    if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    if (int rc = check_mpc_handle(fn, h)) return rc;
-    if (steps_as_body(h->cfg)) {  // continuous actions: actions_out is float32 (check_action_dtype)
-        MpcLaunch m;
-        m.horizon = horizon, m.nominal = nominal, m.actions_out = (float*)actions_out;
-        m.plan_return_out = plan_return_out, m.ess_out = ess_out, m.temperature = temperature;
-        m.refill = refill, m.nominal_lo = nominal_lo, m.nominal_hi = nominal_hi;
-        const int rc = launch_body_mpc(h, BODY_OP_MPC_MPPI, m, n_steps, n_candidates, seed, sigma, discount, workspace, obs_out, reward_out,
-                                       done_out, flags, stream);
-        return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
-    }
-    PendLaunch L = pend_base(h, stream);
-    L.op = PEND_OP_MPC;
-    L.n_steps = n_steps, L.horizon = horizon, L.temperature = temperature;
-    L.plan.n_candidates = n_candidates, L.plan.discount = discount;
-    L.plan.cand = candidate_spec(h, seed, nullptr, sigma);  // the kernel keeps the nominal in LDS
-    L.mpc_nominal = nominal, L.plan.return_out = (double*)workspace;
-    L.mpc_actions_out = actions_out, L.action_dtype = action_dtype;
-    L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
-    L.plan_return_out = plan_return_out, L.ess_out = ess_out;
-    L.refill = refill, L.nominal_lo = nominal_lo, L.nominal_hi = nominal_hi;
-    L.flags = flags;
-    L.selected = &h->last_kernel;
-    int rc = pend_launch(L);
-    if (rc == EMEI_OK) rc = launch_mpc_done_pack((const double*)workspace, n_candidates, h->cfg.n_envs, h->done_mask, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    if (int rc = check_nominal_update(fn, refill, nominal_lo, nominal_hi)) return rc;
+    if (int rc = check_mpc_horizon(fn, horizon, "the nominal lives")) return rc;
+    if (int rc = check_nominal_controller(fn, h, horizon, n_candidates, sigma, action_dtype, flags, nominal, workspace, actions_out)) return rc;
+    LaunchCommon c;
+    c.op = OP_MPC_MPPI;
+    c.mpc.ess_out = ess_out, c.mpc.temperature = temperature;
+    return launch_nominal_controller(fn, h, c, n_steps, horizon, n_candidates, seed, nominal, sigma, discount, refill, nominal_lo, nominal_hi,
+                                     workspace, actions_out, action_dtype, obs_out, reward_out, done_out, plan_return_out, flags, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1058,51 +1043,18 @@ extern "C" EMEI_API int emei_mpc_cem(emei_env* h, int32_t n_steps, int32_t horiz
         return fail(EMEI_ERR_INVALID, "%s: n_elites=%d is outside [1, n_candidates=%d]", fn, n_elites, n_candidates);
     if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
     if (iterations < 1) return fail(EMEI_ERR_INVALID, "%s: iterations=%d < 1", fn, iterations);
-    if (!std::isfinite(refill)) return fail(EMEI_ERR_INVALID, "%s: refill=%g must be finite", fn, (double)refill);
-    if (!(nominal_lo <= nominal_hi))  // also refuses a NaN bound
-        return fail(EMEI_ERR_INVALID, "%s: nominal_lo=%g, nominal_hi=%g: need nominal_lo <= nominal_hi", fn, (double)nominal_lo,
-                    (double)nominal_hi);
+    if (int rc = check_nominal_update(fn, refill, nominal_lo, nominal_hi)) return rc;
     if (!(std::isfinite(sigma_min) && sigma_min >= 0.0))
         return fail(EMEI_ERR_INVALID, "%s: sigma_min=%g must be finite and >= 0", fn, sigma_min);
-    if (horizon > EMEI_MPC_MAX_HORIZON)
-        return fail(EMEI_ERR_INVALID, "%s: horizon=%d exceeds EMEI_MPC_MAX_HORIZON=%d (the mean and the sigma live in LDS)", fn, horizon,
-                    EMEI_MPC_MAX_HORIZON);
-    // every control step starts from the scalar sigma, so it always counts
-    if (int rc = check_candidates(fn, h, horizon, n_candidates, true, sigma)) return rc;
-    if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
-    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "%s: unknown flags 0x%x", fn, flags);
-    if (!nominal) return fail(EMEI_ERR_INVALID, "%s: null nominal", fn);
-    if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
-    if (!actions_out) return fail(EMEI_ERR_INVALID, "%s: null actions_out", fn);
-    EMEI_ON_DEVICE(h, fn);
-    if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    if (int rc = check_mpc_handle(fn, h)) return rc;
-    if (steps_as_body(h->cfg)) {  // continuous actions: actions_out is float32 (check_action_dtype)
-        MpcLaunch m;
-        m.horizon = horizon, m.nominal = nominal, m.actions_out = (float*)actions_out;
-        m.plan_return_out = plan_return_out, m.elite_return_out = elite_return_out;
-        m.n_elites = n_elites, m.iterations = iterations, m.sigma_min = (float)sigma_min;
-        m.refill = refill, m.nominal_lo = nominal_lo, m.nominal_hi = nominal_hi;
-        const int rc = launch_body_mpc(h, BODY_OP_MPC_CEM, m, n_steps, n_candidates, seed, sigma, discount, workspace, obs_out, reward_out,
-                                       done_out, flags, stream);
-        return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
-    }
-    PendLaunch L = pend_base(h, stream);
-    L.op = PEND_OP_MPC_CEM;
-    L.n_steps = n_steps, L.horizon = horizon, L.n_elites = n_elites, L.iterations = iterations;
-    L.plan.n_candidates = n_candidates, L.plan.discount = discount;
-    L.plan.cand = candidate_spec(h, seed, nullptr, sigma);  // the kernel keeps the mean and the sigma in LDS
-    L.sigma_min = (float)sigma_min;
-    L.mpc_nominal = nominal, L.plan.return_out = (double*)workspace;
-    L.mpc_actions_out = actions_out, L.action_dtype = action_dtype;
-    L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
-    L.plan_return_out = plan_return_out, L.elite_return_out = elite_return_out;
-    L.refill = refill, L.nominal_lo = nominal_lo, L.nominal_hi = nominal_hi;
-    L.flags = flags;
-    L.selected = &h->last_kernel;
-    int rc = pend_launch(L);
-    if (rc == EMEI_OK) rc = launch_mpc_done_pack((const double*)workspace, n_candidates, h->cfg.n_envs, h->done_mask, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    if (int rc = check_mpc_horizon(fn, horizon, "the mean and the sigma live")) return rc;
+    // every control step starts from the scalar sigma
+    if (int rc = check_nominal_controller(fn, h, horizon, n_candidates, sigma, action_dtype, flags, nominal, workspace, actions_out)) return rc;
+    LaunchCommon c;
+    c.op = OP_MPC_CEM;
+    c.mpc.elite_return_out = elite_return_out;
+    c.mpc.n_elites = n_elites, c.mpc.iterations = iterations, c.mpc.sigma_min = (float)sigma_min;
+    return launch_nominal_controller(fn, h, c, n_steps, horizon, n_candidates, seed, nominal, sigma, discount, refill, nominal_lo, nominal_hi,
+                                     workspace, actions_out, action_dtype, obs_out, reward_out, done_out, plan_return_out, flags, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1124,6 +1076,14 @@ static int check_policy_weights(const char* fn, const char* arg, const emei_poli
     if (policy->hidden > 0 && (!policy->w1 || !policy->b1))
         return fail(EMEI_ERR_INVALID, "%s: null %s.%s with hidden=%d", fn, arg, !policy->w1 ? "w1" : "b1", policy->hidden);
     return EMEI_OK;
+}
+// the kernel-argument form of a checked struct emei_policy (the caller adds actions_out / action_dtype where its kernel reads them)
+static PolicyArgs policy_args(const emei_env* h, const emei_policy* policy) {
+    PolicyArgs pa{};
+    pa.w1 = policy->w1, pa.b1 = policy->b1, pa.w2 = policy->w2, pa.b2 = policy->b2;
+    pa.hidden = policy->hidden, pa.out_mode = policy->out_mode;
+    ctrl_range(h->cfg.env_id, pa.lo, pa.hi);
+    return pa;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1147,11 +1107,56 @@ static int check_policy_noise(const char* fn, const emei_policy_noise* nz) {
     }
     return EMEI_OK;
 }
+// ... and once the handle is known: the noise's kind against the env's
+static int check_noise_kind(const char* fn, const emei_env* h, const emei_policy_noise* noise) {
+    if ((h->act_dim > 0) == (noise->mode == EMEI_POLICY_NOISE_EPS_GREEDY))
+        return fail(EMEI_ERR_INVALID, "%s: noise.mode=%d: the Gaussian modes are for the continuous envs, EMEI_POLICY_NOISE_EPS_GREEDY for "
+                                      "the discrete ones", fn, noise->mode);
+    return EMEI_OK;
+}
+// the kernel-argument form of a checked struct emei_policy_noise; null: no noise, all zero
+static PolicyNoiseArgs policy_noise_args(const emei_policy_noise* noise) {
+    PolicyNoiseArgs na{};
+    if (!noise) return na;
+    na.seed = noise->seed, na.mode = noise->mode, na.sigma = (float)noise->sigma;
+    if (noise->mode == EMEI_POLICY_NOISE_GAUSS) na.std = noise->std;
+    if (noise->mode == EMEI_POLICY_NOISE_GAUSS_HEAD)
+        na.ws = noise->ws, na.bs = noise->bs, na.log_std_min = noise->log_std_min, na.log_std_max = noise->log_std_max;
+    return na;
+}
+
+// the dtype of the actions a policy call emits (`out`: the name of its argument)
+static int check_policy_action_dtype(const char* fn, const emei_env* h, int action_dtype, const char* out) {
+    if (action_dtype < EMEI_ACT_U8 || action_dtype > EMEI_ACT_F32 || (h->act_dim > 0) != (action_dtype == EMEI_ACT_F32))
+        return fail(EMEI_ERR_INVALID, "%s: action_dtype=%d: %s is uint8 / int32 / int64 for the discrete envs, float32 for the "
+                                      "continuous ones", fn, action_dtype, out);
+    return EMEI_OK;
+}
+
+// What the three policy rollouts refuse alike once their network's weights are checked (noise null: a deterministic launch) ...
+static int check_policy_rollout(const char* fn, emei_env* h, int action_dtype, uint32_t flags, const emei_policy_noise* noise) {
+    if (int rc = check_policy_action_dtype(fn, h, action_dtype, "actions_out")) return rc;
+    if (int rc = check_flags(fn, flags)) return rc;
+    if (noise)
+        if (int rc = check_noise_kind(fn, h, noise)) return rc;
+    EMEI_ON_DEVICE(h, fn);
+    if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    if (h->peers.count > 0)
+        return fail(EMEI_ERR_UNSUPPORTED, "%s: observation peers are set (emei_set_obs_peers), which this kernel does not serve", fn);
+    return EMEI_OK;
+}
+// ... and their launch; `c` arrives with the op and the network.  The kernel leaves the done mask itself.
+static int launch_policy_rollout(const char* fn, emei_env* h, LaunchCommon& c, int32_t n_steps, const emei_policy_noise* noise, int action_dtype,
+                                 float* obs_out, float* reward_out, uint8_t* done_out, uint32_t flags, void* stream) {
+    c.n_steps = n_steps, c.flags = flags;
+    c.obs_out = obs_out, c.reward_out = reward_out, c.done_out = done_out;
+    c.policy_noise = policy_noise_args(noise);
+    return launched(fn, launch(h, c, stream, action_dtype));
+}
 
 // emei_rollout_policy / emei_rollout_policy_noisy (`noisy`: the latter, with `noise` checked in its place of the header's order):
 // n_steps of "observe, evaluate the policy, emei_step" in one launch of the family's policy rollout kernel
-// (pendulum_kernels.h:pend_policy_rollout_kernel, body_kernels.h:body_policy_rollout_kernel, or their noisy twins); the kernel leaves
-// the done mask itself.
+// (pendulum_kernels.h:pend_policy_rollout_kernel, body_kernels.h:body_policy_rollout_kernel, or their noisy twins).
 static int rollout_policy(const char* fn, bool noisy, emei_env* h, int32_t n_steps, const emei_policy* policy, const emei_policy_noise* noise,
                           void* actions_out, int action_dtype, float* obs_out, float* reward_out, uint8_t* done_out, uint32_t flags,
                           void* stream) {
@@ -1161,50 +1166,12 @@ static int rollout_policy(const char* fn, bool noisy, emei_env* h, int32_t n_ste
         if (int rc = check_policy_noise(fn, noise)) return rc;
     if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
     if (int rc = check_policy_weights(fn, "policy", policy)) return rc;
-    if (action_dtype < EMEI_ACT_U8 || action_dtype > EMEI_ACT_F32 || (h->act_dim > 0) != (action_dtype == EMEI_ACT_F32))
-        return fail(EMEI_ERR_INVALID, "%s: action_dtype=%d: actions_out is uint8 / int32 / int64 for the discrete envs, float32 for the "
-                                      "continuous ones", fn, action_dtype);
-    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "%s: unknown flags 0x%x", fn, flags);
-    if (noisy && (h->act_dim > 0) == (noise->mode == EMEI_POLICY_NOISE_EPS_GREEDY))
-        return fail(EMEI_ERR_INVALID, "%s: noise.mode=%d: the Gaussian modes are for the continuous envs, EMEI_POLICY_NOISE_EPS_GREEDY for "
-                                      "the discrete ones", fn, noise->mode);
-    EMEI_ON_DEVICE(h, fn);
-    if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    if (h->peers.count > 0)
-        return fail(EMEI_ERR_UNSUPPORTED, "%s: observation peers are set (emei_set_obs_peers), which this kernel does not serve", fn);
-    PolicyArgs pa{};
-    pa.w1 = policy->w1, pa.b1 = policy->b1, pa.w2 = policy->w2, pa.b2 = policy->b2;
-    pa.actions_out = actions_out, pa.hidden = policy->hidden, pa.out_mode = policy->out_mode, pa.action_dtype = action_dtype;
-    ctrl_range(h->cfg.env_id, pa.lo, pa.hi);
-    PolicyNoiseArgs na{};
-    if (noisy) {
-        na.seed = noise->seed, na.mode = noise->mode, na.sigma = (float)noise->sigma;
-        if (noise->mode == EMEI_POLICY_NOISE_GAUSS) na.std = noise->std;
-        if (noise->mode == EMEI_POLICY_NOISE_GAUSS_HEAD)
-            na.ws = noise->ws, na.bs = noise->bs, na.log_std_min = noise->log_std_min, na.log_std_max = noise->log_std_max;
-    }
-    int rc;
-    if (!steps_as_body(h->cfg)) {
-        PendLaunch L = pend_base(h, stream);
-        L.op = noisy ? PEND_OP_POLICY_NOISY : PEND_OP_POLICY;
-        L.action_dtype = action_dtype;
-        L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
-        L.n_steps = n_steps;
-        L.flags = flags;
-        L.policy = pa, L.policy_noise = na;
-        L.selected = &h->last_kernel;
-        rc = pend_launch(L);
-    } else {
-        BodyLaunch L = body_base(h, stream);
-        L.op = noisy ? BODY_OP_POLICY_NOISY : BODY_OP_POLICY;
-        L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
-        L.n_steps = n_steps;
-        L.flags = flags;
-        L.policy = pa, L.policy_noise = na;
-        L.selected = &h->last_kernel;
-        rc = body_launch(L);
-    }
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    if (int rc = check_policy_rollout(fn, h, action_dtype, flags, noisy ? noise : nullptr)) return rc;
+    LaunchCommon c;
+    c.op = noisy ? OP_POLICY_NOISY : OP_POLICY;
+    c.policy = policy_args(h, policy);
+    c.policy.actions_out = actions_out, c.policy.action_dtype = action_dtype;
+    return launch_policy_rollout(fn, h, c, n_steps, noisy ? noise : nullptr, action_dtype, obs_out, reward_out, done_out, flags, stream);
 }
 extern "C" EMEI_API int emei_rollout_policy(emei_env* h, int32_t n_steps, const emei_policy* policy, void* actions_out, int action_dtype,
                                             float* obs_out, float* reward_out, uint8_t* done_out, uint32_t flags, void* stream) {
@@ -1222,6 +1189,27 @@ extern "C" EMEI_API int emei_rollout_policy_noisy(emei_env* h, int32_t n_steps, 
 // emei_evaluate_policies: emei_evaluate_sequences' query with the candidates replaced by a population of feedback policies, one
 // launch of the family's policy evaluation kernel (pendulum_kernels.h:pend_policy_eval_kernel, body_kernels.h:body_policy_eval_kernel)
 // through the plan-launch descriptor; nothing of the handle is written (h->last_kernel included).
+// What it and its deep twin refuse alike once the weights are checked: one lane per (policy, env) pair with 32-bit indices, one grid
+// dimension of ceil(n_envs / block) blocks per policy ...
+static int check_population(const char* fn, emei_env* h, int32_t n_policies, int block, const double* start_state, const double* return_out) {
+    if (!return_out) return fail(EMEI_ERR_INVALID, "%s: null return_out", fn);
+    const int64_t np = h->cfg.n_envs * (int64_t)n_policies;
+    if (np > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs * n_policies = %lld exceeds 2^31 - 1", fn, (long long)np);
+    const int64_t blocks = (h->cfg.n_envs + block - 1) / block * (int64_t)n_policies;
+    if (blocks > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_policies=%d needs %lld blocks, more than 2^31 - 1", fn, n_policies, (long long)blocks);
+    EMEI_ON_DEVICE(h, fn);
+    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    return EMEI_OK;
+}
+// ... and their launch; `c` arrives with the op and the stacked networks
+static int launch_population(const char* fn, emei_env* h, LaunchCommon& c, int32_t horizon, int32_t n_policies, double discount,
+                             const double* start_state, double* return_out, int32_t* length_out, float* final_obs_out, void* stream) {
+    c.plan.mode = PLAN_GIVEN, c.plan.start_rows = start_state, c.plan.n_candidates = n_policies, c.plan.discount = discount;
+    c.plan.return_out = return_out, c.plan.length_out = length_out;
+    c.n_steps = horizon, c.obs_out = final_obs_out;
+    return launched(fn, launch(h, c, stream));
+}
+
 extern "C" EMEI_API int emei_evaluate_policies(emei_env* h, int32_t horizon, int32_t n_policies, const emei_policy* stacked, double discount,
                                                const double* start_state, double* return_out, int32_t* length_out, float* final_obs_out,
                                                void* stream) {
@@ -1230,34 +1218,10 @@ extern "C" EMEI_API int emei_evaluate_policies(emei_env* h, int32_t horizon, int
     if (int rc = check_policy_struct(fn, "stacked", stacked)) return rc;
     if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
     if (int rc = check_policy_weights(fn, "stacked", stacked)) return rc;
-    if (!return_out) return fail(EMEI_ERR_INVALID, "%s: null return_out", fn);
-    // one lane per (policy, env) pair with 32-bit indices, one grid dimension of ceil(n_envs / 256) blocks per policy
-    const int64_t np = h->cfg.n_envs * (int64_t)n_policies;
-    if (np > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs * n_policies = %lld exceeds 2^31 - 1", fn, (long long)np);
-    const int64_t blocks = (h->cfg.n_envs + kBlock - 1) / kBlock * (int64_t)n_policies;
-    if (blocks > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_policies=%d needs %lld blocks, more than 2^31 - 1", fn, n_policies, (long long)blocks);
-    EMEI_ON_DEVICE(h, fn);
-    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    PolicyArgs pa{};
-    pa.w1 = stacked->w1, pa.b1 = stacked->b1, pa.w2 = stacked->w2, pa.b2 = stacked->b2;
-    pa.hidden = stacked->hidden, pa.out_mode = stacked->out_mode;
-    ctrl_range(h->cfg.env_id, pa.lo, pa.hi);
-    PlanLaunch p;
-    p.mode = PLAN_GIVEN, p.start_rows = start_state, p.n_candidates = n_policies, p.discount = discount;
-    p.return_out = return_out, p.length_out = length_out;
-    int rc;
-    if (!steps_as_body(h->cfg)) {
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_POLICY_EVAL, L.plan = p, L.policy = pa;
-        L.n_steps = horizon, L.obs_out = final_obs_out;
-        rc = pend_launch(L);
-    } else {
-        BodyLaunch L = body_base(h, stream);
-        L.op = BODY_OP_POLICY_EVAL, L.plan = p, L.policy = pa;
-        L.n_steps = horizon, L.obs_out = final_obs_out;
-        rc = body_launch(L);
-    }
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    if (int rc = check_population(fn, h, n_policies, kBlock, start_state, return_out)) return rc;
+    LaunchCommon c;
+    c.op = OP_POLICY_EVAL, c.policy = policy_args(h, stacked);
+    return launch_population(fn, h, c, horizon, n_policies, discount, start_state, return_out, length_out, final_obs_out, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1270,6 +1234,46 @@ extern "C" EMEI_API int emei_evaluate_policies(emei_env* h, int32_t horizon, int
 extern "C" EMEI_API int64_t emei_plan_policy_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
     const int64_t nk = check_plan_shape("emei_plan_policy_workspace_bytes", n_envs, n_candidates);
     return nk < 0 ? nk : plan_partials_bytes(n_envs, nk) + (int64_t)(sizeof(double) + kPlanPolicyMaxAct * sizeof(float)) * nk;
+}
+struct PlanPolicyWorkspace {
+    void* partials;
+    double* returns;
+    float* first_actions;
+};
+static PlanPolicyWorkspace plan_policy_workspace(const emei_env* h, int32_t n_candidates, void* workspace) {
+    double* returns = plan_returns(h, n_candidates, workspace);
+    return {workspace, returns, (float*)(returns + h->cfg.n_envs * (int64_t)n_candidates)};
+}
+
+// What emei_plan_policy and its deep twin refuse alike once the weights are checked ...
+static int check_plan_policy(const char* fn, emei_env* h, int32_t n_candidates, int action_dtype, const void* workspace,
+                             const void* best_action_out, const emei_policy_noise* noise, const double* start_state) {
+    if (int rc = check_plan_lanes(fn, h, n_candidates)) return rc;
+    if (int rc = check_policy_action_dtype(fn, h, action_dtype, "best_action_out")) return rc;
+    if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
+    if (!best_action_out) return fail(EMEI_ERR_INVALID, "%s: null best_action_out", fn);
+    if (int rc = check_noise_kind(fn, h, noise)) return rc;
+    EMEI_ON_DEVICE(h, fn);
+    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
+    return EMEI_OK;
+}
+// ... and their two launches; `c` arrives with the op and the networks
+static int launch_plan_policy(const char* fn, emei_env* h, LaunchCommon& c, int32_t horizon, int32_t n_candidates,
+                              const emei_policy_noise* noise, double discount, double temperature, const double* start_state, void* workspace,
+                              void* best_action_out, int action_dtype, float* mean_action_out, double* best_return_out,
+                              int32_t* best_index_out, int32_t* best_length_out, double* return_out, double* ess_out, void* stream) {
+    const PlanPolicyWorkspace ws = plan_policy_workspace(h, n_candidates, workspace);
+    PlanLaunch& p = c.plan;
+    p.mode = PLAN_DRAWN_KEEP, p.start_rows = start_state, p.n_candidates = n_candidates, p.discount = discount;
+    p.partials = ws.partials, p.return_out = return_out ? return_out : ws.returns, p.first_actions = ws.first_actions;
+    c.policy_noise = policy_noise_args(noise);
+    c.n_steps = horizon;
+    int rc = launch(h, c, stream);
+    if (rc == EMEI_OK)
+        rc = launch_plan_policy_finish(ws.partials, p.return_out, p.first_actions, h->cfg.n_envs, n_candidates, h->act_dim, temperature,
+                                       best_action_out, action_dtype, mean_action_out, best_return_out, best_index_out, best_length_out,
+                                       ess_out, (hipStream_t)stream);
+    return launched(fn, rc);
 }
 
 extern "C" EMEI_API int emei_plan_policy(emei_env* h, int32_t horizon, int32_t n_candidates, const emei_policy* policy,
@@ -1285,49 +1289,13 @@ extern "C" EMEI_API int emei_plan_policy(emei_env* h, int32_t horizon, int32_t n
     if (int rc = check_policy_noise(fn, noise)) return rc;
     if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
     if (int rc = check_policy_weights(fn, "policy", policy)) return rc;
-    if (int rc = check_plan_lanes(fn, h, n_candidates)) return rc;
-    if (action_dtype < EMEI_ACT_U8 || action_dtype > EMEI_ACT_F32 || (h->act_dim > 0) != (action_dtype == EMEI_ACT_F32))
-        return fail(EMEI_ERR_INVALID, "%s: action_dtype=%d: best_action_out is uint8 / int32 / int64 for the discrete envs, float32 for the "
-                                      "continuous ones", fn, action_dtype);
-    if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
-    if (!best_action_out) return fail(EMEI_ERR_INVALID, "%s: null best_action_out", fn);
-    if ((h->act_dim > 0) == (noise->mode == EMEI_POLICY_NOISE_EPS_GREEDY))
-        return fail(EMEI_ERR_INVALID, "%s: noise.mode=%d: the Gaussian modes are for the continuous envs, EMEI_POLICY_NOISE_EPS_GREEDY for "
-                                      "the discrete ones", fn, noise->mode);
-    EMEI_ON_DEVICE(h, fn);
-    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    PolicyArgs pa{};
-    pa.w1 = policy->w1, pa.b1 = policy->b1, pa.w2 = policy->w2, pa.b2 = policy->b2;
-    pa.hidden = policy->hidden, pa.out_mode = policy->out_mode, pa.action_dtype = action_dtype;
-    ctrl_range(h->cfg.env_id, pa.lo, pa.hi);
-    PolicyNoiseArgs na{};
-    na.seed = noise->seed, na.mode = noise->mode, na.sigma = (float)noise->sigma;
-    if (noise->mode == EMEI_POLICY_NOISE_GAUSS) na.std = noise->std;
-    if (noise->mode == EMEI_POLICY_NOISE_GAUSS_HEAD)
-        na.ws = noise->ws, na.bs = noise->bs, na.log_std_min = noise->log_std_min, na.log_std_max = noise->log_std_max;
-    const int64_t nk = h->cfg.n_envs * (int64_t)n_candidates;
-    PlanLaunch p;
-    p.mode = PLAN_DRAWN_KEEP, p.start_rows = start_state, p.n_candidates = n_candidates, p.discount = discount;
-    p.partials = workspace;
-    p.return_out = return_out ? return_out : plan_returns(h, n_candidates, workspace);
-    p.first_actions = (float*)(plan_returns(h, n_candidates, workspace) + nk);
-    int rc;
-    if (!steps_as_body(h->cfg)) {
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_POLICY_PLAN, L.plan = p, L.policy = pa, L.policy_noise = na;
-        L.n_steps = horizon;
-        rc = pend_launch(L);
-    } else {
-        BodyLaunch L = body_base(h, stream);
-        L.op = BODY_OP_POLICY_PLAN, L.plan = p, L.policy = pa, L.policy_noise = na;
-        L.n_steps = horizon;
-        rc = body_launch(L);
-    }
-    if (rc == EMEI_OK)
-        rc = launch_plan_policy_finish(workspace, p.return_out, p.first_actions, h->cfg.n_envs, n_candidates, h->act_dim, temperature,
-                                       best_action_out, action_dtype, mean_action_out, best_return_out, best_index_out, best_length_out,
-                                       ess_out, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    if (int rc = check_plan_policy(fn, h, n_candidates, action_dtype, workspace, best_action_out, noise, start_state)) return rc;
+    LaunchCommon c;
+    c.op = OP_POLICY_PLAN;
+    c.policy = policy_args(h, policy);
+    c.policy.action_dtype = action_dtype;
+    return launch_plan_policy(fn, h, c, horizon, n_candidates, noise, discount, temperature, start_state, workspace, best_action_out,
+                              action_dtype, mean_action_out, best_return_out, best_index_out, best_length_out, return_out, ess_out, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1350,71 +1318,40 @@ extern "C" EMEI_API int emei_mpc_policy(emei_env* h, int32_t n_steps, int32_t ho
     if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
     if (act_mode != EMEI_MPC_POLICY_ACT_BEST && act_mode != EMEI_MPC_POLICY_ACT_MEAN)
         return fail(EMEI_ERR_INVALID, "%s: unknown act_mode=%d", fn, act_mode);
-    if (act_mode == EMEI_MPC_POLICY_ACT_MEAN || ess_out)
+    const bool weighted = act_mode == EMEI_MPC_POLICY_ACT_MEAN || ess_out;
+    if (weighted)
         if (int rc = check_temperature(fn, temperature)) return rc;
     if (int rc = check_policy_struct(fn, "policy", policy)) return rc;
     if (int rc = check_policy_noise(fn, noise)) return rc;
     if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
     if (int rc = check_policy_weights(fn, "policy", policy)) return rc;
     if (int rc = check_plan_lanes(fn, h, n_candidates)) return rc;
-    if (action_dtype < EMEI_ACT_U8 || action_dtype > EMEI_ACT_F32 || (h->act_dim > 0) != (action_dtype == EMEI_ACT_F32))
-        return fail(EMEI_ERR_INVALID, "%s: action_dtype=%d: actions_out is uint8 / int32 / int64 for the discrete envs, float32 for the "
-                                      "continuous ones", fn, action_dtype);
-    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "%s: unknown flags 0x%x", fn, flags);
+    if (int rc = check_policy_action_dtype(fn, h, action_dtype, "actions_out")) return rc;
+    if (int rc = check_flags(fn, flags)) return rc;
     if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
     if (!actions_out) return fail(EMEI_ERR_INVALID, "%s: null actions_out", fn);
-    if ((h->act_dim > 0) == (noise->mode == EMEI_POLICY_NOISE_EPS_GREEDY))
-        return fail(EMEI_ERR_INVALID, "%s: noise.mode=%d: the Gaussian modes are for the continuous envs, EMEI_POLICY_NOISE_EPS_GREEDY for "
-                                      "the discrete ones", fn, noise->mode);
+    if (int rc = check_noise_kind(fn, h, noise)) return rc;
     EMEI_ON_DEVICE(h, fn);
     if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
     if (int rc = check_mpc_handle(fn, h)) return rc;
-    PolicyArgs pa{};
-    pa.w1 = policy->w1, pa.b1 = policy->b1, pa.w2 = policy->w2, pa.b2 = policy->b2;
-    pa.hidden = policy->hidden, pa.out_mode = policy->out_mode, pa.action_dtype = action_dtype;
-    ctrl_range(h->cfg.env_id, pa.lo, pa.hi);
-    PolicyNoiseArgs na{};
-    na.seed = noise->seed, na.mode = noise->mode, na.sigma = (float)noise->sigma;
-    if (noise->mode == EMEI_POLICY_NOISE_GAUSS) na.std = noise->std;
-    if (noise->mode == EMEI_POLICY_NOISE_GAUSS_HEAD)
-        na.ws = noise->ws, na.bs = noise->bs, na.log_std_min = noise->log_std_min, na.log_std_max = noise->log_std_max;
-    const bool weighted = act_mode == EMEI_MPC_POLICY_ACT_MEAN || ess_out;
-    int rc;
-    if (steps_as_body(h->cfg)) {  // continuous actions: actions_out is float32
-        BodyLaunch L = body_base(h, stream);
-        L.op = BODY_OP_MPC_POLICY;
-        L.mpc.horizon = horizon, L.mpc.actions_out = (float*)actions_out;
-        L.mpc.plan_return_out = plan_return_out, L.mpc.plan_index_out = plan_index_out, L.mpc.ess_out = ess_out;
-        L.mpc.temperature = weighted ? temperature : 1.0, L.mpc.act_mode = act_mode, L.mpc.seed_stride = seed_stride;
-        L.n_steps = n_steps;
-        L.plan.n_candidates = n_candidates, L.plan.discount = discount, L.plan.return_out = (double*)workspace;
-        L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
-        L.flags = flags;
-        L.policy = pa, L.policy_noise = na;
-        L.selected = &h->last_kernel;
-        rc = body_launch(L);
-    } else {
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_MPC_POLICY;
-        L.n_steps = n_steps, L.horizon = horizon, L.temperature = weighted ? temperature : 1.0;
-        L.act_mode = act_mode, L.seed_stride = seed_stride;
-        L.plan.n_candidates = n_candidates, L.plan.discount = discount, L.plan.return_out = (double*)workspace;
-        L.mpc_actions_out = actions_out, L.action_dtype = action_dtype;
-        L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
-        L.plan_return_out = plan_return_out, L.plan_index_out = plan_index_out, L.ess_out = ess_out;
-        L.flags = flags;
-        L.policy = pa, L.policy_noise = na;
-        L.selected = &h->last_kernel;
-        rc = pend_launch(L);
-    }
-    if (rc == EMEI_OK) rc = launch_mpc_done_pack((const double*)workspace, n_candidates, h->cfg.n_envs, h->done_mask, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    LaunchCommon c;
+    c.op = OP_MPC_POLICY;
+    c.n_steps = n_steps, c.flags = flags;
+    c.obs_out = obs_out, c.reward_out = reward_out, c.done_out = done_out;
+    c.plan.n_candidates = n_candidates, c.plan.discount = discount, c.plan.return_out = (double*)workspace;
+    c.mpc.horizon = horizon, c.mpc.actions_out = actions_out;
+    c.mpc.plan_return_out = plan_return_out, c.mpc.plan_index_out = plan_index_out, c.mpc.ess_out = ess_out;
+    c.mpc.temperature = weighted ? temperature : 1.0, c.mpc.act_mode = act_mode, c.mpc.seed_stride = seed_stride;
+    c.policy = policy_args(h, policy);
+    c.policy.action_dtype = action_dtype;
+    c.policy_noise = policy_noise_args(noise);
+    return launch_controller(fn, h, c, action_dtype, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
-// emei_rollout_policy_deep / emei_evaluate_policies_deep: the policy calls above for struct emei_policy_deep (two hidden layers), on
-// kernels of their own (pend_policy_rollout_deep_kernel / body_policy_rollout_deep_kernel, pend_policy_eval_deep_kernel /
-// body_policy_eval_deep_kernel).  The refusals mirror check_policy_struct / check_policy_weights.
+// emei_rollout_policy_deep / emei_evaluate_policies_deep / emei_plan_policy_deep: the policy calls above for struct emei_policy_deep
+// (two hidden layers), on kernels of their own (pend_policy_*_deep_kernel / body_policy_*_deep_kernel).  The refusals mirror
+// check_policy_struct / check_policy_weights.
 // with_out_mode false: the terminal value network of emei_plan_policy_deep, whose out_mode is ignored
 static int check_policy_deep_struct(const char* fn, const char* arg, const emei_policy_deep* policy, bool with_out_mode = true) {
     if (!policy) return fail(EMEI_ERR_INVALID, "%s: null %s", fn, arg);
@@ -1439,12 +1376,21 @@ static int check_policy_deep_weights(const char* fn, const char* arg, const emei
         if (!ptr[k]) return fail(EMEI_ERR_INVALID, "%s: null %s.%s", fn, arg, name[k]);
     return EMEI_OK;
 }
+// the kernel-argument form of a checked struct emei_policy_deep (noisy = 0; the caller adds what its kernel reads beyond the network)
 static PolicyDeepArgs policy_deep_args(const emei_env* h, const emei_policy_deep* policy) {
     PolicyDeepArgs pa{};
     pa.w1 = policy->w1, pa.b1 = policy->b1, pa.w2 = policy->w2, pa.b2 = policy->b2, pa.w3 = policy->w3, pa.b3 = policy->b3;
     pa.hidden1 = policy->hidden1, pa.hidden2 = policy->hidden2, pa.out_mode = policy->out_mode;
     ctrl_range(h->cfg.env_id, pa.lo, pa.hi);
     return pa;
+}
+// ... and of the terminal value network: the weights and the widths alone; null: w1 null, no terminal value
+static PolicyDeepArgs policy_value_args(const emei_policy_deep* value) {
+    PolicyDeepArgs va{};
+    if (!value) return va;
+    va.w1 = value->w1, va.b1 = value->b1, va.w2 = value->w2, va.b2 = value->b2, va.w3 = value->w3, va.b3 = value->b3;
+    va.hidden1 = value->hidden1, va.hidden2 = value->hidden2;
+    return va;
 }
 
 extern "C" EMEI_API int emei_rollout_policy_deep(emei_env* h, int32_t n_steps, const emei_policy_deep* policy, const emei_policy_noise* noise,
@@ -1457,48 +1403,12 @@ extern "C" EMEI_API int emei_rollout_policy_deep(emei_env* h, int32_t n_steps, c
         if (int rc = check_policy_noise(fn, noise)) return rc;
     if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
     if (int rc = check_policy_deep_weights(fn, "policy", policy)) return rc;
-    if (action_dtype < EMEI_ACT_U8 || action_dtype > EMEI_ACT_F32 || (h->act_dim > 0) != (action_dtype == EMEI_ACT_F32))
-        return fail(EMEI_ERR_INVALID, "%s: action_dtype=%d: actions_out is uint8 / int32 / int64 for the discrete envs, float32 for the "
-                                      "continuous ones", fn, action_dtype);
-    if (flags & ~EMEI_FLAG_AUTO_RESET) return fail(EMEI_ERR_INVALID, "%s: unknown flags 0x%x", fn, flags);
-    if (noise && (h->act_dim > 0) == (noise->mode == EMEI_POLICY_NOISE_EPS_GREEDY))
-        return fail(EMEI_ERR_INVALID, "%s: noise.mode=%d: the Gaussian modes are for the continuous envs, EMEI_POLICY_NOISE_EPS_GREEDY for "
-                                      "the discrete ones", fn, noise->mode);
-    EMEI_ON_DEVICE(h, fn);
-    if (!h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    if (h->peers.count > 0)
-        return fail(EMEI_ERR_UNSUPPORTED, "%s: observation peers are set (emei_set_obs_peers), which this kernel does not serve", fn);
-    PolicyDeepArgs pa = policy_deep_args(h, policy);
-    pa.actions_out = actions_out, pa.action_dtype = action_dtype, pa.noisy = noise ? 1 : 0;
-    PolicyNoiseArgs na{};
-    if (noise) {
-        na.seed = noise->seed, na.mode = noise->mode, na.sigma = (float)noise->sigma;
-        if (noise->mode == EMEI_POLICY_NOISE_GAUSS) na.std = noise->std;
-        if (noise->mode == EMEI_POLICY_NOISE_GAUSS_HEAD)
-            na.ws = noise->ws, na.bs = noise->bs, na.log_std_min = noise->log_std_min, na.log_std_max = noise->log_std_max;
-    }
-    int rc;
-    if (!steps_as_body(h->cfg)) {
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_POLICY_DEEP;
-        L.action_dtype = action_dtype;
-        L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
-        L.n_steps = n_steps;
-        L.flags = flags;
-        L.policy_deep = pa, L.policy_noise = na;
-        L.selected = &h->last_kernel;
-        rc = pend_launch(L);
-    } else {
-        BodyLaunch L = body_base(h, stream);
-        L.op = BODY_OP_POLICY_DEEP;
-        L.obs_out = obs_out, L.reward_out = reward_out, L.done_out = done_out;
-        L.n_steps = n_steps;
-        L.flags = flags;
-        L.policy_deep = pa, L.policy_noise = na;
-        L.selected = &h->last_kernel;
-        rc = body_launch(L);
-    }
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    if (int rc = check_policy_rollout(fn, h, action_dtype, flags, noise)) return rc;
+    LaunchCommon c;
+    c.op = OP_POLICY_DEEP;
+    c.policy_deep = policy_deep_args(h, policy);
+    c.policy_deep.actions_out = actions_out, c.policy_deep.action_dtype = action_dtype, c.policy_deep.noisy = noise ? 1 : 0;
+    return launch_policy_rollout(fn, h, c, n_steps, noise, action_dtype, obs_out, reward_out, done_out, flags, stream);
 }
 
 extern "C" EMEI_API int emei_evaluate_policies_deep(emei_env* h, int32_t horizon, int32_t n_policies, const emei_policy_deep* stacked,
@@ -1509,31 +1419,10 @@ extern "C" EMEI_API int emei_evaluate_policies_deep(emei_env* h, int32_t horizon
     if (int rc = check_policy_deep_struct(fn, "stacked", stacked)) return rc;
     if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
     if (int rc = check_policy_deep_weights(fn, "stacked", stacked)) return rc;
-    if (!return_out) return fail(EMEI_ERR_INVALID, "%s: null return_out", fn);
-    // one lane per (policy, env) pair with 32-bit indices, one grid dimension of ceil(n_envs / 64) one-wave blocks per policy
-    const int64_t np = h->cfg.n_envs * (int64_t)n_policies;
-    if (np > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_envs * n_policies = %lld exceeds 2^31 - 1", fn, (long long)np);
-    const int64_t blocks = (h->cfg.n_envs + kWave - 1) / kWave * (int64_t)n_policies;
-    if (blocks > INT32_MAX) return fail(EMEI_ERR_INVALID, "%s: n_policies=%d needs %lld blocks, more than 2^31 - 1", fn, n_policies, (long long)blocks);
-    EMEI_ON_DEVICE(h, fn);
-    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    const PolicyDeepArgs pa = policy_deep_args(h, stacked);  // noisy = 0: the population is scored without exploration noise
-    PlanLaunch p;
-    p.mode = PLAN_GIVEN, p.start_rows = start_state, p.n_candidates = n_policies, p.discount = discount;
-    p.return_out = return_out, p.length_out = length_out;
-    int rc;
-    if (!steps_as_body(h->cfg)) {
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_POLICY_EVAL_DEEP, L.plan = p, L.policy_deep = pa;
-        L.n_steps = horizon, L.obs_out = final_obs_out;
-        rc = pend_launch(L);
-    } else {
-        BodyLaunch L = body_base(h, stream);
-        L.op = BODY_OP_POLICY_EVAL_DEEP, L.plan = p, L.policy_deep = pa;
-        L.n_steps = horizon, L.obs_out = final_obs_out;
-        rc = body_launch(L);
-    }
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    if (int rc = check_population(fn, h, n_policies, kWave, start_state, return_out)) return rc;  // one-wave blocks
+    LaunchCommon c;
+    c.op = OP_POLICY_EVAL_DEEP, c.policy_deep = policy_deep_args(h, stacked);  // noisy = 0: scored without exploration noise
+    return launch_population(fn, h, c, horizon, n_policies, discount, start_state, return_out, length_out, final_obs_out, stream);
 }
 
 // emei_plan_policy_deep: emei_plan_policy for struct emei_policy_deep, with an optional terminal value network.  First launch: the
@@ -1557,52 +1446,14 @@ extern "C" EMEI_API int emei_plan_policy_deep(emei_env* h, int32_t horizon, int3
     if (int rc = check_policy_deep_weights(fn, "policy", policy)) return rc;
     if (value)
         if (int rc = check_policy_deep_weights(fn, "value", value)) return rc;
-    if (int rc = check_plan_lanes(fn, h, n_candidates)) return rc;
-    if (action_dtype < EMEI_ACT_U8 || action_dtype > EMEI_ACT_F32 || (h->act_dim > 0) != (action_dtype == EMEI_ACT_F32))
-        return fail(EMEI_ERR_INVALID, "%s: action_dtype=%d: best_action_out is uint8 / int32 / int64 for the discrete envs, float32 for the "
-                                      "continuous ones", fn, action_dtype);
-    if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
-    if (!best_action_out) return fail(EMEI_ERR_INVALID, "%s: null best_action_out", fn);
-    if ((h->act_dim > 0) == (noise->mode == EMEI_POLICY_NOISE_EPS_GREEDY))
-        return fail(EMEI_ERR_INVALID, "%s: noise.mode=%d: the Gaussian modes are for the continuous envs, EMEI_POLICY_NOISE_EPS_GREEDY for "
-                                      "the discrete ones", fn, noise->mode);
-    EMEI_ON_DEVICE(h, fn);
-    if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    PolicyDeepArgs pa = policy_deep_args(h, policy);
-    pa.action_dtype = action_dtype, pa.noisy = 1;
-    PolicyDeepArgs va{};  // w1 null: no terminal value
-    if (value) {
-        va.w1 = value->w1, va.b1 = value->b1, va.w2 = value->w2, va.b2 = value->b2, va.w3 = value->w3, va.b3 = value->b3;
-        va.hidden1 = value->hidden1, va.hidden2 = value->hidden2;
-    }
-    PolicyNoiseArgs na{};
-    na.seed = noise->seed, na.mode = noise->mode, na.sigma = (float)noise->sigma;
-    if (noise->mode == EMEI_POLICY_NOISE_GAUSS) na.std = noise->std;
-    if (noise->mode == EMEI_POLICY_NOISE_GAUSS_HEAD)
-        na.ws = noise->ws, na.bs = noise->bs, na.log_std_min = noise->log_std_min, na.log_std_max = noise->log_std_max;
-    const int64_t nk = h->cfg.n_envs * (int64_t)n_candidates;
-    PlanLaunch p;
-    p.mode = PLAN_DRAWN_KEEP, p.start_rows = start_state, p.n_candidates = n_candidates, p.discount = discount;
-    p.partials = workspace;
-    p.return_out = return_out ? return_out : plan_returns(h, n_candidates, workspace);
-    p.first_actions = (float*)(plan_returns(h, n_candidates, workspace) + nk);
-    int rc;
-    if (!steps_as_body(h->cfg)) {
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_POLICY_PLAN_DEEP, L.plan = p, L.policy_deep = pa, L.policy_noise = na, L.policy_value = va;
-        L.n_steps = horizon;
-        rc = pend_launch(L);
-    } else {
-        BodyLaunch L = body_base(h, stream);
-        L.op = BODY_OP_POLICY_PLAN_DEEP, L.plan = p, L.policy_deep = pa, L.policy_noise = na, L.policy_value = va;
-        L.n_steps = horizon;
-        rc = body_launch(L);
-    }
-    if (rc == EMEI_OK)
-        rc = launch_plan_policy_finish(workspace, p.return_out, p.first_actions, h->cfg.n_envs, n_candidates, h->act_dim, temperature,
-                                       best_action_out, action_dtype, mean_action_out, best_return_out, best_index_out, best_length_out,
-                                       ess_out, (hipStream_t)stream);
-    return rc == EMEI_OK ? rc : fail(rc, "%s: launch failed (%s)", fn, hipGetErrorString(hipGetLastError()));
+    if (int rc = check_plan_policy(fn, h, n_candidates, action_dtype, workspace, best_action_out, noise, start_state)) return rc;
+    LaunchCommon c;
+    c.op = OP_POLICY_PLAN_DEEP;
+    c.policy_deep = policy_deep_args(h, policy);
+    c.policy_deep.action_dtype = action_dtype, c.policy_deep.noisy = 1;
+    c.policy_value = policy_value_args(value);
+    return launch_plan_policy(fn, h, c, horizon, n_candidates, noise, discount, temperature, start_state, workspace, best_action_out,
+                              action_dtype, mean_action_out, best_return_out, best_index_out, best_length_out, return_out, ess_out, stream);
 }
 
 extern "C" EMEI_API int emei_compact_done(emei_env* h, int32_t* idx_out, int32_t* count_out, void* stream) {
@@ -1627,24 +1478,13 @@ extern "C" EMEI_API int emei_episode_init_obs(emei_env* h, int64_t count, const 
     if (!h || !env_index || !episode || !obs_out) return fail(EMEI_ERR_INVALID, "emei_episode_init_obs: null argument");
     EMEI_ON_DEVICE(h, "emei_episode_init_obs");
     if (count <= 0) return fail(EMEI_ERR_INVALID, "emei_episode_init_obs: count=%lld", (long long)count);
-    int rc;
-    if (is_pend(h->cfg.env_id)) {
-        PendLaunch L = pend_base(h, stream);
-        L.op = PEND_OP_INIT_OBS;
-        L.n = count;
-        L.env_index = env_index;
-        L.episode_in = episode;
-        L.obs_out = obs_out;
-        rc = pend_launch(L);
-    } else {
-        BodyLaunch L = body_base(h, stream);
-        L.op = BODY_OP_INIT_OBS;
-        L.n = count;
-        L.env_index = env_index;
-        L.episode_in = episode;
-        L.obs_out = obs_out;
-        rc = body_launch(L);
-    }
+    LaunchCommon c;
+    c.op = OP_INIT_OBS;
+    c.n = count;
+    c.env_index = env_index;
+    c.episode_in = episode;
+    c.obs_out = obs_out;
+    const int rc = launch(h, c, stream);
     return rc == EMEI_OK ? rc : fail(rc, "emei_episode_init_obs: launch failed");
 }
 
@@ -1661,6 +1501,20 @@ static int fill_env_params(int env_id, uint32_t mask, const double* params, EnvP
 
 static bool bad_io(int io_dtype) { return io_dtype != EMEI_IO_F32 && io_dtype != EMEI_IO_F64; }
 static bool misaligned16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
+// the descriptor of a 4-state kernel launched without a handle, on the caller's current device: rows `obs` of io_dtype
+static PendLaunch pend_stateless(int op, int env_id, int precision, int64_t n, int io_dtype, const void* obs, double dt, void* stream) {
+    PendLaunch L;
+    L.op = op;
+    L.env_id = env_id;
+    L.precision = precision;
+    L.obs_in = obs;
+    L.io_f64 = io_dtype == EMEI_IO_F64;
+    L.n = n;
+    L.p = pend_params(env_id, dt);
+    L.trig = current_device_trig();
+    L.stream = (hipStream_t)stream;
+    return L;
+}
 
 extern "C" EMEI_API int emei_reward_io(int env_id, int64_t n, int io_dtype, const void* obs, const void* pre_obs, const void* action,
                               double real_time_scale, int32_t freq_rate, uint32_t env_param_mask, const double* env_params,
@@ -1672,17 +1526,9 @@ extern "C" EMEI_API int emei_reward_io(int env_id, int64_t n, int io_dtype, cons
         return fail(EMEI_ERR_UNSUPPORTED, "emei_reward: env_id %d has no control-cost term to sum over the batch", env_id);
     if (is_pend(env_id)) {
         if (misaligned16(obs)) return fail(EMEI_ERR_INVALID, "emei_reward: obs must be 16-byte aligned");
-        PendLaunch L;
-        L.op = PEND_OP_REWARD_TERMINAL;
-        L.env_id = env_id;
-        L.precision = EMEI_PRECISION_REF;  // evaluated in float64 whatever the row dtype
-        L.obs_in = obs;
-        L.io_f64 = io_dtype == EMEI_IO_F64;
+        // evaluated in float64 whatever the row dtype
+        PendLaunch L = pend_stateless(OP_REWARD_TERMINAL, env_id, EMEI_PRECISION_REF, n, io_dtype, obs, real_time_scale > 0 ? real_time_scale : 0.02, stream);
         L.reward_out = (float*)reward_out;
-        L.n = n;
-        L.p = pend_params(env_id, real_time_scale > 0 ? real_time_scale : 0.02);
-        L.trig = current_device_trig();
-        L.stream = (hipStream_t)stream;
         int rc = pend_launch(L);
         return rc == EMEI_OK ? rc : fail(rc, "emei_reward: launch failed");
     }
@@ -1692,7 +1538,7 @@ extern "C" EMEI_API int emei_reward_io(int env_id, int64_t n, int io_dtype, cons
         if (!(real_time_scale > 0) || freq_rate < 1) return fail(EMEI_ERR_INVALID, "emei_reward: bad dt/freq_rate");
         BodyLaunch L;
         if (int rc_ = fill_env_params(env_id, env_param_mask, env_params, L.env_params, "emei_reward")) return rc_;
-        L.op = BODY_OP_REWARD;
+        L.op = OP_REWARD;
         L.env_id = env_id;
         L.precision = EMEI_PRECISION_REF;
         L.obs_in = obs, L.pre_obs_in = pre_obs, L.actions = action;
@@ -1729,24 +1575,15 @@ extern "C" EMEI_API int emei_terminal_io(int env_id, int64_t n, int io_dtype, co
     if (bad_io(io_dtype)) return fail(EMEI_ERR_INVALID, "emei_terminal: io_dtype=%d", io_dtype);
     if (is_pend(env_id)) {
         if (misaligned16(obs)) return fail(EMEI_ERR_INVALID, "emei_terminal: obs must be 16-byte aligned");
-        PendLaunch L;
-        L.op = PEND_OP_REWARD_TERMINAL;
-        L.env_id = env_id;
-        L.precision = EMEI_PRECISION_REF;
-        L.obs_in = obs;
-        L.io_f64 = io_dtype == EMEI_IO_F64;
+        PendLaunch L = pend_stateless(OP_REWARD_TERMINAL, env_id, EMEI_PRECISION_REF, n, io_dtype, obs, 0.02, stream);
         L.done_out = terminal_out;
-        L.n = n;
-        L.p = pend_params(env_id, 0.02);
-        L.trig = current_device_trig();
-        L.stream = (hipStream_t)stream;
         int rc = pend_launch(L);
         return rc == EMEI_OK ? rc : fail(rc, "emei_terminal: launch failed");
     }
     if (is_body(env_id)) {
         BodyLaunch L;
         if (int rc_ = fill_env_params(env_id, env_param_mask, env_params, L.env_params, "emei_terminal")) return rc_;
-        L.op = BODY_OP_TERMINAL;
+        L.op = OP_TERMINAL;
         L.env_id = env_id;
         L.precision = EMEI_PRECISION_REF;
         L.obs_in = obs;
@@ -1786,27 +1623,18 @@ extern "C" EMEI_API int emei_next_obs_io(int env_id, int64_t n, int io_dtype, co
     const bool ip_as_body = is_ip(env_id) && integrator != EMEI_INTEG_EULER;
     if (is_pend(env_id) && !ip_as_body) {
         if (misaligned16(obs) || misaligned16(next_obs_out)) return fail(EMEI_ERR_INVALID, "emei_next_obs: obs / next_obs_out must be 16-byte aligned");
-        PendLaunch L;
-        L.op = PEND_OP_NEXT_OBS;
-        L.env_id = env_id;
-        L.precision = precision;
+        PendLaunch L = pend_stateless(OP_NEXT_OBS, env_id, precision, n, io_dtype, obs, real_time_scale, stream);
         L.ode_method = ode_method;
-        L.obs_in = obs;
-        L.io_f64 = io_dtype == EMEI_IO_F64;
         L.actions = actions;
         L.action_dtype = action_dtype;
         L.obs_out = (float*)next_obs_out;
-        L.n = n;
         L.freq_rate = freq_rate;
-        L.p = pend_params(env_id, real_time_scale);
-        L.trig = current_device_trig();
-        L.stream = (hipStream_t)stream;
         int rc = pend_launch(L);
         return rc == EMEI_OK ? rc : fail(rc, "emei_next_obs: launch failed");
     }
     if (action_dtype != EMEI_ACT_F32) return fail(EMEI_ERR_INVALID, "continuous-action envs take float32 actions [n,%d]", ad);
     BodyLaunch L;
-    L.op = BODY_OP_NEXT_OBS;
+    L.op = OP_NEXT_OBS;
     L.env_id = env_id;
     L.precision = precision;
     L.obs_in = obs;

@@ -33,7 +33,7 @@
 // (4.5 KiB per wave and step for the cheetah).  LDS slices are wave-private: no barrier.
 #pragma once
 #include "emei_device.h"
-#include "launch.h"  // PlanLaunch
+#include "launch.h"  // LaunchOp, LaunchCommon
 
 namespace emei {
 
@@ -163,94 +163,21 @@ __device__ __forceinline__ void body_substep(typename Body::real (&s)[Body::NS],
     }
 }
 
-enum BodyOp { BODY_OP_ROLLOUT = 0, BODY_OP_RESET, BODY_OP_GET_OBS, BODY_OP_INIT_OBS, BODY_OP_REWARD, BODY_OP_TERMINAL, BODY_OP_NEXT_OBS,
-              BODY_OP_OCCUPANCY /* host only: *selected = waves of the rollout kernel (of L.integrator) the current device holds at once */,
-              BODY_OP_PLAN /* emei_evaluate_sequences: body_plan_kernel */,
-              BODY_OP_MPC_MPPI /* emei_mpc_mppi: body_mpc_mppi_kernel (Body::kFusedMpc) */,
-              BODY_OP_MPC_CEM /* emei_mpc_cem: body_mpc_cem_kernel (Body::kFusedMpc) */,
-              BODY_OP_POLICY /* emei_rollout_policy: body_policy_rollout_kernel */,
-              BODY_OP_POLICY_EVAL /* emei_evaluate_policies: body_policy_eval_kernel */,
-              BODY_OP_POLICY_NOISY /* emei_rollout_policy_noisy: body_policy_rollout_noisy_kernel */,
-              BODY_OP_POLICY_DEEP /* emei_rollout_policy_deep: body_policy_rollout_deep_kernel */,
-              BODY_OP_POLICY_EVAL_DEEP /* emei_evaluate_policies_deep: body_policy_eval_deep_kernel */,
-              BODY_OP_POLICY_PLAN /* emei_plan_policy: body_policy_plan_kernel */,
-              BODY_OP_POLICY_PLAN_DEEP /* emei_plan_policy_deep: body_policy_plan_deep_kernel */,
-              BODY_OP_MPC_POLICY /* emei_mpc_policy: body_mpc_policy_kernel (Body::kFusedMpc) */ };
-
-// What BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM take beyond the base descriptor: n_steps control steps of the planner with plan.n_candidates
-// candidates over `horizon` steps under plan.discount; plan.cand carries the call's seed, sigma and the ctrlrange (its nominal is
-// unused: the kernel keeps the nominal in LDS), `seed` the handle's reset key; plan.return_out = the workspace [n * K]; obs_out /
-// reward_out / done_out as BODY_OP_ROLLOUT's outputs
-struct MpcLaunch {
-    int32_t horizon = 1;
-    float* nominal = nullptr;  // in/out [horizon, n, act_dim]
-    float* actions_out = nullptr;
-    double* plan_return_out = nullptr;  // [n_steps, n] or null
-    double* ess_out = nullptr;          // MPPI: [n_steps, n] or null
-    double temperature = 1.0;           // MPPI
-    float refill = 0.f, nominal_lo = 0.f, nominal_hi = 0.f;
-    // CEM: `iterations` refits to the n_elites best candidates per control step, plan.cand.sigma the width every control step starts
-    // from, sigma_min the floor of the refitted one
-    int32_t n_elites = 1, iterations = 1;
-    float sigma_min = 0.f;
-    double* elite_return_out = nullptr;  // [n_steps, n] or null
-    // BODY_OP_MPC_POLICY (emei_mpc_policy): horizon, actions_out, plan_return_out, ess_out and temperature as above, no nominal;
-    // `policy` and `policy_noise` as BODY_OP_POLICY_PLAN takes them, control step t under the key policy_noise.seed + t * seed_stride;
-    // plan.return_out = the workspace: [n * K] float64 returns, then [n * K] float32 first actions
-    int32_t act_mode = 0;  // enum emei_mpc_policy_act
-    uint64_t seed_stride = 0;
-    int32_t* plan_index_out = nullptr;  // [n_steps, n] or null
-};
-
-// host-side launch descriptor (abi.hip -> body_dispatch.hip -> body_tu.hip)
-struct BodyLaunch {
-    int op = BODY_OP_ROLLOUT, env_id = 0, precision = 0;
-    void* state = nullptr;
-    int32_t* steps = nullptr;
-    uint32_t* episode = nullptr;
-    unsigned long long* done_mask = nullptr;
-    const void* actions = nullptr;     // rollout / next_obs: float32 [.., n, NA]; BODY_OP_REWARD: dtype of obs_in
-    const void* obs_in = nullptr;      // stateless ops: [n, NO] float32, or float64 when io_f64
-    const void* pre_obs_in = nullptr;
-    int io_f64 = 0;                    // stateless ops: obs_in / pre_obs_in / obs_out / reward_out (and the reward's actions) are float64
-    double* batch_cost_scratch = nullptr;  // BODY_OP_REWARD with EMEI_REWARD_BATCH_CTRL_COST: 8 B of device scratch
-    const int64_t* env_index = nullptr;
-    const uint32_t* episode_in = nullptr;
-    float* obs_out = nullptr;
-    double* obs_f64 = nullptr;
-    float* reward_out = nullptr;
-    uint8_t* done_out = nullptr;
-    int64_t n = 0;
-    int32_t n_steps = 1, freq_rate = 1, max_episode_steps = 0;
-    uint32_t flags = 0;
-    uint64_t seed = 0, env_offset = 0;
+// host-side launch descriptor (abi.hip -> body_dispatch.hip -> body_tu.hip): launch.h's common part (actions: float32 [.., n, NA];
+// policy.actions_out and mpc.actions_out: float32) and what only the body kernels read
+struct BodyLaunch : LaunchCommon {
+    const void* pre_obs_in = nullptr;      // OP_REWARD
+    double* batch_cost_scratch = nullptr;  // OP_REWARD with EMEI_REWARD_BATCH_CTRL_COST: 8 B of device scratch
     double dt = 0.002;
     int32_t integrator = 0;
     int32_t solver = 0;  // enum emei_solver (bodies with several simultaneous constraints)
     NoiseSpec noise;
     EnvParams env_params;
-    const void* trig = nullptr;
     unsigned long long* cap_hits = nullptr;  // device counter of the handle
     // chunked rollout (emei_config.rollout_chunk_steps): the handle's work-queue words (see WorkQueue) and its policy
     uint32_t* work = nullptr;
     int32_t chunk_steps = 0;   // 0 = automatic, -1 = off, k > 0 = k steps per work item
     int32_t resident_waves = 0;  // waves of the rollout kernel the device holds at once (automatic policy); 0 = unknown
-    hipStream_t stream = nullptr;
-    int* selected = nullptr;  // out: enum emei_kernel_id of the rollout kernel launched
-    PlanLaunch plan;  // BODY_OP_PLAN; n_steps = the horizon, obs_out = final_obs [n * K, NO] or null
-    MpcLaunch mpc;    // BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM
-    PolicyNoiseArgs policy_noise = {};  // BODY_OP_POLICY_NOISY (emei_rollout_policy_noisy): the noise of the call, next to `policy`
-    PolicyArgs policy = {};  // BODY_OP_POLICY: BODY_OP_ROLLOUT's fields without `actions`; weights, ctrlrange and actions_out (float32)
-                             // BODY_OP_POLICY_EVAL: the STACKED weights (member p at p * its size), with `plan` as PLAN_GIVEN takes it:
-                             // n_candidates = the number of policies, return_out / length_out [P, n]; obs_out = final_obs [P, n, NO] or null
-    PolicyDeepArgs policy_deep = {};  // BODY_OP_POLICY_DEEP: BODY_OP_POLICY_NOISY's fields with the two-hidden-layer network here
-                                      // (policy_deep.noisy: whether `policy_noise` is the call's noise or unused);
-                                      // BODY_OP_POLICY_EVAL_DEEP: BODY_OP_POLICY_EVAL's fields with the STACKED networks here
-    // BODY_OP_POLICY_PLAN (emei_plan_policy): `policy` and `policy_noise` as BODY_OP_POLICY_NOISY takes them (actions_out unused), `plan`
-    // what PLAN_DRAWN_KEEP takes (cand unused) plus plan.first_actions; n_steps = the horizon
-    PolicyDeepArgs policy_value = {};  // BODY_OP_POLICY_PLAN_DEEP (emei_plan_policy_deep): BODY_OP_POLICY_PLAN's fields with the network
-                                       // in `policy_deep` (noisy set) and the terminal value network here (w1 null: no bootstrap;
-                                       // out_mode, lo, hi and noisy unused)
 };
 int body_launch(const BodyLaunch& L);  // body_dispatch.hip
 
@@ -1649,7 +1576,7 @@ static int launch_body(const BodyLaunch& L) {
     dim3 grid((unsigned)((L.n + kBlock - 1) / kBlock));
     dim3 rgrid((unsigned)((L.n + rollout_block<Body>() - 1) / rollout_block<Body>()));  // the rollout kernel's own block size
     switch (L.op) {
-        case BODY_OP_ROLLOUT: {
+        case OP_ROLLOUT: {
             BodyArgs<Body> a;
             a.state = (R*)L.state, a.steps = L.steps, a.episode = L.episode, a.done_mask = L.done_mask;
             a.actions = (const float*)L.actions, a.obs_out = L.obs_out, a.reward_out = L.reward_out, a.done_out = L.done_out;
@@ -1697,8 +1624,8 @@ static int launch_body(const BodyLaunch& L) {
                                      : (L.integrator == EMEI_INTEG_RK4 ? EMEI_KERNEL_BODY_RK4 : EMEI_KERNEL_BODY);
             break;
         }
-        case BODY_OP_POLICY:
-        case BODY_OP_POLICY_NOISY: {  // always one piece: block b = env block b (the work queue is body_rollout_kernel's)
+        case OP_POLICY:
+        case OP_POLICY_NOISY: {  // always one piece: block b = env block b (the work queue is body_rollout_kernel's)
             const bool rk4 = L.integrator == EMEI_INTEG_RK4;
             BodyArgs<Body> a;
             a.state = (R*)L.state, a.steps = L.steps, a.episode = L.episode, a.done_mask = L.done_mask;
@@ -1710,7 +1637,7 @@ static int launch_body(const BodyLaunch& L) {
             a.cap_hits = L.cap_hits;
             a.work = nullptr, a.chunk_steps = 0, a.n_waves = rgrid.x, a.n_items = 0;
             const dim3 blk(rollout_block<Body>());
-            if (L.op == BODY_OP_POLICY_NOISY) {
+            if (L.op == OP_POLICY_NOISY) {
                 if (rk4) hipLaunchKernelGGL((body_policy_rollout_noisy_kernel<Body, true>), rgrid, blk, 0, L.stream, a, L.policy, L.policy_noise);
                 else hipLaunchKernelGGL((body_policy_rollout_noisy_kernel<Body, false>), rgrid, blk, 0, L.stream, a, L.policy, L.policy_noise);
                 if (L.selected) *L.selected = rk4 ? EMEI_KERNEL_BODY_POLICY_NOISY_RK4 : EMEI_KERNEL_BODY_POLICY_NOISY;
@@ -1721,7 +1648,7 @@ static int launch_body(const BodyLaunch& L) {
             }
             break;
         }
-        case BODY_OP_POLICY_DEEP: {  // one piece, ONE-WAVE blocks for every body: block b = env wave b, its dynamic LDS the h1 tile
+        case OP_POLICY_DEEP: {  // one piece, ONE-WAVE blocks for every body: block b = env wave b, its dynamic LDS the h1 tile
             const bool rk4 = L.integrator == EMEI_INTEG_RK4;
             const dim3 wgrid((unsigned)((L.n + kWave - 1) / kWave));
             BodyArgs<Body> a;
@@ -1746,7 +1673,7 @@ static int launch_body(const BodyLaunch& L) {
             if (L.selected) *L.selected = rk4 ? EMEI_KERNEL_BODY_POLICY_DEEP_RK4 : EMEI_KERNEL_BODY_POLICY_DEEP;
             break;
         }
-        case BODY_OP_POLICY_EVAL_DEEP: {  // block b = (policy b / env waves, env wave b % env waves); abi.hip bounds the grid
+        case OP_POLICY_EVAL_DEEP: {  // block b = (policy b / env waves, env wave b % env waves); abi.hip bounds the grid
             const PlanLaunch& P = L.plan;
             const unsigned env_waves = (unsigned)((L.n + kWave - 1) / kWave);
             const dim3 egrid(env_waves * (unsigned)P.n_candidates);
@@ -1765,7 +1692,7 @@ static int launch_body(const BodyLaunch& L) {
             }
             break;
         }
-        case BODY_OP_POLICY_EVAL: {  // emei_evaluate_policies: block b = (policy b / grid.x, env block b % grid.x); abi.hip bounds the grid
+        case OP_POLICY_EVAL: {  // emei_evaluate_policies: block b = (policy b / grid.x, env block b % grid.x); abi.hip bounds the grid
             const PlanLaunch& P = L.plan;
             const dim3 egrid(grid.x * (unsigned)P.n_candidates);
             const int semi = (int)(L.integrator == EMEI_INTEG_SEMI_IMPLICIT);
@@ -1779,7 +1706,7 @@ static int launch_body(const BodyLaunch& L) {
                                    P.return_out, P.length_out, L.obs_out);
             break;
         }
-        case BODY_OP_POLICY_PLAN: {  // emei_plan_policy: one lane per candidate, n * n_candidates < 2^31 (checked in abi.hip)
+        case OP_POLICY_PLAN: {  // emei_plan_policy: one lane per candidate, n * n_candidates < 2^31 (checked in abi.hip)
             const PlanLaunch& P = L.plan;
             if (!P.partials || !P.return_out || !P.first_actions) return EMEI_ERR_INVALID;
             const dim3 pgrid((unsigned)((L.n * P.n_candidates + kBlock - 1) / kBlock));
@@ -1794,7 +1721,7 @@ static int launch_body(const BodyLaunch& L) {
                                    L.policy, L.policy_noise, L.env_offset, P.return_out, P.first_actions, (PlanPartial*)P.partials);
             break;
         }
-        case BODY_OP_POLICY_PLAN_DEEP: {  // emei_plan_policy_deep: BODY_OP_POLICY_PLAN's lanes as one-wave blocks, the tile as dynamic LDS
+        case OP_POLICY_PLAN_DEEP: {  // emei_plan_policy_deep: OP_POLICY_PLAN's lanes as one-wave blocks, the tile as dynamic LDS
             const PlanLaunch& P = L.plan;
             if (!P.partials || !P.return_out || !P.first_actions) return EMEI_ERR_INVALID;
             const dim3 pgrid((unsigned)((L.n * P.n_candidates + kWave - 1) / kWave));
@@ -1816,7 +1743,7 @@ static int launch_body(const BodyLaunch& L) {
             }
             break;
         }
-        case BODY_OP_OCCUPANCY: {
+        case OP_OCCUPANCY: {
             int dev = 0, cus = 0, nb = 0;
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
                 return EMEI_ERR_HIP;
@@ -1834,19 +1761,19 @@ static int launch_body(const BodyLaunch& L) {
             if (L.selected) *L.selected = nb * cus * (rollout_block<Body>() / kWave);
             return EMEI_OK;
         }
-        case BODY_OP_RESET:
+        case OP_RESET:
             hipLaunchKernelGGL(body_reset_kernel<Body>, grid, dim3(kBlock), 0, L.stream, (R*)L.state, L.steps, L.episode,
                                L.n, L.seed, L.env_offset, NoiseArgs<Body::NS>(L.noise));
             break;
-        case BODY_OP_GET_OBS:
+        case OP_GET_OBS:
             hipLaunchKernelGGL(body_get_obs_kernel<Body>, grid, dim3(kBlock), 0, L.stream, (const R*)L.state, L.obs_f64,
                                L.n, m);
             break;
-        case BODY_OP_INIT_OBS:
+        case OP_INIT_OBS:
             hipLaunchKernelGGL(body_init_obs_kernel<Body>, grid, dim3(kBlock), 0, L.stream, L.env_index, L.episode_in,
                                L.obs_out, L.n, L.seed, L.env_offset, NoiseArgs<Body::NS>(L.noise), m);
             break;
-        case BODY_OP_REWARD: {
+        case OP_REWARD: {
             const double* bc = nullptr;
             if (L.batch_cost_scratch) {  // EMEI_REWARD_BATCH_CTRL_COST: whole-batch sum of action^2 first (stream-ordered)
                 if constexpr (!Body::kHasCtrlCost) return EMEI_ERR_UNSUPPORTED;
@@ -1866,7 +1793,7 @@ static int launch_body(const BodyLaunch& L) {
                                    (const float*)L.pre_obs_in, (const float*)L.actions, (float*)L.reward_out, L.n, L.freq_rate, m, bc);
             break;
         }
-        case BODY_OP_TERMINAL:
+        case OP_TERMINAL:
             if (L.io_f64)
                 hipLaunchKernelGGL((body_terminal_kernel<Body, double>), grid, dim3(kBlock), 0, L.stream, (const double*)L.obs_in,
                                    L.done_out, L.n, m);
@@ -1874,7 +1801,7 @@ static int launch_body(const BodyLaunch& L) {
                 hipLaunchKernelGGL((body_terminal_kernel<Body, float>), grid, dim3(kBlock), 0, L.stream, (const float*)L.obs_in,
                                    L.done_out, L.n, m);
             break;
-        case BODY_OP_NEXT_OBS:
+        case OP_NEXT_OBS:
             if constexpr (Body::kObsIsState) {
                 const int semi = (int)(L.integrator == EMEI_INTEG_SEMI_IMPLICIT);
                 const SinCosEntry* tt = (const SinCosEntry*)L.trig;
@@ -1898,7 +1825,7 @@ static int launch_body(const BodyLaunch& L) {
             } else {
                 return EMEI_ERR_UNSUPPORTED;  // e.g. the double pendulum's observation "wrap" is not invertible
             }
-        case BODY_OP_PLAN: {
+        case OP_PLAN: {
             const PlanLaunch& P = L.plan;
             if (P.mode != PLAN_GIVEN && !P.partials) return EMEI_ERR_INVALID;
             if (P.mode == PLAN_DRAWN_KEEP && !P.return_out) return EMEI_ERR_INVALID;
@@ -1919,15 +1846,15 @@ static int launch_body(const BodyLaunch& L) {
             }
             break;
         }
-        case BODY_OP_MPC_MPPI:
-        case BODY_OP_MPC_CEM:
+        case OP_MPC_MPPI:
+        case OP_MPC_CEM:
             if constexpr (Body::kFusedMpc) {
                 if (int rc = launch_body_mpc<Body>(L, m)) return rc;
                 break;
             } else {
                 return EMEI_ERR_UNSUPPORTED;  // abi.hip refuses these handles with a message of its own
             }
-        case BODY_OP_MPC_POLICY:
+        case OP_MPC_POLICY:
             if constexpr (Body::kFusedMpc) {
                 if (int rc = launch_body_mpc_policy<Body>(L, m)) return rc;
                 break;

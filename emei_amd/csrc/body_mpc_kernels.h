@@ -623,7 +623,7 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
-// the one launch of emei_mpc_policy's body route (BODY_OP_MPC_POLICY), one wave per env
+// the one launch of emei_mpc_policy's body route (OP_MPC_POLICY), one wave per env
 template <class Body>
 static int launch_body_mpc_policy(const BodyLaunch& L, const typename Body::Model& m) {
     const MpcLaunch& M = L.mpc;
@@ -632,7 +632,7 @@ static int launch_body_mpc_policy(const BodyLaunch& L, const typename Body::Mode
     BodyMpcPolicyArgs<Body> a;
     a.state = (typename Body::real*)L.state, a.steps = L.steps, a.episode = L.episode;
     a.trig = (const SinCosEntry*)L.trig, a.cap_hits = L.cap_hits;
-    a.work = L.plan.return_out, a.actions_out = M.actions_out;
+    a.work = L.plan.return_out, a.actions_out = (float*)M.actions_out;
     a.obs_out = L.obs_out, a.reward_out = L.reward_out, a.done_out = L.done_out;
     a.plan_return_out = M.plan_return_out, a.plan_index_out = M.plan_index_out, a.ess_out = M.ess_out;
     a.n = L.n, a.n_steps = L.n_steps, a.horizon = M.horizon, a.n_cand = L.plan.n_candidates;
@@ -651,18 +651,18 @@ static int launch_body_mpc_policy(const BodyLaunch& L, const typename Body::Mode
     return EMEI_OK;
 }
 
-// the one launch of either controller (BODY_OP_MPC_MPPI / BODY_OP_MPC_CEM), one wave per env
+// the one launch of either controller (OP_MPC_MPPI / OP_MPC_CEM), one wave per env
 template <class Body>
 static int launch_body_mpc(const BodyLaunch& L, const typename Body::Model& m) {
     const MpcLaunch& M = L.mpc;
-    const bool cem = L.op == BODY_OP_MPC_CEM;
+    const bool cem = L.op == OP_MPC_CEM;
     if (M.horizon < 1 || M.horizon > EMEI_MPC_MAX_HORIZON) return EMEI_ERR_INVALID;  // the LDS slices of the mean and the sigma
     if (cem && (M.iterations < 1 || M.n_elites < 1 || M.n_elites > L.plan.n_candidates)) return EMEI_ERR_INVALID;
     if (NoiseArgs<Body::NS>(L.noise).obs_on) return EMEI_ERR_UNSUPPORTED;  // the plan's model steps without observation noise
     BodyMpcArgs<Body> a;
     a.state = (typename Body::real*)L.state, a.steps = L.steps, a.episode = L.episode;
     a.trig = (const SinCosEntry*)L.trig, a.cap_hits = L.cap_hits;
-    a.nominal = M.nominal, a.work = L.plan.return_out, a.actions_out = M.actions_out;
+    a.nominal = M.nominal, a.work = L.plan.return_out, a.actions_out = (float*)M.actions_out;
     a.obs_out = L.obs_out, a.reward_out = L.reward_out, a.done_out = L.done_out;
     a.plan_return_out = M.plan_return_out, a.ess_out = M.ess_out, a.elite_return_out = M.elite_return_out;
     a.n = L.n, a.n_steps = L.n_steps, a.horizon = M.horizon, a.n_cand = L.plan.n_candidates;

@@ -1939,13 +1939,13 @@ static int launch_env(const PendLaunch& L) {
     a.seed = L.seed;
     a.env_offset = L.env_offset;
     a.p = Env::make_params(L.p);
-    a.obs_f64 = L.op == PEND_OP_ROLLOUT ? L.obs_f64 : nullptr;
-    a.host_flag = L.op == PEND_OP_ROLLOUT ? L.host_flag : nullptr;
+    a.obs_f64 = L.op == OP_ROLLOUT ? L.obs_f64 : nullptr;
+    a.host_flag = L.op == OP_ROLLOUT ? L.host_flag : nullptr;
     a.flag_value = L.flag_value;
     a.first_block = 0, a.xcd_contiguous = 0;
     dim3 grid((unsigned)((L.n + kBlock - 1) / kBlock));
     switch (L.op) {
-        case PEND_OP_ROLLOUT: {
+        case OP_ROLLOUT: {
             // discrete envs take uint8/int32/int64 actions, continuous envs float32
             int sel;
             if constexpr (Env::kDiscrete) {
@@ -1961,19 +1961,19 @@ static int launch_env(const PendLaunch& L) {
             if (L.selected) *L.selected = sel;
             break;
         }
-        case PEND_OP_RESET:
+        case OP_RESET:
             hipLaunchKernelGGL(pend_reset_kernel<Env>, grid, dim3(kBlock), 0, L.stream, (R*)L.state, L.steps,
                                L.episode, L.n, L.seed, L.env_offset, a.p);
             break;
-        case PEND_OP_INIT_OBS:
+        case OP_INIT_OBS:
             hipLaunchKernelGGL(pend_init_obs_kernel<Env>, grid, dim3(kBlock), 0, L.stream, L.env_index, L.episode_in,
                                (float4*)L.obs_out, L.n, L.seed, L.env_offset, a.p);
             break;
-        case PEND_OP_GET_OBS:
+        case OP_GET_OBS:
             hipLaunchKernelGGL(pend_get_obs_kernel<Env>, grid, dim3(kBlock), 0, L.stream, (const R*)L.state,
                                L.obs_f64, L.n);
             break;
-        case PEND_OP_REWARD_TERMINAL:
+        case OP_REWARD_TERMINAL:
             if (L.io_f64)
                 hipLaunchKernelGGL((pend_reward_terminal_kernel<Env, double>), grid, dim3(kBlock), 0, L.stream,
                                    (const double*)L.obs_in, (double*)L.reward_out, L.done_out, L.n, a.p, a.trig);
@@ -1981,7 +1981,7 @@ static int launch_env(const PendLaunch& L) {
                 hipLaunchKernelGGL((pend_reward_terminal_kernel<Env, float>), grid, dim3(kBlock), 0, L.stream,
                                    (const float*)L.obs_in, (float*)L.reward_out, L.done_out, L.n, a.p, a.trig);
             break;
-        case PEND_OP_NEXT_OBS:
+        case OP_NEXT_OBS:
             if (L.io_f64)
                 hipLaunchKernelGGL((pend_next_obs_kernel<Env, double>), grid, dim3(kBlock), 0, L.stream, (const double*)L.obs_in,
                                    L.actions, L.action_dtype, (double*)L.obs_out, L.n, L.freq_rate, a.p, a.trig);
@@ -1989,7 +1989,7 @@ static int launch_env(const PendLaunch& L) {
                 hipLaunchKernelGGL((pend_next_obs_kernel<Env, float>), grid, dim3(kBlock), 0, L.stream, (const float*)L.obs_in,
                                    L.actions, L.action_dtype, (float*)L.obs_out, L.n, L.freq_rate, a.p, a.trig);
             break;
-        case PEND_OP_PLAN: {
+        case OP_PLAN: {
             const PlanLaunch& P = L.plan;
             if (P.mode == PLAN_GIVEN) {
                 // discrete envs take uint8/int32/int64 actions, continuous envs float32
@@ -2022,84 +2022,84 @@ static int launch_env(const PendLaunch& L) {
             }
             break;
         }
-        case PEND_OP_MPC: {
+        case OP_MPC_MPPI: {
             MpcArgs<Env> m;
             m.state = (R*)L.state, m.steps = L.steps, m.episode = L.episode, m.trig = a.trig;
-            m.nominal = L.mpc_nominal, m.work = L.plan.return_out, m.actions_out = L.mpc_actions_out;
+            m.nominal = L.mpc.nominal, m.work = L.plan.return_out, m.actions_out = L.mpc.actions_out;
             m.obs_out = (float4*)L.obs_out, m.reward_out = L.reward_out, m.done_out = L.done_out;
-            m.plan_return_out = L.plan_return_out, m.ess_out = L.ess_out;
-            m.n = L.n, m.n_steps = L.n_steps, m.horizon = L.horizon, m.n_cand = L.plan.n_candidates, m.freq_rate = L.freq_rate;
+            m.plan_return_out = L.mpc.plan_return_out, m.ess_out = L.mpc.ess_out;
+            m.n = L.n, m.n_steps = L.n_steps, m.horizon = L.mpc.horizon, m.n_cand = L.plan.n_candidates, m.freq_rate = L.freq_rate;
             m.action_dtype = L.action_dtype, m.max_episode_steps = L.max_episode_steps, m.flags = L.flags;
             m.reset_seed = L.seed, m.env_offset = L.env_offset, m.seed = L.plan.cand.seed;
-            m.discount = L.plan.discount, m.temperature = L.temperature;
+            m.discount = L.plan.discount, m.temperature = L.mpc.temperature;
             m.sigma = L.plan.cand.sigma, m.lo = L.plan.cand.lo, m.hi = L.plan.cand.hi;
-            m.refill = L.refill, m.nominal_lo = L.nominal_lo, m.nominal_hi = L.nominal_hi;
+            m.refill = L.mpc.refill, m.nominal_lo = L.mpc.nominal_lo, m.nominal_hi = L.mpc.nominal_hi;
             m.p = a.p;
-            if (L.horizon < 1 || L.horizon > EMEI_MPC_MAX_HORIZON) return EMEI_ERR_INVALID;  // the LDS slice of the nominal
+            if (L.mpc.horizon < 1 || L.mpc.horizon > EMEI_MPC_MAX_HORIZON) return EMEI_ERR_INVALID;  // the LDS slice of the nominal
             constexpr int kWavesPerBlock = kBlock / kWave;  // one wave per env
             const dim3 mgrid((unsigned)((L.n + kWavesPerBlock - 1) / kWavesPerBlock));
             hipLaunchKernelGGL(pend_mpc_mppi_kernel<Env>, mgrid, dim3(kBlock), 0, L.stream, m);
             if (L.selected) *L.selected = EMEI_KERNEL_PEND_MPC_MPPI;
             break;
         }
-        case PEND_OP_MPC_CEM: {
+        case OP_MPC_CEM: {
             MpcCemArgs<Env> m;
             m.state = (R*)L.state, m.steps = L.steps, m.episode = L.episode, m.trig = a.trig;
-            m.nominal = L.mpc_nominal, m.work = L.plan.return_out, m.actions_out = L.mpc_actions_out;
+            m.nominal = L.mpc.nominal, m.work = L.plan.return_out, m.actions_out = L.mpc.actions_out;
             m.obs_out = (float4*)L.obs_out, m.reward_out = L.reward_out, m.done_out = L.done_out;
-            m.plan_return_out = L.plan_return_out, m.elite_return_out = L.elite_return_out;
-            m.n = L.n, m.n_steps = L.n_steps, m.horizon = L.horizon, m.n_cand = L.plan.n_candidates, m.n_elites = L.n_elites;
-            m.iterations = L.iterations, m.freq_rate = L.freq_rate;
+            m.plan_return_out = L.mpc.plan_return_out, m.elite_return_out = L.mpc.elite_return_out;
+            m.n = L.n, m.n_steps = L.n_steps, m.horizon = L.mpc.horizon, m.n_cand = L.plan.n_candidates, m.n_elites = L.mpc.n_elites;
+            m.iterations = L.mpc.iterations, m.freq_rate = L.freq_rate;
             m.action_dtype = L.action_dtype, m.max_episode_steps = L.max_episode_steps, m.flags = L.flags;
             m.reset_seed = L.seed, m.env_offset = L.env_offset, m.seed = L.plan.cand.seed;
             m.discount = L.plan.discount;
-            m.sigma = L.plan.cand.sigma, m.sigma_min = L.sigma_min, m.lo = L.plan.cand.lo, m.hi = L.plan.cand.hi;
-            m.refill = L.refill, m.nominal_lo = L.nominal_lo, m.nominal_hi = L.nominal_hi;
+            m.sigma = L.plan.cand.sigma, m.sigma_min = L.mpc.sigma_min, m.lo = L.plan.cand.lo, m.hi = L.plan.cand.hi;
+            m.refill = L.mpc.refill, m.nominal_lo = L.mpc.nominal_lo, m.nominal_hi = L.mpc.nominal_hi;
             m.p = a.p;
-            if (L.horizon < 1 || L.horizon > EMEI_MPC_MAX_HORIZON) return EMEI_ERR_INVALID;  // the LDS slices of the mean and the sigma
-            if (L.iterations < 1 || L.n_elites < 1 || L.n_elites > L.plan.n_candidates) return EMEI_ERR_INVALID;
+            if (L.mpc.horizon < 1 || L.mpc.horizon > EMEI_MPC_MAX_HORIZON) return EMEI_ERR_INVALID;  // the LDS slices of the mean and the sigma
+            if (L.mpc.iterations < 1 || L.mpc.n_elites < 1 || L.mpc.n_elites > L.plan.n_candidates) return EMEI_ERR_INVALID;
             constexpr int kWavesPerBlock = kBlock / kWave;  // one wave per env
             const dim3 mgrid((unsigned)((L.n + kWavesPerBlock - 1) / kWavesPerBlock));
             hipLaunchKernelGGL(pend_mpc_cem_kernel<Env>, mgrid, dim3(kBlock), 0, L.stream, m);
             if (L.selected) *L.selected = EMEI_KERNEL_PEND_MPC_CEM;
             break;
         }
-        case PEND_OP_MPC_POLICY: {
+        case OP_MPC_POLICY: {
             MpcPolicyArgs<Env> m;
             m.state = (R*)L.state, m.steps = L.steps, m.episode = L.episode, m.trig = a.trig;
-            m.work = L.plan.return_out, m.actions_out = L.mpc_actions_out;
+            m.work = L.plan.return_out, m.actions_out = L.mpc.actions_out;
             m.obs_out = (float4*)L.obs_out, m.reward_out = L.reward_out, m.done_out = L.done_out;
-            m.plan_return_out = L.plan_return_out, m.plan_index_out = L.plan_index_out, m.ess_out = L.ess_out;
-            m.n = L.n, m.n_steps = L.n_steps, m.horizon = L.horizon, m.n_cand = L.plan.n_candidates, m.freq_rate = L.freq_rate;
-            m.action_dtype = L.action_dtype, m.max_episode_steps = L.max_episode_steps, m.act_mode = L.act_mode, m.flags = L.flags;
-            m.reset_seed = L.seed, m.env_offset = L.env_offset, m.seed_stride = L.seed_stride;
-            m.discount = L.plan.discount, m.temperature = L.temperature;
+            m.plan_return_out = L.mpc.plan_return_out, m.plan_index_out = L.mpc.plan_index_out, m.ess_out = L.mpc.ess_out;
+            m.n = L.n, m.n_steps = L.n_steps, m.horizon = L.mpc.horizon, m.n_cand = L.plan.n_candidates, m.freq_rate = L.freq_rate;
+            m.action_dtype = L.action_dtype, m.max_episode_steps = L.max_episode_steps, m.act_mode = L.mpc.act_mode, m.flags = L.flags;
+            m.reset_seed = L.seed, m.env_offset = L.env_offset, m.seed_stride = L.mpc.seed_stride;
+            m.discount = L.plan.discount, m.temperature = L.mpc.temperature;
             m.p = a.p;
-            if (L.horizon < 1 || L.plan.n_candidates < 1 || !m.work || !m.actions_out) return EMEI_ERR_INVALID;
+            if (L.mpc.horizon < 1 || L.plan.n_candidates < 1 || !m.work || !m.actions_out) return EMEI_ERR_INVALID;
             constexpr int kWavesPerBlock = kBlock / kWave;  // one wave per env
             const dim3 mgrid((unsigned)((L.n + kWavesPerBlock - 1) / kWavesPerBlock));
             hipLaunchKernelGGL(pend_mpc_policy_kernel<Env>, mgrid, dim3(kBlock), 0, L.stream, m, L.policy, L.policy_noise);
             if (L.selected) *L.selected = EMEI_KERNEL_PEND_MPC_POLICY;
             break;
         }
-        case PEND_OP_POLICY:
+        case OP_POLICY:
             if (L.peers.count > 0) return EMEI_ERR_UNSUPPORTED;  // no peer stores on this kernel (abi.hip refuses with a message)
             hipLaunchKernelGGL(pend_policy_rollout_kernel<Env>, grid, dim3(kBlock), 0, L.stream, a, L.policy);
             if (L.selected) *L.selected = EMEI_KERNEL_PEND_POLICY;
             break;
-        case PEND_OP_POLICY_NOISY:
+        case OP_POLICY_NOISY:
             if (L.peers.count > 0) return EMEI_ERR_UNSUPPORTED;
             hipLaunchKernelGGL(pend_policy_rollout_noisy_kernel<Env>, grid, dim3(kBlock), 0, L.stream, a, L.policy, L.policy_noise);
             if (L.selected) *L.selected = EMEI_KERNEL_PEND_POLICY_NOISY;
             break;
-        case PEND_OP_POLICY_EVAL: {  // emei_evaluate_policies: block b = (policy b / grid.x, env block b % grid.x); abi.hip bounds the grid
+        case OP_POLICY_EVAL: {  // emei_evaluate_policies: block b = (policy b / grid.x, env block b % grid.x); abi.hip bounds the grid
             const PlanLaunch& P = L.plan;
             hipLaunchKernelGGL(pend_policy_eval_kernel<Env>, dim3(grid.x * (unsigned)P.n_candidates), dim3(kBlock), 0, L.stream,
                                (const R*)L.state, P.start_rows, L.n, grid.x, L.n_steps, P.discount, L.freq_rate, a.p, a.trig, L.policy,
                                P.return_out, P.length_out, (float4*)L.obs_out);
             break;
         }
-        case PEND_OP_POLICY_PLAN: {  // emei_plan_policy: one lane per candidate, n * n_candidates < 2^31 (checked in abi.hip)
+        case OP_POLICY_PLAN: {  // emei_plan_policy: one lane per candidate, n * n_candidates < 2^31 (checked in abi.hip)
             const PlanLaunch& P = L.plan;
             if (!P.partials || !P.return_out || !P.first_actions) return EMEI_ERR_INVALID;
             const dim3 pgrid((unsigned)((L.n * P.n_candidates + kBlock - 1) / kBlock));
@@ -2108,7 +2108,7 @@ static int launch_env(const PendLaunch& L) {
                                P.return_out, P.first_actions, (PlanPartial*)P.partials);
             break;
         }
-        case PEND_OP_POLICY_PLAN_DEEP: {  // emei_plan_policy_deep: PEND_OP_POLICY_PLAN's lanes as one-wave blocks, the tile as dynamic LDS
+        case OP_POLICY_PLAN_DEEP: {  // emei_plan_policy_deep: OP_POLICY_PLAN's lanes as one-wave blocks, the tile as dynamic LDS
             const PlanLaunch& P = L.plan;
             if (!P.partials || !P.return_out || !P.first_actions) return EMEI_ERR_INVALID;
             if (int rc = policy_deep_lds_opt_in<pend_policy_plan_deep_kernel<Env>>()) return rc;
@@ -2119,7 +2119,7 @@ static int launch_env(const PendLaunch& L) {
                                L.policy_noise, L.policy_value, L.env_offset, P.return_out, P.first_actions, (PlanPartial*)P.partials);
             break;
         }
-        case PEND_OP_POLICY_DEEP: {  // one-wave blocks, the wave's h1 tile as dynamic LDS
+        case OP_POLICY_DEEP: {  // one-wave blocks, the wave's h1 tile as dynamic LDS
             if (L.peers.count > 0) return EMEI_ERR_UNSUPPORTED;
             if (int rc = policy_deep_lds_opt_in<pend_policy_rollout_deep_kernel<Env>>()) return rc;
             const dim3 wgrid((unsigned)((L.n + kWave - 1) / kWave));
@@ -2128,7 +2128,7 @@ static int launch_env(const PendLaunch& L) {
             if (L.selected) *L.selected = EMEI_KERNEL_PEND_POLICY_DEEP;
             break;
         }
-        case PEND_OP_POLICY_EVAL_DEEP: {  // block b = (policy b / env waves, env wave b % env waves); abi.hip bounds the grid
+        case OP_POLICY_EVAL_DEEP: {  // block b = (policy b / env waves, env wave b % env waves); abi.hip bounds the grid
             const PlanLaunch& P = L.plan;
             if (int rc = policy_deep_lds_opt_in<pend_policy_eval_deep_kernel<Env>>()) return rc;
             const unsigned env_waves = (unsigned)((L.n + kWave - 1) / kWave);

@@ -76,6 +76,40 @@ def _sigmas(x, state_dim):
     return x
 
 
+def _plan_policy_checked(engine, H, K, policy, noise, value, discount, temperature, deep):
+    """validated (H, K, policy struct, noise struct, value struct or None, discount, temperature or None) of Engine.plan_policy — deep:
+    with a policy.DeepMLPPolicy (emei_plan_policy_deep), else with a one-layer policy.MLPPolicy; policy, noise and value are bound
+    to `engine` (shapes against the env, the noise mode against the env kind).  Needs no handle."""
+    from .policy import DeepMLPPolicy, DeepValueFunction, MLPPolicy, PolicyNoise
+
+    H, K = int(H), int(K)
+    if H < 1 or K < 1:
+        raise ValueError(f"horizon={H} and n_candidates={K} must be >= 1")
+    if deep and not isinstance(policy, DeepMLPPolicy):
+        raise TypeError("the two-hidden-layer plan_policy takes an emei_amd.DeepMLPPolicy")
+    if not isinstance(policy, MLPPolicy):
+        raise TypeError("plan_policy takes an emei_amd.MLPPolicy")
+    if not deep and isinstance(policy, DeepMLPPolicy):
+        raise ValueError("plan_policy: the two-hidden-layer network (DeepMLPPolicy) is not served by this call yet; "
+                         "it takes an MLPPolicy with one hidden layer or none")
+    if not isinstance(noise, PolicyNoise):
+        raise TypeError("plan_policy takes an emei_amd.PolicyNoise (the exploration noise that makes the candidates differ)")
+    if value is not None and not isinstance(value, DeepValueFunction):
+        raise TypeError("plan_policy takes an emei_amd.DeepValueFunction as value= (the terminal value network), or None")
+    discount = float(discount)
+    if not 0.0 < discount <= 1.0:
+        raise ValueError(f"discount={discount} is outside (0, 1]")
+    if temperature is not None:
+        temperature = float(temperature)
+        if not (0.0 < temperature < float("inf")):
+            raise ValueError(f"temperature={temperature} must be finite and > 0 (None: no weighted mean, no ess)")
+    policy.bind(engine)
+    # a log-std head reads the last hidden layer (the affine policy: the observation)
+    ns = noise.bind(engine).struct(policy.hidden2 if deep else policy.hidden if policy.hidden else policy.obs_dim)
+    vs = value.bind(engine).struct() if value is not None else None
+    return H, K, policy.struct(), ns, vs, discount, temperature
+
+
 class Engine:
     """N independent env instances of one kind on one GPU (this rank's shard)."""
 
@@ -361,8 +395,6 @@ class Engine:
             L.check(L.lib().emei_rollout_policy(self._h, T, C.byref(ps), _ptr(act), _ACT_DTYPES[dtype], _ptr(obs), _ptr(rew), _ptr(done),
                                                 flags, _stream()))
             return act, obs, rew, done
-        if not isinstance(noise, PolicyNoise):
-            raise TypeError("noise= takes an emei_amd.PolicyNoise")
         ns = noise.bind(self).struct(policy.hidden if policy.hidden else policy.obs_dim)
         L.check(L.lib().emei_rollout_policy_noisy(self._h, T, C.byref(ps), C.byref(ns), _ptr(act), _ACT_DTYPES[dtype], _ptr(obs), _ptr(rew),
                                                   _ptr(done), flags, _stream()))
@@ -533,56 +565,12 @@ class Engine:
 
     # -- planning around a feedback policy (emei_plan_policy) ---------------------------------------------------
     def _plan_policy_args(self, H, K, policy, noise, discount, temperature):
-        """validated (H, K, policy struct, noise struct, discount, temperature or None) of plan_policy; policy and noise are bound to
-        this engine (shapes against the env, the noise mode against the env kind).  Needs no handle."""
-        from .policy import DeepMLPPolicy, MLPPolicy, PolicyNoise
-
-        H, K = int(H), int(K)
-        if H < 1 or K < 1:
-            raise ValueError(f"horizon={H} and n_candidates={K} must be >= 1")
-        if not isinstance(policy, MLPPolicy):
-            raise TypeError("plan_policy takes an emei_amd.MLPPolicy")
-        if isinstance(policy, DeepMLPPolicy):
-            raise ValueError("plan_policy: the two-hidden-layer network (DeepMLPPolicy) is not served by this call yet; "
-                             "it takes an MLPPolicy with one hidden layer or none")
-        if not isinstance(noise, PolicyNoise):
-            raise TypeError("plan_policy takes an emei_amd.PolicyNoise (the exploration noise that makes the candidates differ)")
-        discount = float(discount)
-        if not 0.0 < discount <= 1.0:
-            raise ValueError(f"discount={discount} is outside (0, 1]")
-        if temperature is not None:
-            temperature = float(temperature)
-            if not (0.0 < temperature < float("inf")):
-                raise ValueError(f"temperature={temperature} must be finite and > 0 (None: no weighted mean, no ess)")
-        policy.bind(self)
-        ns = noise.bind(self).struct(policy.hidden if policy.hidden else policy.obs_dim)
-        return H, K, policy.struct(), ns, discount, temperature
+        """_plan_policy_checked for the one-layer calls (plan_policy, mpc_policy), which have no value network"""
+        H, K, ps, ns, _, discount, temperature = _plan_policy_checked(self, H, K, policy, noise, None, discount, temperature, False)
+        return H, K, ps, ns, discount, temperature
 
     def _plan_policy_deep_args(self, H, K, policy, noise, value, discount, temperature):
-        """validated (H, K, policy struct, noise struct, value struct or None, discount, temperature or None) of plan_policy with a
-        policy.DeepMLPPolicy (emei_plan_policy_deep); policy, noise and value are bound to this engine.  Needs no handle."""
-        from .policy import DeepMLPPolicy, DeepValueFunction, PolicyNoise
-
-        H, K = int(H), int(K)
-        if H < 1 or K < 1:
-            raise ValueError(f"horizon={H} and n_candidates={K} must be >= 1")
-        if not isinstance(policy, DeepMLPPolicy):
-            raise TypeError("the two-hidden-layer plan_policy takes an emei_amd.DeepMLPPolicy")
-        if not isinstance(noise, PolicyNoise):
-            raise TypeError("plan_policy takes an emei_amd.PolicyNoise (the exploration noise that makes the candidates differ)")
-        if value is not None and not isinstance(value, DeepValueFunction):
-            raise TypeError("plan_policy takes an emei_amd.DeepValueFunction as value= (the terminal value network), or None")
-        discount = float(discount)
-        if not 0.0 < discount <= 1.0:
-            raise ValueError(f"discount={discount} is outside (0, 1]")
-        if temperature is not None:
-            temperature = float(temperature)
-            if not (0.0 < temperature < float("inf")):
-                raise ValueError(f"temperature={temperature} must be finite and > 0 (None: no weighted mean, no ess)")
-        policy.bind(self)
-        ns = noise.bind(self).struct(policy.hidden2)  # a log-std head reads h2
-        vs = value.bind(self).struct() if value is not None else None
-        return H, K, policy.struct(), ns, vs, discount, temperature
+        return _plan_policy_checked(self, H, K, policy, noise, value, discount, temperature, True)
 
     @_on_device
     def plan_policy(self, H, K, policy, noise, discount=1.0, temperature=None, start_state=None, returns=False, length=False, ess=False,
@@ -608,10 +596,7 @@ class Engine:
         if value is not None and not deep:
             raise ValueError("plan_policy: value= (the terminal value) comes with the two-hidden-layer call: pass a DeepMLPPolicy (a "
                              "one-layer policy embeds in one exactly: include/emei_hip.h, emei_rollout_policy_deep)")
-        if deep:
-            H, K, ps, ns, vs, discount, temperature = self._plan_policy_deep_args(H, K, policy, noise, value, discount, temperature)
-        else:
-            H, K, ps, ns, discount, temperature = self._plan_policy_args(H, K, policy, noise, discount, temperature)
+        H, K, ps, ns, vs, discount, temperature = _plan_policy_checked(self, H, K, policy, noise, value, discount, temperature, deep)
         if ess and temperature is None:
             raise ValueError("ess=True needs a temperature")
         st = self._start_rows(start_state)
@@ -633,6 +618,23 @@ class Engine:
         return (act, ret, idx) + ((mean,) if mean is not None else ()) + ((rets,) if returns else ()) + ((ln,) if length else ()) \
             + ((es,) if ess else ())
 
+    def _mpc_nominal_defaults(self, refill, clamp):
+        """(refill, lo, hi) of mpc_mppi / mpc_cem with their defaults: refill 0.5 (discrete) / 0.0 (continuous), the clamp (0.05, 0.95)
+        on the discrete envs and the ctrlrange on the continuous ones"""
+        if refill is None:
+            refill = 0.5 if self.act_dim == 0 else 0.0
+        if clamp is None:
+            clamp = (0.05, 0.95) if self.act_dim == 0 else _CTRL_RANGE.get(self.env_name, (-1.0, 1.0))
+        return refill, float(clamp[0]), float(clamp[1])
+
+    def _mpc_outputs(self, T, out, dtype, diagnostics):
+        """what a fused controller fills: (actions [T, N(, act_dim)] of `dtype`, obs, reward, done — `out`, checked, or new ones, as
+        rollout's — and a list with one [T, N] tensor per dtype of `diagnostics`, None for a None)"""
+        obs, rew, done = self._check_outputs(out, (T,)) if out is not None else self.alloc_outputs(T)
+        act = torch.empty((T, self.n_envs) + self._act_tail, dtype=dtype, device=self.device)
+        diag = [None if dt is None else torch.empty((T, self.n_envs), dtype=dt, device=self.device) for dt in diagnostics]
+        return act, obs, rew, done, diag
+
     @_on_device
     def mpc_mppi(self, T, H, K, seed, temperature, nominal, discount=1.0, sigma=None, refill=None, clamp=None, auto_reset=False,
                  out=None, diagnostics=False):
@@ -653,16 +655,9 @@ class Engine:
         if nominal is None:
             raise ValueError("mpc_mppi needs a nominal tensor (it is updated in place)")
         H, K, nominal, sigma, dtype = self._candidate_args(H, K, nominal, sigma, None)
-        if refill is None:
-            refill = 0.5 if self.act_dim == 0 else 0.0
-        if clamp is None:
-            clamp = (0.05, 0.95) if self.act_dim == 0 else _CTRL_RANGE.get(self.env_name, (-1.0, 1.0))
-        lo, hi = float(clamp[0]), float(clamp[1])
-        obs, rew, done = self._check_outputs(out, (T,)) if out is not None else self.alloc_outputs(T)
+        refill, lo, hi = self._mpc_nominal_defaults(refill, clamp)
+        act, obs, rew, done, (pr, es) = self._mpc_outputs(T, out, dtype, (torch.float64,) * 2 if diagnostics else (None,) * 2)
         ws = self._workspace("_mpc_ws", L.lib().emei_mpc_mppi_workspace_bytes, K)
-        act = torch.empty((T, self.n_envs) + self._act_tail, dtype=dtype, device=self.device)
-        pr = torch.empty((T, self.n_envs), dtype=torch.float64, device=self.device) if diagnostics else None
-        es = torch.empty((T, self.n_envs), dtype=torch.float64, device=self.device) if diagnostics else None
         L.check(L.lib().emei_mpc_mppi(self._h, T, H, K, _seed64(seed), _ptr(nominal), sigma, float(discount), float(temperature),
                                       float(refill), lo, hi, _ptr(ws), _ptr(act), _ACT_DTYPES[dtype], _ptr(obs), _ptr(rew), _ptr(done),
                                       _ptr(pr), _ptr(es), L.FLAG_AUTO_RESET if auto_reset else 0, _stream()))
@@ -693,16 +688,9 @@ class Engine:
             raise ValueError(f"n_elites={n_elites} is outside [1, n_candidates={K}]")
         if iterations < 1:
             raise ValueError(f"iterations={iterations} must be >= 1")
-        if refill is None:
-            refill = 0.5 if self.act_dim == 0 else 0.0
-        if clamp is None:
-            clamp = (0.05, 0.95) if self.act_dim == 0 else _CTRL_RANGE.get(self.env_name, (-1.0, 1.0))
-        lo, hi = float(clamp[0]), float(clamp[1])
-        obs, rew, done = self._check_outputs(out, (T,)) if out is not None else self.alloc_outputs(T)
+        refill, lo, hi = self._mpc_nominal_defaults(refill, clamp)
+        act, obs, rew, done, (pr, er) = self._mpc_outputs(T, out, dtype, (torch.float64,) * 2 if diagnostics else (None,) * 2)
         ws = self._workspace("_mpc_cem_ws", L.lib().emei_mpc_cem_workspace_bytes, K)
-        act = torch.empty((T, self.n_envs) + self._act_tail, dtype=dtype, device=self.device)
-        pr = torch.empty((T, self.n_envs), dtype=torch.float64, device=self.device) if diagnostics else None
-        er = torch.empty((T, self.n_envs), dtype=torch.float64, device=self.device) if diagnostics else None
         L.check(L.lib().emei_mpc_cem(self._h, T, H, K, n_elites, iterations, _seed64(seed), _ptr(nominal), sigma, float(sigma_min),
                                      float(discount), float(refill), lo, hi, _ptr(ws), _ptr(act), _ACT_DTYPES[dtype], _ptr(obs), _ptr(rew),
                                      _ptr(done), _ptr(pr), _ptr(er), L.FLAG_AUTO_RESET if auto_reset else 0, _stream()))
@@ -736,14 +724,10 @@ class Engine:
             raise ValueError("act='mean' needs a temperature")
         H, K, ps, ns, discount, temperature = self._plan_policy_args(H, K, policy, noise, discount, temperature)
         stride = H if seed_stride is None else int(seed_stride)
-        obs, rew, done = self._check_outputs(out, (T,)) if out is not None else self.alloc_outputs(T)
-        ws = self._workspace("_mpc_policy_ws", L.lib().emei_mpc_policy_workspace_bytes, K)
         dtype = torch.int64 if self.act_dim == 0 else torch.float32
-        new = lambda dt: torch.empty((T, self.n_envs), dtype=dt, device=self.device)
-        actions = torch.empty((T, self.n_envs) + self._act_tail, dtype=dtype, device=self.device)
-        pr = new(torch.float64) if diagnostics else None
-        pi = new(torch.int32) if diagnostics else None
-        es = new(torch.float64) if diagnostics and temperature is not None else None
+        diag = (torch.float64, torch.int32, torch.float64 if temperature is not None else None) if diagnostics else (None,) * 3
+        actions, obs, rew, done, (pr, pi, es) = self._mpc_outputs(T, out, dtype, diag)
+        ws = self._workspace("_mpc_policy_ws", L.lib().emei_mpc_policy_workspace_bytes, K)
         L.check(L.lib().emei_mpc_policy(self._h, T, H, K, C.byref(ps), C.byref(ns), _seed64(stride),
                                         L.MPC_POLICY_ACT_MEAN if act == "mean" else L.MPC_POLICY_ACT_BEST, discount,
                                         1.0 if temperature is None else temperature, _ptr(ws), _ptr(actions), _ACT_DTYPES[dtype],
