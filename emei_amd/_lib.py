@@ -229,6 +229,15 @@ SYMBOLS = {
     "emei_evaluate_policies_deep": (C.c_int, [_vp, _i32, _i32, C.POINTER(EmeiPolicyDeep), _dbl, _vp, _vp, _vp, _vp, _vp]),
     "emei_plan_policy_deep": (C.c_int, [_vp, _i32, _i32, C.POINTER(EmeiPolicyDeep), C.POINTER(EmeiPolicyNoise), C.POINTER(EmeiPolicyDeep),
                                         _dbl, _dbl, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the open-loop plan calls with a terminal value: the plain call's arguments with `value` after `discount`
+    "emei_plan_value_workspace_bytes": (_i64, [_i64, _i32]),
+    "emei_evaluate_sequences_value": (C.c_int, [_vp, _i32, _i32, _vp, C.c_int, _dbl, C.POINTER(EmeiPolicyDeep), _vp, _vp, _vp, _vp, _vp]),
+    "emei_plan_shooting_value": (C.c_int, [_vp, _i32, _i32, _u64, _vp, _dbl, _dbl, C.POINTER(EmeiPolicyDeep), _vp, _vp, _vp, C.c_int, _vp,
+                                           _vp, _vp, _vp, _vp]),
+    "emei_plan_mppi_value": (C.c_int, [_vp, _i32, _i32, _u64, _vp, _dbl, _dbl, C.POINTER(EmeiPolicyDeep), _dbl, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp]),
+    "emei_plan_cem_value": (C.c_int, [_vp, _i32, _i32, _i32, _u64, _vp, _dbl, _vp, _dbl, C.POINTER(EmeiPolicyDeep), _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp]),
     "emei_mpc_policy_workspace_bytes": (_i64, [_i64, _i32]),
     "emei_mpc_policy": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(EmeiPolicy), C.POINTER(EmeiPolicyNoise), _u64, _i32, _dbl, _dbl, _vp, _vp,
                                   C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),

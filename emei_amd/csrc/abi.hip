@@ -744,29 +744,59 @@ static double* plan_returns(const emei_env* h, int32_t n_candidates, void* works
     return (double*)((char*)workspace + plan_partials_bytes(h->cfg.n_envs, h->cfg.n_envs * (int64_t)n_candidates));
 }
 
-// what every OP_PLAN call sets alike (launch.h: PlanMode)
-static LaunchCommon plan_call(int mode, const double* start_rows, int32_t horizon, int32_t n_candidates, double discount) {
+// The *_value twins of the four open-loop plan calls share their plain call's body: `with_value` adds the terminal value's refusals
+// between the scalars and the handle (check_plan_value) and sends the first launch to OP_PLAN_VALUE.  The struct helpers are the
+// deep policy calls' (below).
+static int check_policy_deep_struct(const char* fn, const char* arg, const emei_policy_deep* policy, bool with_out_mode = true);
+static int check_policy_deep_weights(const char* fn, const char* arg, const emei_policy_deep* policy);
+static PolicyDeepArgs policy_value_args(const emei_policy_deep* value);
+
+// NULL value, value.struct_size, .hidden1, .hidden2, .reserved; a NULL handle; NULL value w1 .. b3
+static int check_plan_value(const char* fn, const emei_env* h, const emei_policy_deep* value) {
+    if (int rc = check_policy_deep_struct(fn, "value", value, false)) return rc;
+    if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
+    return check_policy_deep_weights(fn, "value", value);
+}
+
+// what every OP_PLAN / OP_PLAN_VALUE call sets alike (launch.h: PlanMode); value: the checked terminal value, or null for OP_PLAN
+static LaunchCommon plan_call(int mode, const double* start_rows, int32_t horizon, int32_t n_candidates, double discount,
+                              const emei_policy_deep* value) {
     LaunchCommon c;
-    c.op = OP_PLAN, c.n_steps = horizon;
+    c.op = value ? OP_PLAN_VALUE : OP_PLAN, c.n_steps = horizon;
     c.plan.mode = mode, c.plan.start_rows = start_rows, c.plan.n_candidates = n_candidates, c.plan.discount = discount;
+    c.policy_value = policy_value_args(value);
     return c;
 }
 
-extern "C" EMEI_API int emei_evaluate_sequences(emei_env* h, int32_t horizon, int32_t n_candidates, const void* actions, int action_dtype,
-                                                double discount, const double* start_state, double* return_out, int32_t* length_out,
-                                                float* final_obs_out, void* stream) {
-    const char* fn = "emei_evaluate_sequences";
+static int evaluate_sequences(const char* fn, bool with_value, emei_env* h, int32_t horizon, int32_t n_candidates, const void* actions,
+                              int action_dtype, double discount, const emei_policy_deep* value, const double* start_state,
+                              double* return_out, int32_t* length_out, float* final_obs_out, void* stream) {
     if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
+    if (with_value)
+        if (int rc = check_plan_value(fn, h, value)) return rc;
     if (!h) return fail(EMEI_ERR_INVALID, "%s: null handle", fn);
     if (!actions || !return_out || !length_out) return fail(EMEI_ERR_INVALID, "%s: null argument", fn);
     if (int rc = check_plan_lanes(fn, h, n_candidates)) return rc;
     if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
     EMEI_ON_DEVICE(h, fn);
     if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    LaunchCommon c = plan_call(PLAN_GIVEN, start_state, horizon, n_candidates, discount);
+    LaunchCommon c = plan_call(PLAN_GIVEN, start_state, horizon, n_candidates, discount, value);
     c.plan.return_out = return_out, c.plan.length_out = length_out;
     c.actions = actions, c.obs_out = final_obs_out;
     return launched(fn, launch(h, c, stream, action_dtype));
+}
+extern "C" EMEI_API int emei_evaluate_sequences(emei_env* h, int32_t horizon, int32_t n_candidates, const void* actions, int action_dtype,
+                                                double discount, const double* start_state, double* return_out, int32_t* length_out,
+                                                float* final_obs_out, void* stream) {
+    return evaluate_sequences("emei_evaluate_sequences", false, h, horizon, n_candidates, actions, action_dtype, discount, nullptr,
+                              start_state, return_out, length_out, final_obs_out, stream);
+}
+extern "C" EMEI_API int emei_evaluate_sequences_value(emei_env* h, int32_t horizon, int32_t n_candidates, const void* actions,
+                                                      int action_dtype, double discount, const emei_policy_deep* value,
+                                                      const double* start_state, double* return_out, int32_t* length_out,
+                                                      float* final_obs_out, void* stream) {
+    return evaluate_sequences("emei_evaluate_sequences_value", true, h, horizon, n_candidates, actions, action_dtype, discount, value,
+                              start_state, return_out, length_out, final_obs_out, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -819,25 +849,45 @@ extern "C" EMEI_API int emei_sample_candidates(emei_env* h, int32_t horizon, int
     return launched(fn, rc);
 }
 
-extern "C" EMEI_API int emei_plan_shooting(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal,
-                                           double sigma, double discount, const double* start_state, void* workspace,
-                                           void* best_action_out, int action_dtype, void* best_sequence_out, double* best_return_out,
-                                           int32_t* best_index_out, int32_t* best_length_out, void* stream) {
-    const char* fn = "emei_plan_shooting";
+// with_value: the value plan kernels keep every return (one instantiation serves the three planners), so the workspace is
+// emei_plan_value_workspace_bytes' and the returns lie behind the partials as emei_plan_mppi's do
+static int plan_shooting(const char* fn, bool with_value, emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed,
+                         const float* nominal, double sigma, double discount, const emei_policy_deep* value, const double* start_state,
+                         void* workspace, void* best_action_out, int action_dtype, void* best_sequence_out, double* best_return_out,
+                         int32_t* best_index_out, int32_t* best_length_out, void* stream) {
     if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
+    if (with_value)
+        if (int rc = check_plan_value(fn, h, value)) return rc;
     if (int rc = check_candidates(fn, h, horizon, n_candidates, nominal != nullptr, sigma)) return rc;
     if (check_action_dtype(h, action_dtype) != EMEI_OK) return EMEI_ERR_INVALID;
     if (!workspace || !best_action_out || !best_return_out || !best_index_out) return fail(EMEI_ERR_INVALID, "%s: null argument", fn);
     EMEI_ON_DEVICE(h, fn);
     if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    LaunchCommon c = plan_call(PLAN_DRAWN, start_state, horizon, n_candidates, discount);
+    LaunchCommon c = plan_call(with_value ? PLAN_DRAWN_KEEP : PLAN_DRAWN, start_state, horizon, n_candidates, discount, value);
     PlanLaunch& p = c.plan;
     p.cand = candidate_spec(h, seed, nominal, sigma), p.partials = workspace;
+    if (with_value) p.return_out = plan_returns(h, n_candidates, workspace);
     int rc = launch(h, c, stream);
     if (rc == EMEI_OK)
         rc = launch_plan_finish(workspace, p.cand, h->cfg.n_envs, n_candidates, horizon, h->act_dim, best_action_out, action_dtype,
                                 best_sequence_out, best_return_out, best_index_out, best_length_out, (hipStream_t)stream);
     return launched(fn, rc);
+}
+extern "C" EMEI_API int emei_plan_shooting(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal,
+                                           double sigma, double discount, const double* start_state, void* workspace,
+                                           void* best_action_out, int action_dtype, void* best_sequence_out, double* best_return_out,
+                                           int32_t* best_index_out, int32_t* best_length_out, void* stream) {
+    return plan_shooting("emei_plan_shooting", false, h, horizon, n_candidates, seed, nominal, sigma, discount, nullptr, start_state,
+                         workspace, best_action_out, action_dtype, best_sequence_out, best_return_out, best_index_out, best_length_out,
+                         stream);
+}
+extern "C" EMEI_API int emei_plan_shooting_value(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal,
+                                                 double sigma, double discount, const emei_policy_deep* value, const double* start_state,
+                                                 void* workspace, void* best_action_out, int action_dtype, void* best_sequence_out,
+                                                 double* best_return_out, int32_t* best_index_out, int32_t* best_length_out, void* stream) {
+    return plan_shooting("emei_plan_shooting_value", true, h, horizon, n_candidates, seed, nominal, sigma, discount, value, start_state,
+                         workspace, best_action_out, action_dtype, best_sequence_out, best_return_out, best_index_out, best_length_out,
+                         stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -851,19 +901,20 @@ extern "C" EMEI_API int64_t emei_plan_mppi_workspace_bytes(int64_t n_envs, int32
     return keep_workspace_bytes("emei_plan_mppi_workspace_bytes", n_envs, n_candidates);
 }
 
-extern "C" EMEI_API int emei_plan_mppi(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal, double sigma,
-                                       double discount, double temperature, const double* start_state, void* workspace,
-                                       float* nominal_out, double* best_return_out, int32_t* best_index_out, double* ess_out,
-                                       void* stream) {
-    const char* fn = "emei_plan_mppi";
+static int plan_mppi(const char* fn, bool with_value, emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed,
+                     const float* nominal, double sigma, double discount, const emei_policy_deep* value, double temperature,
+                     const double* start_state, void* workspace, float* nominal_out, double* best_return_out, int32_t* best_index_out,
+                     double* ess_out, void* stream) {
     if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
     if (int rc = check_temperature(fn, temperature)) return rc;
+    if (with_value)
+        if (int rc = check_plan_value(fn, h, value)) return rc;
     if (int rc = check_candidates(fn, h, horizon, n_candidates, nominal != nullptr, sigma)) return rc;
     if (!workspace) return fail(EMEI_ERR_INVALID, "%s: null workspace", fn);
     if (!nominal_out) return fail(EMEI_ERR_INVALID, "%s: null nominal_out", fn);
     EMEI_ON_DEVICE(h, fn);
     if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    LaunchCommon c = plan_call(PLAN_DRAWN_KEEP, start_state, horizon, n_candidates, discount);
+    LaunchCommon c = plan_call(PLAN_DRAWN_KEEP, start_state, horizon, n_candidates, discount, value);
     PlanLaunch& p = c.plan;
     p.cand = candidate_spec(h, seed, nominal, sigma), p.partials = workspace, p.return_out = plan_returns(h, n_candidates, workspace);
     int rc = launch(h, c, stream);
@@ -871,6 +922,20 @@ extern "C" EMEI_API int emei_plan_mppi(emei_env* h, int32_t horizon, int32_t n_c
         rc = launch_plan_mppi_finish(workspace, p.return_out, p.cand, h->cfg.n_envs, n_candidates, horizon, h->act_dim, temperature, nominal_out,
                                      best_return_out, best_index_out, ess_out, (hipStream_t)stream);
     return launched(fn, rc);
+}
+extern "C" EMEI_API int emei_plan_mppi(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal, double sigma,
+                                       double discount, double temperature, const double* start_state, void* workspace,
+                                       float* nominal_out, double* best_return_out, int32_t* best_index_out, double* ess_out,
+                                       void* stream) {
+    return plan_mppi("emei_plan_mppi", false, h, horizon, n_candidates, seed, nominal, sigma, discount, nullptr, temperature, start_state,
+                     workspace, nominal_out, best_return_out, best_index_out, ess_out, stream);
+}
+extern "C" EMEI_API int emei_plan_mppi_value(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal,
+                                             double sigma, double discount, const emei_policy_deep* value, double temperature,
+                                             const double* start_state, void* workspace, float* nominal_out, double* best_return_out,
+                                             int32_t* best_index_out, double* ess_out, void* stream) {
+    return plan_mppi("emei_plan_mppi_value", true, h, horizon, n_candidates, seed, nominal, sigma, discount, value, temperature,
+                     start_state, workspace, nominal_out, best_return_out, best_index_out, ess_out, stream);
 }
 
 // emei_sample_candidates_sigma: emei_sample_candidates' Gaussian mode with the sigma read per entry (there is no scalar to check)
@@ -895,15 +960,16 @@ extern "C" EMEI_API int64_t emei_plan_cem_workspace_bytes(int64_t n_envs, int32_
     return keep_workspace_bytes("emei_plan_cem_workspace_bytes", n_envs, n_candidates);
 }
 
-extern "C" EMEI_API int emei_plan_cem(emei_env* h, int32_t horizon, int32_t n_candidates, int32_t n_elites, uint64_t seed,
-                                      const float* nominal, double sigma, const float* sigma_map, double discount,
-                                      const double* start_state, void* workspace, float* mean_out, float* std_out,
-                                      double* best_return_out, int32_t* best_index_out, double* elite_return_out, void* stream) {
-    const char* fn = "emei_plan_cem";
+static int plan_cem(const char* fn, bool with_value, emei_env* h, int32_t horizon, int32_t n_candidates, int32_t n_elites, uint64_t seed,
+                    const float* nominal, double sigma, const float* sigma_map, double discount, const emei_policy_deep* value,
+                    const double* start_state, void* workspace, float* mean_out, float* std_out, double* best_return_out,
+                    int32_t* best_index_out, double* elite_return_out, void* stream) {
     // n_elites is refused after horizon and n_candidates, before discount
     if (horizon >= 1 && n_candidates >= 1 && (n_elites < 1 || n_elites > n_candidates))
         return fail(EMEI_ERR_INVALID, "%s: n_elites=%d is outside [1, n_candidates=%d]", fn, n_elites, n_candidates);
     if (int rc = check_plan_scalars(fn, horizon, n_candidates, discount)) return rc;
+    if (with_value)
+        if (int rc = check_plan_value(fn, h, value)) return rc;
     // with a sigma_map the scalar is ignored
     if (int rc = check_candidates(fn, h, horizon, n_candidates, nominal && !sigma_map, sigma)) return rc;
     if (sigma_map && !nominal) return fail(EMEI_ERR_INVALID, "%s: a sigma_map needs a nominal", fn);
@@ -913,7 +979,7 @@ extern "C" EMEI_API int emei_plan_cem(emei_env* h, int32_t horizon, int32_t n_ca
     if (!mean_out) return fail(EMEI_ERR_INVALID, "%s: null mean_out", fn);
     EMEI_ON_DEVICE(h, fn);
     if (!start_state && !h->has_state) return fail(EMEI_ERR_STATE, "%s: call reset before using the state", fn);
-    LaunchCommon c = plan_call(PLAN_DRAWN_KEEP, start_state, horizon, n_candidates, discount);
+    LaunchCommon c = plan_call(PLAN_DRAWN_KEEP, start_state, horizon, n_candidates, discount, value);
     PlanLaunch& p = c.plan;
     p.cand = candidate_spec(h, seed, nominal, sigma), p.sigma_map = sigma_map;
     p.partials = workspace, p.return_out = plan_returns(h, n_candidates, workspace);
@@ -922,6 +988,25 @@ extern "C" EMEI_API int emei_plan_cem(emei_env* h, int32_t horizon, int32_t n_ca
         rc = launch_plan_cem_finish(workspace, p.return_out, p.cand, sigma_map, h->cfg.n_envs, n_candidates, n_elites, horizon, h->act_dim, mean_out,
                                     std_out, best_return_out, best_index_out, elite_return_out, (hipStream_t)stream);
     return launched(fn, rc);
+}
+extern "C" EMEI_API int emei_plan_cem(emei_env* h, int32_t horizon, int32_t n_candidates, int32_t n_elites, uint64_t seed,
+                                      const float* nominal, double sigma, const float* sigma_map, double discount,
+                                      const double* start_state, void* workspace, float* mean_out, float* std_out,
+                                      double* best_return_out, int32_t* best_index_out, double* elite_return_out, void* stream) {
+    return plan_cem("emei_plan_cem", false, h, horizon, n_candidates, n_elites, seed, nominal, sigma, sigma_map, discount, nullptr,
+                    start_state, workspace, mean_out, std_out, best_return_out, best_index_out, elite_return_out, stream);
+}
+extern "C" EMEI_API int emei_plan_cem_value(emei_env* h, int32_t horizon, int32_t n_candidates, int32_t n_elites, uint64_t seed,
+                                            const float* nominal, double sigma, const float* sigma_map, double discount,
+                                            const emei_policy_deep* value, const double* start_state, void* workspace, float* mean_out,
+                                            float* std_out, double* best_return_out, int32_t* best_index_out, double* elite_return_out,
+                                            void* stream) {
+    return plan_cem("emei_plan_cem_value", true, h, horizon, n_candidates, n_elites, seed, nominal, sigma, sigma_map, discount, value,
+                    start_state, workspace, mean_out, std_out, best_return_out, best_index_out, elite_return_out, stream);
+}
+// one size for the three value planners: the shooting variant keeps every return as well
+extern "C" EMEI_API int64_t emei_plan_value_workspace_bytes(int64_t n_envs, int32_t n_candidates) {
+    return keep_workspace_bytes("emei_plan_value_workspace_bytes", n_envs, n_candidates);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1353,7 +1438,7 @@ extern "C" EMEI_API int emei_mpc_policy(emei_env* h, int32_t n_steps, int32_t ho
 // (two hidden layers), on kernels of their own (pend_policy_*_deep_kernel / body_policy_*_deep_kernel).  The refusals mirror
 // check_policy_struct / check_policy_weights.
 // with_out_mode false: the terminal value network of emei_plan_policy_deep, whose out_mode is ignored
-static int check_policy_deep_struct(const char* fn, const char* arg, const emei_policy_deep* policy, bool with_out_mode = true) {
+static int check_policy_deep_struct(const char* fn, const char* arg, const emei_policy_deep* policy, bool with_out_mode) {
     if (!policy) return fail(EMEI_ERR_INVALID, "%s: null %s", fn, arg);
     if (policy->struct_size != sizeof(emei_policy_deep))
         return fail(EMEI_ERR_INVALID, "%s: %s.struct_size=%u != sizeof(emei_policy_deep)=%zu", fn, arg, policy->struct_size,

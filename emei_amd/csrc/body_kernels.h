@@ -1550,6 +1550,108 @@ __global__ void __launch_bounds__(kWave)
     if (active) ret_out[j] = ret;
 }
 
+// emei_evaluate_sequences_value / emei_plan_shooting_value / emei_plan_mppi_value / emei_plan_cem_value (the normative text:
+// include/emei_hip.h) for the bodies: body_plan_kernel's loop — the same controls, substeps and outputs, the padding lanes parked — as
+// ONE-WAVE blocks with body_policy_plan_deep_kernel's static LDS (the trig table, the body's scratch at stride kWave); the block's
+// dynamic LDS is the wave's h1 tile of the value network.  Lane l of block b holds candidate j = 64 b + l: the waves (the cheetah's
+// lane lending) and plan_reduce_wave's slots are those of the 256-thread kernel.  DRAWN here is body_plan_kernel's DRAWN + KEEP.
+// Terminal value, as body_policy_plan_deep_kernel's: `live` also falls at t == horizon - 1, so the terminal bits have the flag
+// `noterm` of their own; `o` lives across the loop and holds x_H whenever some lane never terminated; i divides in 32 bits and the
+// score is kept with selects (body_policy_plan_kernel says why).  Every active lane's return leaves after the bootstrap; the given
+// candidates' length and final observation leave at their last counted step, as body_plan_kernel's.
+template <class Body, bool RK4, bool DRAWN = false, class Spec = CandidateSpec>
+__global__ void __launch_bounds__(kWave)
+    body_plan_value_kernel(const typename Body::real* state, const double* start_rows, const float* actions, int64_t n_envs,
+                           int32_t n_cand, int32_t horizon, double discount, int freq_rate, int semi, typename Body::Model m,
+                           const SinCosEntry* trig_tab, unsigned long long* cap_hits, const PolicyDeepArgs val, double* ret_out,
+                           int32_t* len_out, float* final_obs, Spec sp, PlanPartial* partials) {
+    using R = typename Body::real;
+    constexpr int NS = Body::NS, NO = Body::NO, NA = Body::NA;
+    extern __shared__ __attribute__((aligned(16))) float4 deep_h1_s[];
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table<kWave>(trig_s, trig_tab);  // every thread reaches the barrier
+    TrigCtx trig;
+    trig.tab = trig_s;
+    if constexpr (Body::kScratchPerLane > 0) {
+        __shared__ __attribute__((aligned(16))) R scratch_s[Body::kScratchPerLane * kWave];
+        trig.scratch = scratch_s;
+    }
+    trig.scratch_stride = kWave;
+    trig.cap_hits = cap_hits;
+    const int lane = threadIdx.x;
+    const int64_t nk = n_envs * n_cand;
+    const int64_t j = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const bool active = j < nk;
+    // no divergent branch around the loads, and a 32-bit division (nk <= 2^31 - 1, abi.hip): see body_policy_plan_kernel
+    const uint32_t ju = active ? (uint32_t)j : 0u, iu = ju / (uint32_t)n_cand;
+    const int64_t i = iu;
+    const uint32_t kc = ju - iu * (uint32_t)n_cand;
+    R s[NS], parked[NS];
+    if (start_rows) {  // wave-uniform; the caller's float64 rows are narrowed as emei_set_state narrows them (util_kernels.hip)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = (R)start_rows[i * NS + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = state[(int64_t)k * n_envs + i];
+    }
+    Body::park(parked);  // as body_rollout_kernel's padding lanes
+#pragma unroll
+    for (int k = 0; k < NS; ++k) s[k] = active ? s[k] : parked[k];
+    double ret = 0.0, g = 1.0;
+    int32_t len = 0;  // steps counted so far (ret and len stop changing with the lane's last counted step)
+    bool live = active, noterm = active;
+    float o[NO];  // what each step emits: x_H after the last one, for the value
+    for (int t = 0; t < horizon; ++t) {
+        R ctrl[NA];  // padding lanes: zero, as the rollout's staging gives them
+        if constexpr (DRAWN) {
+            CandidateWords cw(sp.seed, sp.env_offset + (uint64_t)i, kc);
+#pragma unroll
+            for (int k = 0; k < NA; ++k) {
+                const float a = draw_action(cw, sp, n_envs, i, t, k, NA);
+                ctrl[k] = active ? (R)a : R(0);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < NA; ++k) ctrl[k] = active ? (R)actions[((int64_t)t * nk + j) * NA + k] : R(0);
+        }
+        R pre[NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) pre[k] = s[k];
+        typename Body::Warm warm{};
+        for (int k = 0; k < freq_rate; ++k) body_substep<Body, RK4>(s, ctrl, m, semi != 0, trig, warm);
+        R rew;
+        bool term;
+        Body::outputs(s, pre, ctrl, m, freq_rate, o, rew, term, trig);
+        const double counted = ret + g * (double)(float)rew, g_next = g * discount;
+        ret = live ? counted : ret;
+        g = live ? g_next : g;
+        len = live ? t + 1 : len;
+        const bool leaves = live & (term | (t == horizon - 1));  // the lane's last counted step
+        noterm = noterm & !term;
+        live = live & !leaves;
+        if constexpr (!DRAWN) {
+            if (leaves) {
+                len_out[j] = t + 1;
+                if (final_obs) {
+#pragma unroll
+                    for (int k = 0; k < NO; ++k) final_obs[j * NO + k] = o[k];
+                }
+            }
+        }
+        if (__ballot(live) == 0ull) break;  // wave-uniform
+    }
+    if (__ballot(noterm) != 0ull) {  // wave-uniform: some lane never terminated, so the loop ran to x_H
+        const PolicyNoiseArgs none{};  // val.noisy == 0: never read
+        float v[1];
+        policy_eval_deep_t<NO, 1, false, true>(val, none, 0, 0, o, v, deep_h1_s, lane);
+        const double tail = g * (double)v[0];  // rounded to float64, then added
+        const double boot = ret + tail;
+        ret = noterm ? boot : ret;
+    }
+    if constexpr (DRAWN) plan_reduce_wave(j, nk, i, n_cand, ret, len, partials);
+    if (active) ret_out[j] = ret;
+}
+
 // the one launch of body_plan_kernel: DRAWN kernels read no actions and write no lengths or final observations, and only KEEP
 // gives them a return_out; one lane per candidate, n * n_candidates < 2^31 (checked in abi.hip)
 template <class Body, bool RK4, bool DRAWN, bool KEEP, class Spec>
@@ -1562,6 +1664,22 @@ static void launch_body_plan(const BodyLaunch& L, const typename Body::Model& m,
                        L.n_steps, P.discount, L.freq_rate, semi, m, (const SinCosEntry*)L.trig, L.cap_hits,
                        DRAWN && !KEEP ? nullptr : P.return_out, DRAWN ? nullptr : P.length_out, DRAWN ? nullptr : L.obs_out, sp,
                        DRAWN ? (PlanPartial*)P.partials : nullptr);
+}
+
+// the one launch of body_plan_value_kernel: launch_body_plan's arguments on one-wave blocks with the value network's h1 tile; the
+// drawn kernels always keep their returns
+template <class Body, bool RK4, bool DRAWN, class Spec>
+static int launch_body_plan_value(const BodyLaunch& L, const typename Body::Model& m, const Spec& sp) {
+    const PlanLaunch& P = L.plan;
+    if (int rc = policy_deep_lds_opt_in<body_plan_value_kernel<Body, RK4, DRAWN, Spec>>()) return rc;
+    const dim3 pgrid((unsigned)((L.n * P.n_candidates + kWave - 1) / kWave));
+    const int semi = RK4 ? 0 : (int)(L.integrator == EMEI_INTEG_SEMI_IMPLICIT);
+    hipLaunchKernelGGL((body_plan_value_kernel<Body, RK4, DRAWN, Spec>), pgrid, dim3(kWave), policy_deep_tile_bytes(L.policy_value.hidden1),
+                       L.stream, (const typename Body::real*)L.state, P.start_rows, DRAWN ? nullptr : (const float*)L.actions, L.n,
+                       P.n_candidates, L.n_steps, P.discount, L.freq_rate, semi, m, (const SinCosEntry*)L.trig, L.cap_hits, L.policy_value,
+                       P.return_out, DRAWN ? nullptr : P.length_out, DRAWN ? nullptr : L.obs_out, sp,
+                       DRAWN ? (PlanPartial*)P.partials : nullptr);
+    return EMEI_OK;
 }
 
 }  // namespace emei
@@ -1861,6 +1979,23 @@ static int launch_body(const BodyLaunch& L) {
             } else {
                 return EMEI_ERR_UNSUPPORTED;  // abi.hip refuses these handles with a message of its own
             }
+        case OP_PLAN_VALUE: {  // OP_PLAN's dispatch over body_plan_value_kernel; PLAN_DRAWN goes to the KEEP instantiation
+            const PlanLaunch& P = L.plan;
+            if (!L.policy_value.w1 || !P.return_out) return EMEI_ERR_INVALID;
+            if (P.mode != PLAN_GIVEN && !P.partials) return EMEI_ERR_INVALID;
+            const bool rk4 = L.integrator == EMEI_INTEG_RK4;
+            int rc;
+            if (P.mode == PLAN_GIVEN) {
+                rc = rk4 ? launch_body_plan_value<Body, true, false>(L, m, P.cand) : launch_body_plan_value<Body, false, false>(L, m, P.cand);
+            } else if (P.sigma_map) {  // emei_plan_cem_value with a sigma per entry
+                const CandidateSpecMap spm(P.cand, P.sigma_map);
+                rc = rk4 ? launch_body_plan_value<Body, true, true>(L, m, spm) : launch_body_plan_value<Body, false, true>(L, m, spm);
+            } else {
+                rc = rk4 ? launch_body_plan_value<Body, true, true>(L, m, P.cand) : launch_body_plan_value<Body, false, true>(L, m, P.cand);
+            }
+            if (rc) return rc;
+            break;
+        }
         default: return EMEI_ERR_INVALID;
     }
     return hipGetLastError() == hipSuccess ? EMEI_OK : EMEI_ERR_HIP;

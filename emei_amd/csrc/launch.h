@@ -22,6 +22,10 @@ enum LaunchOp {
     // emei_evaluate_sequences and the first launch of emei_plan_shooting / _mppi / _cem: `plan` (PlanMode), actions (PLAN_GIVEN),
     // obs_out = final_obs [n * K, NO] or null
     OP_PLAN,
+    // emei_evaluate_sequences_value / emei_plan_shooting_value / _mppi_value / _cem_value: OP_PLAN's fields with the terminal value
+    // network in `policy_value` (w1 non-null; out_mode, lo, hi and noisy unused) on the one-wave plan kernels; every mode keeps its
+    // returns in plan.return_out (PLAN_DRAWN included)
+    OP_PLAN_VALUE,
     // emei_mpc_mppi: n_steps control steps of MPPI with plan.n_candidates candidates over mpc.horizon steps under plan.discount;
     // plan.cand carries the call's seed, sigma and the ctrlrange (its nominal is unused: the kernel keeps mpc.nominal in LDS), `seed`
     // the handle's reset key; plan.return_out = the workspace [n * K]; mpc.actions_out, obs_out / reward_out / done_out and flags as

@@ -1147,6 +1147,96 @@ __global__ void __launch_bounds__(kWave)
     plan_reduce_wave(j, nk, i, n_cand, ret, len, partials);
 }
 
+// emei_evaluate_sequences_value / emei_plan_shooting_value / emei_plan_mppi_value / emei_plan_cem_value (the normative text:
+// include/emei_hip.h): pend_plan_kernel's loop, expression for expression, as ONE-WAVE blocks whose dynamic LDS is the wave's h1 tile
+// of the value network — lane l of block b holds candidate j = 64 b + l, so the waves and plan_reduce_wave's slots are those of the
+// 256-thread kernel.  DRAWN here is pend_plan_kernel's DRAWN + KEEP (the shooting call keeps its returns too: one instantiation).
+// Terminal value: `live` falls only at a terminal bit, so after the loop it says "never terminated"; the loop leaves early only once
+// no lane is live, and a live lane's `fo`, refreshed at every step it counted, is x_H — the wave then evaluates `val` on the rows it
+// holds, raw (no output clause), and the live lanes take ret + g_H * (double)v by a select, as pend_policy_plan_deep_kernel's do.
+// len and final_obs are what pend_plan_kernel leaves.
+template <class Env, typename ActT, bool DRAWN = false, class Spec = CandidateSpec>
+__global__ void __launch_bounds__(kWave)
+    pend_plan_value_kernel(const typename Env::real* state, const double* start_rows, const ActT* actions, int64_t n_envs, int32_t n_cand,
+                           int32_t horizon, double discount, int freq_rate, typename Env::Params p, const SinCosEntry* trig,
+                           const PolicyDeepArgs val, double* ret_out, int32_t* len_out, float4* final_obs, Spec sp, PlanPartial* partials) {
+    using R = typename Env::real;
+    extern __shared__ __attribute__((aligned(16))) float4 deep_h1_s[];
+    __shared__ SinCosEntry trig_s[kTrigTableSize];
+    stage_trig_table<kWave>(trig_s, trig, Env::trig_rot_c(), Env::trig_rot_s());
+    const int64_t nk = n_envs * n_cand;
+    const int64_t j = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    if (j >= nk) return;
+    const int64_t i = j / n_cand;
+    R s[4];
+    // start state: the handle's SoA, or the caller's float64 rows narrowed as emei_set_state narrows them (util_kernels.hip)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = start_rows ? (R)start_rows[i * 4 + k] : state[k * n_envs + i];
+    typename Env::Carry c;
+    trig_ctx_init(c.trig, trig_s);
+    Env::prime(s, c, p);
+
+    double ret = 0.0, g = 1.0;
+    int32_t len = horizon;
+    bool live = true;
+    float4 fo = make_float4(0.f, 0.f, 0.f, 0.f);
+    // actions a chunk ahead of their use, as in pend_rollout_kernel (steps past the horizon clamped, not branched around)
+    constexpr int kChunk = 8;
+    const int last = horizon - 1;
+    ActT cur[kChunk], nxt[kChunk];
+    CandidateWordsT<true> cw(sp.seed, sp.env_offset + (uint64_t)i, (uint32_t)(j - i * n_cand));
+    if constexpr (!DRAWN) {
+#pragma unroll
+        for (int u = 0; u < kChunk; ++u) cur[u] = (actions + (int64_t)min(u, last) * nk)[j];
+    }
+    bool any_live = true;
+    for (int t0 = 0; t0 < horizon && any_live; t0 += kChunk) {
+        if constexpr (!DRAWN) {
+#pragma unroll
+            for (int u = 0; u < kChunk; ++u) nxt[u] = (actions + (int64_t)min(t0 + kChunk + u, last) * nk)[j];
+        }
+#pragma unroll
+        for (int u = 0; u < kChunk; ++u) {
+            const int t = t0 + u;
+            if (t >= horizon) break;
+            R o[4], rew;
+            bool term;
+            if constexpr (DRAWN) cur[u] = (ActT)draw_action(cw, sp, n_envs, i, t, 0, Env::kDiscrete ? 0 : Env::kActDim);
+            Env::step(s, c, Env::decode_t(cur[u]), p, freq_rate, o, rew, term);
+            if (live) {
+                ret = ret + g * (double)(float)rew;
+                g = g * discount;
+                fo = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
+                if (term) live = false, len = t + 1;
+            }
+            if (__ballot(live) == 0ull) {  // wave-uniform
+                any_live = false;
+                break;
+            }
+        }
+        if constexpr (!DRAWN) {
+#pragma unroll
+            for (int u = 0; u < kChunk; ++u) cur[u] = nxt[u];
+        }
+    }
+    if (__ballot(live) != 0ull) {  // wave-uniform: some lane never terminated, so the loop ran all `horizon` steps
+        const float x[4] = {fo.x, fo.y, fo.z, fo.w};  // a live lane's: x_H
+        const PolicyNoiseArgs none{};                 // val.noisy == 0: never read
+        float v[1];
+        policy_eval_deep_t<4, 1, false, true>(val, none, 0, 0, x, v, deep_h1_s, (int)threadIdx.x);
+        const double tail = g * (double)v[0];  // rounded to float64, then added
+        const double boot = ret + tail;
+        ret = live ? boot : ret;
+    }
+    ret_out[j] = ret;  // j < nk here
+    if constexpr (DRAWN) {
+        plan_reduce_wave(j, nk, i, n_cand, ret, len, partials);
+    } else {
+        len_out[j] = len;
+        if (final_obs) final_obs[j] = fo;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // emei_mpc_mppi: receding-horizon MPPI control episodes in ONE launch (the normative text: include/emei_hip.h).
 // The draws read the nominal from the wave's LDS slice: CandidateSpecLds (emei_device.h, shared with the body kernels' controllers).
@@ -1915,6 +2005,20 @@ static void launch_pend_plan(const PendLaunch& L, const RolloutArgs<Env>& a, con
                        DRAWN ? (PlanPartial*)P.partials : nullptr);
 }
 
+// the one launch of pend_plan_value_kernel: launch_pend_plan's arguments on one-wave blocks with the value network's h1 tile; the
+// drawn kernels always keep their returns
+template <class Env, class ActT, bool DRAWN, class Spec>
+static int launch_pend_plan_value(const PendLaunch& L, const RolloutArgs<Env>& a, const Spec& sp) {
+    const PlanLaunch& P = L.plan;
+    if (int rc = policy_deep_lds_opt_in<pend_plan_value_kernel<Env, ActT, DRAWN, Spec>>()) return rc;
+    const dim3 pgrid((unsigned)((L.n * P.n_candidates + kWave - 1) / kWave));
+    hipLaunchKernelGGL((pend_plan_value_kernel<Env, ActT, DRAWN, Spec>), pgrid, dim3(kWave), policy_deep_tile_bytes(L.policy_value.hidden1),
+                       L.stream, (const typename Env::real*)L.state, P.start_rows, DRAWN ? nullptr : (const ActT*)L.actions, L.n,
+                       P.n_candidates, L.n_steps, P.discount, L.freq_rate, a.p, a.trig, L.policy_value, P.return_out,
+                       DRAWN ? nullptr : P.length_out, DRAWN ? nullptr : (float4*)L.obs_out, sp, DRAWN ? (PlanPartial*)P.partials : nullptr);
+    return EMEI_OK;
+}
+
 // host-side dispatch over (env id, precision)
 // every launch of one Env type (one translation unit instantiates exactly one Env: pendulum_tu.hip)
 template <class Env>
@@ -2136,6 +2240,34 @@ static int launch_env(const PendLaunch& L) {
                                policy_deep_tile_bytes(L.policy_deep.hidden1), L.stream, (const R*)L.state, P.start_rows, L.n, env_waves,
                                L.n_steps, P.discount, L.freq_rate, a.p, a.trig, L.policy_deep, P.return_out, P.length_out,
                                (float4*)L.obs_out);
+            break;
+        }
+        case OP_PLAN_VALUE: {  // OP_PLAN's dispatch over pend_plan_value_kernel; PLAN_DRAWN goes to the KEEP instantiation
+            const PlanLaunch& P = L.plan;
+            if (!L.policy_value.w1 || !P.return_out) return EMEI_ERR_INVALID;
+            int rc;
+            if (P.mode == PLAN_GIVEN) {
+                const CandidateSpec none{};
+                if constexpr (Env::kDiscrete) {
+                    if (L.action_dtype == EMEI_ACT_U8) rc = launch_pend_plan_value<Env, uint8_t, false>(L, a, none);
+                    else if (L.action_dtype == EMEI_ACT_I32) rc = launch_pend_plan_value<Env, int32_t, false>(L, a, none);
+                    else if (L.action_dtype == EMEI_ACT_I64) rc = launch_pend_plan_value<Env, int64_t, false>(L, a, none);
+                    else return EMEI_ERR_INVALID;
+                } else {
+                    if (L.action_dtype != EMEI_ACT_F32) return EMEI_ERR_INVALID;
+                    rc = launch_pend_plan_value<Env, float, false>(L, a, none);
+                }
+            } else {
+                using DrawT = typename std::conditional<Env::kDiscrete, int, float>::type;
+                if (!P.partials) return EMEI_ERR_INVALID;
+                if (P.sigma_map) {  // emei_plan_cem_value with a sigma per entry: continuous envs
+                    if constexpr (!Env::kDiscrete) rc = launch_pend_plan_value<Env, DrawT, true>(L, a, CandidateSpecMap(P.cand, P.sigma_map));
+                    else return EMEI_ERR_INVALID;
+                } else {
+                    rc = launch_pend_plan_value<Env, DrawT, true>(L, a, P.cand);
+                }
+            }
+            if (rc) return rc;
             break;
         }
         default: return EMEI_ERR_INVALID;

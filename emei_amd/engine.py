@@ -401,12 +401,16 @@ class Engine:
         return act, obs, rew, done
 
     @_on_device
-    def evaluate_sequences(self, actions, discount=1.0, start_state=None, final_obs=False):
+    def evaluate_sequences(self, actions, discount=1.0, start_state=None, final_obs=False, value=None):
         """Score K candidate action sequences per env from the current state (or `start_state`) in one launch, for planners
         (emei_evaluate_sequences).  The handle's state, counters and snapshot are left as they are.
         actions [H, N, K(, act_dim)] on the engine's device; start_state None or [N, state_dim] (float64 rows of set_state).
         -> (returns float64 [N, K]: sum of discount^t * reward_t up to the first terminal step, included; lengths int32 [N, K]:
-        that step + 1, or H; [final_obs float32 [N, K, obs_dim]: the observation of the last counted step])"""
+        that step + 1, or H; [final_obs float32 [N, K, obs_dim]: the observation of the last counted step])
+        value= (a policy.DeepValueFunction) adds a TERMINAL VALUE (emei_evaluate_sequences_value): every candidate that set no terminal
+        bit in its H steps gets discount^H * float64(V(final obs)) on top of its return; one that terminated gets nothing, at the last
+        step included (its length is H too).  Lengths and final_obs do not change."""
+        vs = self._plan_value(value, "evaluate_sequences")
         if not isinstance(actions, torch.Tensor) or actions.dim() < 3:
             raise ValueError("actions must be a tensor [H, N, K(, act_dim)] on the engine's device")
         H, K = int(actions.shape[0]), int(actions.shape[2])
@@ -421,8 +425,12 @@ class Engine:
         ret = torch.empty((self.n_envs, K), dtype=torch.float64, device=self.device)
         length = torch.empty((self.n_envs, K), dtype=torch.int32, device=self.device)
         fo = torch.empty((self.n_envs, K, self.obs_dim), dtype=torch.float32, device=self.device) if final_obs else None
-        L.check(L.lib().emei_evaluate_sequences(self._h, H, K, _ptr(flat), dt, float(discount), _ptr(st), _ptr(ret), _ptr(length),
-                                                _ptr(fo), _stream()))
+        if vs is None:
+            L.check(L.lib().emei_evaluate_sequences(self._h, H, K, _ptr(flat), dt, float(discount), _ptr(st), _ptr(ret), _ptr(length),
+                                                    _ptr(fo), _stream()))
+        else:
+            L.check(L.lib().emei_evaluate_sequences_value(self._h, H, K, _ptr(flat), dt, float(discount), C.byref(vs), _ptr(st), _ptr(ret),
+                                                          _ptr(length), _ptr(fo), _stream()))
         return (ret, length, fo) if final_obs else (ret, length)
 
     @_on_device
@@ -454,6 +462,17 @@ class Engine:
         entry = L.lib().emei_evaluate_policies_deep if isinstance(pop, DeepPolicyPopulation) else L.lib().emei_evaluate_policies
         L.check(entry(self._h, H, P, C.byref(ps), float(discount), _ptr(st), _ptr(ret), _ptr(length), _ptr(fo), _stream()))
         return (ret, length, fo) if final_obs else (ret, length)
+
+    def _plan_value(self, value, who):
+        """the checked terminal value of the open-loop plan calls (evaluate_sequences, plan_shooting, plan_mppi, plan_cem): None, or
+        struct emei_policy_deep over a policy.DeepValueFunction bound to this engine as plan_policy binds it.  Needs no handle."""
+        if value is None:
+            return None
+        from .policy import DeepValueFunction
+
+        if not isinstance(value, DeepValueFunction):
+            raise TypeError(f"{who} takes an emei_amd.DeepValueFunction as value= (the terminal value network), or None")
+        return value.bind(self).struct()
 
     def _start_rows(self, start_state):
         """validated start_state of the plan calls: None, or contiguous float64 rows [N, state_dim] on the engine's device"""
@@ -518,35 +537,47 @@ class Engine:
 
     @_on_device
     def plan_shooting(self, H, K, seed, discount=1.0, nominal=None, sigma=None, start_state=None, sequence=False, length=False,
-                      dtype=None):
+                      dtype=None, value=None):
         """Random shooting in two launches (emei_plan_shooting): K candidate sequences of H steps per env are drawn in the lanes
         that score them from the current state (or `start_state` [N, state_dim] float64) and arg-maxed on the device.
         -> (best_action [N(, act_dim)], best_return float64 [N], best_index int32 [N][, best_sequence [H, N(, act_dim)]]
         [, best_length int32 [N]]): the first maximum of evaluate_sequences(sample_candidates(...)) per env, NaN returns below
-        everything.  The handle is left as it is.  Arguments as sample_candidates."""
+        everything.  The handle is left as it is.  Arguments as sample_candidates.
+        value= (a policy.DeepValueFunction): the candidates are scored as evaluate_sequences(..., value=) scores them
+        (emei_plan_shooting_value), and the winner, its return and its length are those of the bootstrapped returns."""
+        vs = self._plan_value(value, "plan_shooting")
         H, K, nominal, sigma, dtype = self._candidate_args(H, K, nominal, sigma, dtype)
         st = self._start_rows(start_state)
-        ws = self._workspace("_plan_ws", L.lib().emei_plan_shooting_workspace_bytes, K)
-        tail = self._act_tail
-        act = torch.empty((self.n_envs,) + tail, dtype=dtype, device=self.device)
-        seq = torch.empty((H, self.n_envs) + tail, dtype=dtype, device=self.device) if sequence else None
+        if vs is None:
+            ws = self._workspace("_plan_ws", L.lib().emei_plan_shooting_workspace_bytes, K)
+        else:
+            ws = self._workspace("_plan_value_ws", L.lib().emei_plan_value_workspace_bytes, K)
+        act = torch.empty((self.n_envs,) + self._act_tail, dtype=dtype, device=self.device)
+        seq = torch.empty((H, self.n_envs) + self._act_tail, dtype=dtype, device=self.device) if sequence else None
         ret = torch.empty(self.n_envs, dtype=torch.float64, device=self.device)
         idx = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
         ln = torch.empty(self.n_envs, dtype=torch.int32, device=self.device) if length else None
-        L.check(L.lib().emei_plan_shooting(self._h, H, K, _seed64(seed), _ptr(nominal), sigma, float(discount), _ptr(st),
-                                           _ptr(ws), _ptr(act), _ACT_DTYPES[dtype], _ptr(seq), _ptr(ret), _ptr(idx), _ptr(ln),
-                                           _stream()))
+        head = (self._h, H, K, _seed64(seed), _ptr(nominal), sigma, float(discount))
+        tail = (_ptr(st), _ptr(ws), _ptr(act), _ACT_DTYPES[dtype], _ptr(seq), _ptr(ret), _ptr(idx), _ptr(ln), _stream())
+        if vs is None:
+            L.check(L.lib().emei_plan_shooting(*head, *tail))
+        else:
+            L.check(L.lib().emei_plan_shooting_value(*head, C.byref(vs), *tail))
         return (act, ret, idx) + ((seq,) if sequence else ()) + ((ln,) if length else ())
 
     @_on_device
-    def plan_mppi(self, H, K, seed, temperature, discount=1.0, nominal=None, sigma=None, start_state=None, out=None, ess=False):
+    def plan_mppi(self, H, K, seed, temperature, discount=1.0, nominal=None, sigma=None, start_state=None, out=None, ess=False,
+                  value=None):
         """The MPPI update of a nominal sequence in two launches (emei_plan_mppi): the K candidates per env that
         plan_shooting(H, K, seed, nominal=, sigma=) scores are scored the same way, weighted by exp((return - best) / temperature)
         (NaN returns weigh 0, ties with the best 1) and averaged — the candidates redrawn on the device, never stored.
         -> (nominal_out float32 [H, N(, act_dim)], best_return float64 [N], best_index int32 [N][, ess float64 [N]]): the weighted
         mean (a mean inside the ctrlrange, or a Bernoulli probability for the discrete envs: the next call's `nominal`), plan_shooting's
         winner bit for bit, and the effective sample size (sum w)^2 / sum w^2.  out: a float32 tensor of nominal_out's shape to write
-        into; it may be `nominal` itself (in place).  The handle is left as it is.  Other arguments as sample_candidates."""
+        into; it may be `nominal` itself (in place).  The handle is left as it is.  Other arguments as sample_candidates.
+        value= (a policy.DeepValueFunction): MPPI with a terminal value (emei_plan_mppi_value) — the weights, the mean, the winner and
+        the ess use the returns evaluate_sequences(..., value=) gives; the winner is plan_shooting(..., value=)'s bit for bit."""
+        vs = self._plan_value(value, "plan_mppi")
         H, K, nominal, sigma, _ = self._candidate_args(H, K, nominal, sigma, None)
         temperature = float(temperature)
         st = self._start_rows(start_state)
@@ -555,12 +586,19 @@ class Engine:
             out = torch.empty(shape if nominal is None else tuple(nominal.shape), dtype=torch.float32, device=self.device)
         else:
             self._check_plan_out("out", out, shape, nominal, "nominal")
-        ws = self._workspace("_mppi_ws", L.lib().emei_plan_mppi_workspace_bytes, K)
+        if vs is None:
+            ws = self._workspace("_mppi_ws", L.lib().emei_plan_mppi_workspace_bytes, K)
+        else:
+            ws = self._workspace("_plan_value_ws", L.lib().emei_plan_value_workspace_bytes, K)
         ret = torch.empty(self.n_envs, dtype=torch.float64, device=self.device)
         idx = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
         es = torch.empty(self.n_envs, dtype=torch.float64, device=self.device) if ess else None
-        L.check(L.lib().emei_plan_mppi(self._h, H, K, _seed64(seed), _ptr(nominal), sigma, float(discount), temperature,
-                                       _ptr(st), _ptr(ws), _ptr(out), _ptr(ret), _ptr(idx), _ptr(es), _stream()))
+        head = (self._h, H, K, _seed64(seed), _ptr(nominal), sigma, float(discount))
+        tail = (temperature, _ptr(st), _ptr(ws), _ptr(out), _ptr(ret), _ptr(idx), _ptr(es), _stream())
+        if vs is None:
+            L.check(L.lib().emei_plan_mppi(*head, *tail))
+        else:
+            L.check(L.lib().emei_plan_mppi_value(*head, C.byref(vs), *tail))
         return (out, ret, idx) + ((es,) if ess else ())
 
     # -- planning around a feedback policy (emei_plan_policy) ---------------------------------------------------
@@ -747,7 +785,7 @@ class Engine:
 
     @_on_device
     def plan_cem(self, H, K, n_elites, seed, discount=1.0, nominal=None, sigma=None, start_state=None, out=None, out_sigma=None,
-                 elite_return=False):
+                 elite_return=False, value=None):
         """One cross-entropy-method iteration in two launches (emei_plan_cem): the K candidates per env that plan_shooting(H, K, seed,
         nominal=, sigma=) scores are scored the same way, the n_elites best per env — the planner's order: higher return first, NaN
         last, ties to the lower index — are selected on the device, redrawn and their mean and population standard deviation taken.
@@ -755,7 +793,10 @@ class Engine:
         -> (mean float32 [H, N(, act_dim)], std (the same shape; None for the discrete envs, whose mean is a Bernoulli probability),
         best_return float64 [N], best_index int32 [N][, elite_return float64 [N]: the return of the last candidate admitted]).
         out / out_sigma: float32 tensors to write mean / std into; they may be `nominal` / the sigma tensor themselves (in place).
-        The handle is left as it is.  Other arguments as sample_candidates."""
+        The handle is left as it is.  Other arguments as sample_candidates.
+        value= (a policy.DeepValueFunction): CEM with a terminal value (emei_plan_cem_value) — the elite set, the moments, the winner
+        and elite_return use the returns evaluate_sequences(..., value=) gives."""
+        vs = self._plan_value(value, "plan_cem")
         sigma_map = None
         if isinstance(sigma, torch.Tensor):
             H, K, nominal, _, _ = self._candidate_args(H, K, nominal, 1.0, None)
@@ -779,13 +820,19 @@ class Engine:
             out_sigma = torch.empty(like, dtype=torch.float32, device=self.device)
         else:
             self._check_plan_out("out_sigma", out_sigma, shape, sigma_map, "the sigma tensor")
-        ws = self._workspace("_cem_ws", L.lib().emei_plan_cem_workspace_bytes, K)
+        if vs is None:
+            ws = self._workspace("_cem_ws", L.lib().emei_plan_cem_workspace_bytes, K)
+        else:
+            ws = self._workspace("_plan_value_ws", L.lib().emei_plan_value_workspace_bytes, K)
         ret = torch.empty(self.n_envs, dtype=torch.float64, device=self.device)
         idx = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
         er = torch.empty(self.n_envs, dtype=torch.float64, device=self.device) if elite_return else None
-        L.check(L.lib().emei_plan_cem(self._h, H, K, n_elites, _seed64(seed), _ptr(nominal), sigma, _ptr(sigma_map),
-                                      float(discount), _ptr(st), _ptr(ws), _ptr(out), _ptr(out_sigma), _ptr(ret), _ptr(idx), _ptr(er),
-                                      _stream()))
+        head = (self._h, H, K, n_elites, _seed64(seed), _ptr(nominal), sigma, _ptr(sigma_map), float(discount))
+        tail = (_ptr(st), _ptr(ws), _ptr(out), _ptr(out_sigma), _ptr(ret), _ptr(idx), _ptr(er), _stream())
+        if vs is None:
+            L.check(L.lib().emei_plan_cem(*head, *tail))
+        else:
+            L.check(L.lib().emei_plan_cem_value(*head, C.byref(vs), *tail))
         return (out, out_sigma, ret, idx) + ((er,) if elite_return else ())
 
     @_on_device

@@ -286,14 +286,16 @@ class HipEnv(EmeiEnv):
         x = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
         return x.to(device=self.engine.device, dtype=dtype).contiguous()
 
-    def evaluate_action_sequences(self, actions, discount=1.0, start_state=None, final_obs=False):
+    def evaluate_action_sequences(self, actions, discount=1.0, start_state=None, final_obs=False, value=None):
         """The query a planner asks of the true dynamics (random shooting, CEM, MPPI; core.py:18-37,190-193 serve model-based
         callers with freeze() and get_batch_next_obs): K candidate action sequences per env scored from the envs' current
         states, or from `start_state` rows [num_envs, state_dim] float64, in one launch (Engine.evaluate_sequences).
         actions [H, num_envs, K(, act_dim)] -> (returns float64 [num_envs, K], lengths int32 [num_envs, K][, final_obs float32
         [num_envs, K, obs_dim]]): the discounted sum of rewards up to the first terminal step (included), that step + 1 (or H),
         the observation of that step.  No observation noise, TimeLimit or auto-reset; the env's state is left as it is.
-        NumPy input gives NumPy arrays, tensors give tensors."""
+        NumPy input gives NumPy arrays, tensors give tensors.
+        value= (an emei_amd.DeepValueFunction): a terminal value — every candidate that never terminated in its `horizon` steps gets
+        discount^horizon * V(final obs) on top of its return (ABI emei_evaluate_sequences_value); lengths and final_obs do not change."""
         import torch
 
         assert self.state is not None, "Call reset before using step method."  # base_control.py:67
@@ -305,7 +307,7 @@ class HipEnv(EmeiEnv):
         if eng.act_dim > 0:
             a = a.to(torch.float32)
         st = self._as_device(start_state, torch.float64)
-        out = eng.evaluate_sequences(a.contiguous(), discount=discount, start_state=st, final_obs=final_obs)
+        out = eng.evaluate_sequences(a.contiguous(), discount=discount, start_state=st, final_obs=final_obs, value=value)
         if isinstance(actions, torch.Tensor):
             return out
         return tuple(t.cpu().numpy() for t in out)
@@ -324,7 +326,7 @@ class HipEnv(EmeiEnv):
         return self.engine.evaluate_policies(policies, horizon, discount=discount, start_state=st, final_obs=final_obs)
 
     def plan_random_shooting(self, horizon, n_candidates, seed, discount=1.0, nominal=None, sigma=None, start_state=None,
-                             sequence=False, length=False, dtype=None):
+                             sequence=False, length=False, dtype=None, value=None):
         """Random-shooting MPC's planning half in two launches (Engine.plan_shooting, ABI emei_plan_shooting): per env,
         `n_candidates` action sequences of `horizon` steps are drawn on the device as a pure function of (seed, env, candidate),
         scored as evaluate_action_sequences scores them, and the first best one is returned —
@@ -333,7 +335,9 @@ class HipEnv(EmeiEnv):
         (discrete) or means [horizon, num_envs, act_dim] of Gaussians with `sigma`, clipped to the action space (continuous);
         None: fair coins / uniform on the action space.  best_action has the dtype step() takes (int64 / float32) unless `dtype`
         says otherwise.  A NumPy `nominal` or `start_state` gives NumPy arrays; otherwise tensors, which step() takes as they are.
-        The env's state is left as it is."""
+        The env's state is left as it is.
+        value= (an emei_amd.DeepValueFunction): the candidates are scored with the terminal value of evaluate_action_sequences(...,
+        value=) (ABI emei_plan_shooting_value)."""
         import torch
 
         assert self.state is not None, "Call reset before using step method."  # base_control.py:67
@@ -341,11 +345,11 @@ class HipEnv(EmeiEnv):
         as_numpy = isinstance(nominal, np.ndarray) or isinstance(start_state, np.ndarray)
         nom, st = self._as_device(nominal, torch.float32), self._as_device(start_state, torch.float64)
         out = eng.plan_shooting(horizon, n_candidates, seed, discount=discount, nominal=nom, sigma=sigma, start_state=st,
-                                sequence=sequence, length=length, dtype=dtype)
+                                sequence=sequence, length=length, dtype=dtype, value=value)
         return tuple(t.cpu().numpy() for t in out) if as_numpy else out
 
     def plan_mppi(self, horizon, n_candidates, seed, temperature, discount=1.0, nominal=None, sigma=None, start_state=None,
-                  out=None, ess=False):
+                  out=None, ess=False, value=None):
         """MPPI's update of a nominal action sequence in two launches (Engine.plan_mppi, ABI emei_plan_mppi): the candidates of
         plan_random_shooting(horizon, n_candidates, seed, nominal=, sigma=) are scored as there, weighted by
         exp((return - best return) / temperature) and averaged on the device —
@@ -353,7 +357,9 @@ class HipEnv(EmeiEnv):
         [, ess float64 [num_envs]]).  nominal_out is the next call's `nominal`: means inside the action space (continuous) or
         Bernoulli probabilities (discrete; clamp them away from 0 and 1 to keep exploring).  out: a float32 tensor to write
         nominal_out into, `nominal` itself included (tensors only).  A NumPy `nominal` or `start_state` gives NumPy arrays;
-        otherwise tensors.  The env's state is left as it is."""
+        otherwise tensors.  The env's state is left as it is.
+        value= (an emei_amd.DeepValueFunction): MPPI with a terminal value, the planner of TD-MPC without its actor — the weights,
+        the mean, the winner and the ess use the returns of evaluate_action_sequences(..., value=) (ABI emei_plan_mppi_value)."""
         import torch
 
         assert self.state is not None, "Call reset before using step method."  # base_control.py:67
@@ -361,7 +367,7 @@ class HipEnv(EmeiEnv):
         as_numpy = isinstance(nominal, np.ndarray) or isinstance(start_state, np.ndarray)
         nom, st = self._as_device(nominal, torch.float32), self._as_device(start_state, torch.float64)
         res = eng.plan_mppi(horizon, n_candidates, seed, temperature, discount=discount, nominal=nom, sigma=sigma, start_state=st,
-                            out=out, ess=ess)
+                            out=out, ess=ess, value=value)
         return tuple(t.cpu().numpy() for t in res) if as_numpy else res
 
     def plan_policy(self, horizon, n_candidates, policy, noise, discount=1.0, temperature=None, start_state=None, returns=False,
@@ -458,7 +464,7 @@ class HipEnv(EmeiEnv):
         return tuple(t.cpu().numpy() for t in out + (nom,))
 
     def plan_cem(self, horizon, n_candidates, n_elites, seed, discount=1.0, nominal=None, sigma=None, start_state=None, iterations=1,
-                 elite_return=False):
+                 elite_return=False, value=None):
         """The cross-entropy method's refit of a sampling distribution over action sequences, two launches per iteration
         (Engine.plan_cem, ABI emei_plan_cem): iteration j draws the candidates of plan_random_shooting(horizon, n_candidates,
         seed + j, nominal=mean, sigma=std), scores them as there, and replaces (mean, std) by the mean and the population standard
@@ -467,7 +473,9 @@ class HipEnv(EmeiEnv):
         probability), best_return float64 [num_envs], best_index int32 [num_envs][, elite_return float64 [num_envs]]) of the LAST
         iteration.  nominal / sigma: the first iteration's distribution — sigma a float or an array of nominal's shape; None / None:
         fair coins / uniform on the action space.  They are copied, the caller's arrays are not written.  A NumPy `nominal`, `sigma`
-        or `start_state` gives NumPy arrays; otherwise tensors.  The env's state is left as it is."""
+        or `start_state` gives NumPy arrays; otherwise tensors.  The env's state is left as it is.
+        value= (an emei_amd.DeepValueFunction): every iteration scores its candidates with the terminal value of
+        evaluate_action_sequences(..., value=) (ABI emei_plan_cem_value)."""
         import torch
 
         assert self.state is not None, "Call reset before using step method."  # base_control.py:67
@@ -485,7 +493,7 @@ class HipEnv(EmeiEnv):
         for j in range(int(iterations)):
             res = eng.plan_cem(horizon, n_candidates, n_elites, int(seed) + j, discount=discount, nominal=mean, sigma=std,
                                start_state=st, out=mean, out_sigma=std if isinstance(std, torch.Tensor) else None,
-                               elite_return=elite_return)
+                               elite_return=elite_return, value=value)
             mean, std = res[0], res[1]
         return tuple(None if t is None else t.cpu().numpy() for t in res) if as_numpy else res
 

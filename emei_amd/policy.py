@@ -244,7 +244,20 @@ class DeepValueFunction:
                 raise ValueError(f"{name}={v} is outside [1, {L.POLICY_DEEP_MAX_HIDDEN}]")
         self.obs_dim = int(self.w1.shape[1])
 
-    to = DeepMLPPolicy.to
+    @classmethod
+    def from_module(cls, seq):
+        """torch.nn.Sequential(Linear, ReLU, Linear, ReLU, Linear(hidden2, 1)) -> DeepValueFunction, as MLPPolicy.from_module reads an
+        actor; a value has no output clause, so nothing may follow the last Linear."""
+        mods = list(seq)
+        lin, relu = torch.nn.Linear, torch.nn.ReLU
+        if [type(m) for m in mods] != [lin, relu, lin, relu, lin]:
+            raise ValueError("DeepValueFunction.from_module takes Linear, ReLU, Linear, ReLU, Linear(hidden2, 1); got "
+                             + ", ".join(type(m).__name__ for m in mods))
+        if any(m.bias is None for m in mods[::2]):
+            raise ValueError("from_module: every Linear needs a bias")
+        return cls(mods[4].weight, mods[4].bias, mods[2].weight, mods[2].bias, mods[0].weight, mods[0].bias)
+
+    to = DeepMLPPolicy.to  # to(device): the weights moved in place, returns self
 
     def bind(self, engine):
         """check obs_dim against `engine`'s env and move the weights to its device"""

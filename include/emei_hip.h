@@ -68,7 +68,11 @@ extern "C" {
  *    emei_mpc_policy_workspace_bytes, emei_mpc_policy (policy-guided control episodes in one launch: per control step emei_plan_policy
  *    around a one-layer struct emei_policy under a noise seed that advances by seed_stride, the best or the weighted-mean first
  *    action, emei_step and auto-reset, for the envs emei_mpc_mppi serves), EMEI_KERNEL_PEND_MPC_POLICY / EMEI_KERNEL_BODY_MPC_POLICY
- *    in an enum of their own (enum emei_kernel_id_mpc_policy). */
+ *    in an enum of their own (enum emei_kernel_id_mpc_policy);
+ *    emei_evaluate_sequences_value, emei_plan_shooting_value, emei_plan_mppi_value, emei_plan_cem_value and
+ *    emei_plan_value_workspace_bytes (the four open-loop plan calls with emei_plan_policy_deep's terminal value — a struct
+ *    emei_policy_deep with one output, added to the return of every candidate that never terminated; the handle is untouched, no
+ *    kernel id). */
 #define EMEI_ABI_VERSION 8
 
 #if defined(__GNUC__)
@@ -972,6 +976,55 @@ EMEI_API int emei_mpc_policy(emei_env* h, int32_t n_steps, int32_t horizon, int3
                              double temperature, void* workspace, void* actions_out, int action_dtype, float* obs_out,
                              float* reward_out, uint8_t* done_out, double* plan_return_out, int32_t* plan_index_out, double* ess_out,
                              uint32_t flags, void* stream);
+
+/* A TERMINAL VALUE for the open-loop planners: emei_evaluate_sequences, emei_plan_shooting, emei_plan_mppi and emei_plan_cem with a
+ * learned value of the observation the horizon ends in on top of every candidate's return — MPPI with a terminal cost, PETS /
+ * PlaNet-style CEM with a critic, the planner of TD-MPC and POLO without an actor — at one network evaluation per candidate, not one
+ * per step.  `value` is a struct emei_policy_deep with n_out = 1, as emei_plan_policy_deep's: w1 [hidden1, obs_dim], b1 [hidden1],
+ * w2 [hidden2, hidden1], b2 [hidden2], w3 [1, hidden2], b3 [1]; the widths are its own, each in [1, EMEI_POLICY_DEEP_MAX_HIDDEN];
+ * out_mode is ignored; its pointers are DEVICE pointers, read during the launch and not retained.  `value` is required here: without
+ * one, call the plain entry point.
+ *
+ * Semantics (normative).  Each of the four calls is its plain counterpart clause for clause — the candidates (a pure function of
+ * (seed, g, k)), the start-state rule, the per-step arithmetic, L(i, k), the untouched handle, "neither allocates nor synchronises"
+ * — with one clause added:
+ *   Terminal value.  A candidate that set no terminal bit in any of its `horizon` steps gets
+ *       ret = ret + g_H * (double)v,
+ *   where g_H is the float64 running product of the discount after `horizon` multiplications and v = (float)y_0 of the value network
+ *   in emei_rollout_policy_deep's arithmetic (float64 ascending sums, h1 / h2 rounded to float32 before the ReLU, NaN gives 0),
+ *   evaluated on x_H, the float32 observation row that step horizon - 1 emits — the row final_obs_out holds for that candidate.  The
+ *   product is rounded to float64 and then added (no fused multiply-add).  There is no output clause: a NaN y_0 makes the return NaN,
+ *   and the planner's order puts it last.  A candidate that terminated gets nothing, at whichever step, the last one included (its
+ *   L equals horizon too: L does not tell the two apart).  L and final_obs_out are unchanged by the value.
+ * Everything downstream uses the bootstrapped returns: return_out, the planner's order, (k*, r*) and the best_* outputs; the MPPI
+ * weights, mean and ESS; the CEM elite set, moments and elite_return_out.  The candidates do not depend on the returns, so the second
+ * launches are the plain calls' (plan_finish, plan_mppi_finish, plan_cem_finish redraw the same candidates).
+ * Kernels: pend_plan_value_kernel / body_plan_value_kernel — the loop of pend_plan_kernel / body_plan_kernel, one lane per candidate
+ * j = i * n_candidates + k, launched as ONE-WAVE blocks whose dynamic LDS is the wave's h1 tile (64 KiB at the cap); the value is
+ * evaluated after the loop, skipped by a wave all of whose candidates terminated.  The handle is untouched, no kernel id.
+ * workspace (the three planners): emei_plan_value_workspace_bytes(n_envs, n_candidates) bytes of device memory, 16-byte aligned,
+ * contents irrelevant before and after; it equals emei_plan_cem_workspace_bytes (emei_plan_shooting_value keeps every return too)
+ * and is negative where that is.  Host only, no handle, no HIP call.
+ * EMEI_ERR_INVALID before any HIP call, each message naming the argument, in this order: the plain call's scalar checks in its order
+ * (horizon, n_candidates[, n_elites before], discount[, temperature]); NULL value; value.struct_size, value.hidden1, value.hidden2,
+ * value.reserved; a NULL handle; NULL value w1, b1, w2, b2, w3, b3, in this order; the plain call's remaining checks in its order.
+ * EMEI_ERR_STATE where the plain call gives it. */
+EMEI_API int64_t emei_plan_value_workspace_bytes(int64_t n_envs, int32_t n_candidates);
+EMEI_API int emei_evaluate_sequences_value(emei_env* h, int32_t horizon, int32_t n_candidates, const void* actions, int action_dtype,
+                                           double discount, const emei_policy_deep* value, const double* start_state,
+                                           double* return_out, int32_t* length_out, float* final_obs_out, void* stream);
+EMEI_API int emei_plan_shooting_value(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal,
+                                      double sigma, double discount, const emei_policy_deep* value, const double* start_state,
+                                      void* workspace, void* best_action_out, int action_dtype, void* best_sequence_out,
+                                      double* best_return_out, int32_t* best_index_out, int32_t* best_length_out, void* stream);
+EMEI_API int emei_plan_mppi_value(emei_env* h, int32_t horizon, int32_t n_candidates, uint64_t seed, const float* nominal, double sigma,
+                                  double discount, const emei_policy_deep* value, double temperature, const double* start_state,
+                                  void* workspace, float* nominal_out, double* best_return_out, int32_t* best_index_out, double* ess_out,
+                                  void* stream);
+EMEI_API int emei_plan_cem_value(emei_env* h, int32_t horizon, int32_t n_candidates, int32_t n_elites, uint64_t seed, const float* nominal,
+                                 double sigma, const float* sigma_map, double discount, const emei_policy_deep* value,
+                                 const double* start_state, void* workspace, float* mean_out, float* std_out, double* best_return_out,
+                                 int32_t* best_index_out, double* elite_return_out, void* stream);
 
 /* Which kernel the LAST emei_step / emei_rollout of this handle launched (enum emei_kernel_id): a debug /
  * test getter, so that a parity test can assert that the path it checked is the path bench.py times. */
